@@ -14,12 +14,14 @@ operating point: more steps are more groups of 20, not larger groups) as one lau
 host thread through the library's stream-ordered path (throughput-mode handles: one code stream per lane, range
 errors deferred, finalize on the device, the decoder reads the encoder's device-resident strings): a 512-stream
 step is 8 waves, so the chip only fills with many steps resident at once.  Every slot of a group codes its own seeded
-tensor.  The timed region contains EXACTLY `--steps` complete steps; `single_batch` in the output is one step at a
-time (BASELINE config 2 as literally written), `saturation` the rate at 1 ... 128 batches per group.  After the timed
-region every step's decoded tensor is compared with its input, and the bytes of EVERY distinct input with the CPU
-reference's bytes (sha256 over all 512 streams of each).
+tensor.  `--warmup` untimed steps of the same pattern (at least two launch groups) come first; the timed region then
+contains EXACTLY `--steps` complete steps, and `value` / `ms_per_step` are that region's.  After it, every step's
+EntropyDecodeFinalize flags are checked, and the last step of every distinct input decodes exactly to that input.
+`--dump-outputs DIR` writes what the last timed step returned (strings, offsets, decoded symbols, flags) as .npy
+files; the inputs are seeded, so two builds compare output for output.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3              (the headline alone)
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full       (every figure below)
     python bench.py --gpus N ...            (no launcher around it: starts the N ranks itself, fails without N devices)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
@@ -27,7 +29,10 @@ Multi-GPU: the batch dimension shards (independent code streams), so every rank
 codes its own 512-stream shard (weak scaling); no data-path collective, only the
 barrier + max-reduce of the timing.
 
-The same line carries, as sub-objects (N = 1 only; `--no-extras` drops them):
+With `--full` the line also carries the per-kernel figures (`kernels_ms`, `kernels_ms_in_flight` and the roofline,
+from `--repeats` profiled timed regions of their own), GDN, the CPU reference's rate and the bytes of EVERY distinct
+input compared with its bytes (sha256 over all 512 streams of each), and, as sub-objects (N = 1 only; `--no-extras`
+drops all but single_batch):
   single_batch  ONE 512-stream batch at a time (BASELINE config 2 as literally written), both families;
   escapes       the same --steps command on two other input laws: 1 % of the symbols replaced by far-out values
                 (SURVEY.md §8d's second run) and the overflow draws folded away (no escape codes at all);
@@ -1098,6 +1103,120 @@ def model_workload(args, world, rank, device, distributed):
         dist.destroy_process_group()
 
 
+def run_steps(lookup_t, slots, side_streams, total_steps, depth, mode, sink=None, distributed=False):
+    """Exactly `total_steps` steps, `depth` in flight, enqueued by this one thread; returns (seconds, per-step results,
+    seconds to enqueue).  Step k codes slots[k % depth].  Only the last `depth` steps (one per distinct input) keep
+    their handles and decoded tensors; older steps keep their EntropyDecodeFinalize flags alone, their buffers go back
+    to the pools in stream order — a step holds ~140 MB, so a long run would otherwise fill the device."""
+    if distributed:
+        import torch.distributed as dist
+    torch.cuda.synchronize()
+    if distributed:
+        dist.barrier()
+        torch.cuda.synchronize()
+    results = []
+    light = 0                                   # results[:light] hold their flags alone
+
+    def lighten():
+        nonlocal light
+        # (strings copied to the host on the sink's stream are read after this thread moves on: keep those handles)
+        while sink is None and light < len(results) - depth:
+            h, d, dec_r, ok_r, slot = results[light]
+            results[light] = (None, None, None, ok_r, slot)
+            light += 1
+
+    t0 = time.perf_counter()
+    if depth <= 1:
+        for k in range(total_steps):
+            results.append(one_step(lookup_t, slots[0], mode) + (0,))
+            torch.cuda.current_stream().synchronize()
+            lighten()
+    else:
+        # groups of `depth` steps, one launch per group and direction
+        for g, k0 in enumerate(range(0, total_steps, depth)):
+            idx = [k % depth for k in range(k0, min(k0 + depth, total_steps))]
+            with torch.cuda.stream(side_streams[g % len(side_streams)]):
+                for r, slot in zip(step_group(lookup_t, [slots[i] for i in idx], mode, sink), idx):
+                    results.append(r + (slot,))
+                lighten()
+    t_enqueued = time.perf_counter() - t0
+    torch.cuda.synchronize()
+    if distributed:
+        dist.barrier()
+        torch.cuda.synchronize()
+    return time.perf_counter() - t0, results, t_enqueued
+
+
+def verify(results, slots):
+    """Parity gate (outside the timed region): every step's sanity flags are true; the steps that kept their handles
+    (the last one of every distinct input) decode exactly to their input and have no deferred error pending."""
+    for h, d, dec_r, ok_r, slot in results:
+        if h is not None:
+            tfc.entropy_decode_status(d)
+            tfc.entropy_encode_status(h)
+        assert bool(ok_r.all()), "EntropyDecodeFinalize reported a failed stream"
+        if h is not None:
+            assert torch.equal(dec_r.reshape(STREAMS, ELEMS), slots[slot]), "decode(encode(x)) != x"
+
+
+def headline_run(args, lookup, lookup_t, device, rank, distributed):
+    """The headline figure alone: `--warmup` untimed steps of the timed pattern (at least two launch groups, so that the
+    pools hold the buffers the timed groups ask for: a fresh 50-100 MB driver allocation per buffer would otherwise be
+    timed instead of the coder), then ONE timed region of exactly `--steps` steps, `--inflight` per launch group, with
+    nothing else on the GPU and no per-kernel events.  Returns the measurements (every rank) — rank 0 formats."""
+    inflight = max(1, min(args.inflight, args.steps))
+    slots = [sample_symbols_device(lookup, 1000 * rank + k, device, args.escape_fraction) for k in range(inflight)]
+    side_streams = [torch.cuda.Stream(device=device)]
+    mode = "throughput" if inflight > 1 else "latency"
+    run = lambda n: run_steps(lookup_t, slots, side_streams, n, inflight, mode, distributed=distributed)
+    _, res, _ = run(max(args.warmup, min(args.steps, 2 * inflight)))
+    verify(res, slots)
+    del res
+    elapsed, results, t_enqueued = run(args.steps)
+    elapsed_local = elapsed
+    if distributed:                             # the region's time is the slowest rank's
+        import torch.distributed as dist
+        t = torch.tensor([elapsed], dtype=torch.float64, device=device)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t[0].item())
+    verify(results, slots)
+    slot0 = next(r for r in results if r[0] is not None and r[4] == 0)
+    return {"inflight": inflight, "elapsed": elapsed, "elapsed_local": elapsed_local, "t_enqueued": t_enqueued,
+            "total_bytes": tfc.entropy_encode_status(slot0[0]), "escape_share": escape_share(lookup, slots[0]),
+            "last": results[-1]}
+
+
+DUMP_BYTES = 60 << 20       # --dump-outputs: all files together stay below this
+
+
+def dump_sample(a, k, seed):
+    """`a` flattened, or a fixed seeded sample of k of its elements (in order of position) when it has more."""
+    a = np.asarray(a).reshape(-1)
+    if a.size <= k:
+        return a
+    return a[np.sort(np.random.default_rng(seed).choice(a.size, k, replace=False))]
+
+
+def dump_outputs(path, last):
+    """What a caller of the timed path received from its last step, as .npy files under `path`: the encoder's strings
+    (all streams' bytes, packed, and the stream offsets), the decoded symbols and EntropyDecodeFinalize's flags."""
+    h, _, decoded, ok, _ = last
+    blob, offsets = tfc.device_strings(h)
+    offsets = offsets.cpu().numpy()
+    data = blob[:int(offsets[-1])].cpu().numpy()
+    decoded_k = 1 << 19                                     # float64: 4 MiB
+    arrays = {
+        "string_offsets": offsets.astype(np.float64),
+        "decode_ok": ok.cpu().numpy().astype(np.float32),
+        "decoded": dump_sample(decoded.cpu().numpy(), decoded_k, seed=1).astype(np.float64),
+    }
+    room = (DUMP_BYTES - sum(a.nbytes for a in arrays.values())) // 4
+    arrays["strings"] = dump_sample(data, room, seed=2).astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def c2_run(args, lookup, lookup_t, device, world, rank, distributed, escape_fraction, steps, inflight,
            serial=True, fold=False, to_host=False, repeats=1):
     """The coder round trip at BASELINE config 2 with `escape_fraction` of the symbols out of range: exactly
@@ -1114,51 +1233,18 @@ def c2_run(args, lookup, lookup_t, device, world, rank, distributed, escape_frac
     sink = HostSink(device, inflight) if to_host else None
     torch.cuda.synchronize()
 
-    def run_steps(total_steps, depth, mode):
-        """Exactly `total_steps` steps, `depth` in flight, enqueued by this one thread; returns
-        (seconds, per-step results)."""
-        torch.cuda.synchronize()
-        if distributed:
-            dist.barrier()
-            torch.cuda.synchronize()
-        results = []
-        t0 = time.perf_counter()
-        if depth <= 1:
-            for k in range(total_steps):
-                results.append(one_step(lookup_t, slots[0], mode) + (0,))
-                torch.cuda.current_stream().synchronize()
-        else:
-            # groups of `depth` steps, one launch per group and direction
-            for g, k0 in enumerate(range(0, total_steps, depth)):
-                idx = [k % depth for k in range(k0, min(k0 + depth, total_steps))]
-                with torch.cuda.stream(side_streams[g % len(side_streams)]):
-                    for r, slot in zip(step_group(lookup_t, [slots[i] for i in idx], mode, sink), idx):
-                        results.append(r + (slot,))
-        t_enqueued = time.perf_counter() - t0
-        torch.cuda.synchronize()
-        if distributed:
-            dist.barrier()
-            torch.cuda.synchronize()
-        return time.perf_counter() - t0, results, t_enqueued
-
-    def verify(results):
-        """Parity gate (outside the timed region): every step's round trip is exact, the sanity flags
-        are true, and no deferred error is pending."""
-        for h, d, dec_r, ok_r, slot in results:
-            tfc.entropy_decode_status(d)
-            tfc.entropy_encode_status(h)
-            assert bool(ok_r.all()), "EntropyDecodeFinalize reported a failed stream"
-            assert torch.equal(dec_r.reshape(STREAMS, ELEMS), slots[slot]), "decode(encode(x)) != x"
+    def run_steps_(total_steps, depth, mode):
+        return run_steps(lookup_t, slots, side_streams, total_steps, depth, mode, sink, distributed)
 
     flight_mode = "throughput" if inflight > 1 else "latency"
-    _, res, _ = run_steps(max(min(args.warmup, 3), 1), 1, "latency")
-    verify(res)
+    _, res, _ = run_steps_(max(min(args.warmup, 3), 1), 1, "latency")
+    verify(res, slots)
     if inflight > 1:
         # the timed pattern once, untimed: primes both streams and the stream-ordered memory pool with
         # exactly the buffers the timed region asks for (a fresh 50-100 MB driver allocation per buffer
         # would otherwise be timed instead of the coder)
-        _, res, _ = run_steps(steps, inflight, flight_mode)
-        verify(res)
+        _, res, _ = run_steps_(steps, inflight, flight_mode)
+        verify(res, slots)
     del res
     torch.cuda.synchronize()
 
@@ -1174,11 +1260,11 @@ def c2_run(args, lookup, lookup_t, device, world, rank, distributed, escape_frac
                 continue
             _lib.lib().tfc_profile_enable(1)
             n = min(steps, 5 if mode == "latency" else 2)
-            sec, results, _ = run_steps(n, 1, mode)
+            sec, results, _ = run_steps_(n, 1, mode)
             enc_ms, enc_n = profile_query("enc_kernel")
             dec_ms, dec_n = profile_query("dec_kernel")
             _lib.lib().tfc_profile_enable(0)
-            verify(results)
+            verify(results, slots)
             del results
             m[key] = {"seconds": sec, "steps": n, "enc_ms": enc_ms / max(enc_n, 1), "dec_ms": dec_ms / max(dec_n, 1)}
     # the timed region: exactly `steps` steps
@@ -1189,9 +1275,9 @@ def c2_run(args, lookup, lookup_t, device, world, rank, distributed, escape_frac
     results = None
     for _ in range(max(1, repeats)):
         if results is not None:
-            verify(results)
+            verify(results, slots)
             del results
-        e, results, t_enqueued = run_steps(steps, inflight, flight_mode)
+        e, results, t_enqueued = run_steps_(steps, inflight, flight_mode)
         reps_local.append(e)
         if distributed:                         # every region's time is the slowest rank's
             t = torch.tensor([e], dtype=torch.float64, device=device)
@@ -1209,11 +1295,11 @@ def c2_run(args, lookup, lookup_t, device, world, rank, distributed, escape_frac
         if cnt:
             stages[name] = ms / cnt
     _lib.lib().tfc_profile_enable(0)
-    verify(results)
+    verify(results, slots)
     # every distinct input's bytes (sha256 of the packed blob and of its offsets), for the comparison with the CPU reference
     shas = {}
     for r in results:
-        if r[4] not in shas:
+        if r[0] is not None and r[4] not in shas:
             shas[r[4]] = handle_hashes(r[0])
     del results
     if sink is not None:
@@ -1402,11 +1488,20 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: per-kernel, roofline and single-batch figures, the CPU "
+                         "reference baseline and byte comparison, GDN, and (N = 1) the saturation / strings_to_host / "
+                         "escapes / conv / training / models sub-objects.  Off: the line holds the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the encoder's strings and offsets, "
+                         "the decoded symbols, the decoders' flags) to DIR/<name>.npy in float32 / float64; rank 0's "
+                         "shard, a fixed seeded sample where an array is large (at most 60 MiB in all)")
     ap.add_argument("--repeats", type=int, default=5,
-                    help="timed regions of --steps steps each (barrier + synchronize around every one); the median is `value`")
+                    help="--full, --leg: profiled timed regions of --steps steps each (barrier + synchronize around every "
+                         "one) for the per-kernel figures; the median is the leg's `value`")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the headline measurement (no single_batch / escapes / models / conv sub-objects)")
+                    help="with --full: no single_batch / escapes / models / conv sub-objects")
     ap.add_argument("--inflight", type=int, default=20,
                     help="batches per launch group (one host thread; 1 = one batch at a time): the headline's operating point. "
                          "FIXED at 20 — `value` is the rate of groups of 20 batches whatever --steps is (fewer steps than "
@@ -1440,6 +1535,8 @@ def main():
                     help="diagnostic for a one-GPU box: run the single rank inside an RCCL process group of world size 1, "
                          "so that the model workloads' per-step gather (and every other distributed branch) executes")
     args = ap.parse_args()
+    if args.dump_outputs and (args.workload != "c2" or args.leg != "all"):
+        ap.error("--dump-outputs: the c2 headline only (no --workload, no --leg)")
 
     if maybe_spawn(args):
         return
@@ -1500,13 +1597,12 @@ def main():
         if distributed:
             dist.destroy_process_group()
         return
-    m = c2_run(args, lookup, lookup_t, device, world, rank, distributed, args.escape_fraction, args.steps,
-               args.inflight, serial=True, repeats=args.repeats)
-    inflight, elapsed, total_bytes = m["inflight"], m["elapsed"], m["total_bytes"]
+    h = headline_run(args, lookup, lookup_t, device, rank, distributed)
+    inflight, elapsed, total_bytes = h["inflight"], h["elapsed"], h["total_bytes"]
     per_rank = None
     if distributed:
         # every rank's own rate and byte total, so that the N = 1 SCALE value can be checked against BENCH
-        mine = torch.tensor([STREAMS * PIXELS_PER_STREAM / 1e6 / (m["elapsed_local"] / args.steps), float(total_bytes)],
+        mine = torch.tensor([STREAMS * PIXELS_PER_STREAM / 1e6 / (h["elapsed_local"] / args.steps), float(total_bytes)],
                             dtype=torch.float64, device=device)
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
@@ -1515,34 +1611,13 @@ def main():
                     "note": "each rank's own rate over its own clock (value uses the slowest rank's) and the byte total "
                             "of its slot-0 batch; ranks code differently seeded batches"}
 
+    out = None
+    lanes = inflight > 1
+    symbols = STREAMS * ELEMS
+    pixels_all = world * STREAMS * PIXELS_PER_STREAM
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
-        pixels_all = world * STREAMS * PIXELS_PER_STREAM
         value_mpix = pixels_all / 1e6 / (elapsed / args.steps)
-        symbols = STREAMS * ELEMS
-        enc_avg, dec_avg = m["serial"]["enc_ms"], m["serial"]["dec_ms"]     # a launch has the GPU to itself
-        enc_tr, dec_tr = m["enc_tr"], m["dec_tr"]                           # timed region
-        # algorithmic bytes per launch: encode reads 4 B/symbol and
-        # writes the code bytes; decode reads the code bytes and writes 4 B/symbol.
-        alg_dec = 4 * symbols + total_bytes
-        alg_enc = 4 * symbols + total_bytes
-        lanes = inflight > 1
-        jobs_per_launch = min(inflight, 64) if lanes else 1      # steps coded by one launch of the kernel
-        dom, dom_ms, dom_bytes = ("dec_kernel", dec_tr, alg_dec) if dec_tr >= enc_tr else (
-            "enc_kernel", enc_tr, alg_enc)
-        dom_bytes *= jobs_per_launch
-        achieved = dom_bytes / 1e9 / (dom_ms / 1e3) if dom_ms > 0 else 0.0
-        dom_symbol = {("dec_kernel", True): "dec_lanes_kernel", ("enc_kernel", True): "enc_lanes_kernel",
-                      ("dec_kernel", False): "dec_fast_kernel", ("enc_kernel", False): "enc_fast_kernel"}[(dom, lanes)]
-        stages = m.get("stages") or {}
-        if lanes and stages:
-            # throughput-mode calls run the pipelined kernels of csrc/range_pipe.h: the dominant KERNEL is one stage
-            # (dec_parse_next runs beside dec_chain from its first released rows to its last: its span is the chain's)
-            stage = max((k for k in stages if k != "dec_parse_next"), key=stages.get)
-            dom_symbol, dom_ms = stage + "_kernel", stages[stage]
-            dom_bytes = (alg_dec if stage.startswith("dec") else alg_enc) * jobs_per_launch
-            achieved = dom_bytes / 1e9 / (dom_ms / 1e3)
-        ser, ser_l = m["serial"], m["serial_lanes"]
         out = {
             "metric": "Mpixels/s encode+decode round-trip (bit-exact)",
             "value": round(value_mpix, 2),
@@ -1551,7 +1626,6 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 4),
-            "timed_regions_ms_per_step": [round(1e3 * v / args.steps, 4) for v in m["repetitions"]],
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -1565,145 +1639,198 @@ def main():
                 "input_law": "SURVEY 8(d): uniform 12-bit draws inverted through each row's CDF, overflow bucket included "
                              "(the rows' tail mass 2^-8 takes the Elias-gamma escape path)" +
                              (f"; {args.escape_fraction:g} of the symbols replaced by far-out values" if args.escape_fraction else ""),
-                "symbols_on_the_escape_path": round(m["escape_share"], 5),
+                "symbols_on_the_escape_path": round(h["escape_share"], 5),
                 "parallelism": f"batch-sharded x{world}",
                 "steps_in_flight": inflight,
                 "launch": "the coding calls of the steps in flight are one launch per direction "
                           "(tfc_encoder_encode_many / tfc_decoder_decode_many); every step keeps its own handles and strings",
                 "host_threads": 1,
-                "timing": f"{len(m['repetitions'])} timed regions of exactly --steps steps, each between its own barrier + "
-                          "synchronize; value / ms_per_step = their median, timed_regions_ms_per_step = all of them",
+                "timing": "one timed region of exactly --steps steps between its own barrier + synchronize, after --warmup "
+                          "untimed steps of the same pattern (at least two launch groups) and with no per-kernel events; "
+                          "value / ms_per_step = that region",
                 "strings": "stay in HBM inside their handles in the timed region (device finalize; the decoders read them "
-                           "in place); sub-object strings_to_host: the same command with every string copied to pinned "
-                           "host memory inside the timed region",
+                           "in place); sub-object strings_to_host (--full): the same command with every string copied to "
+                           "pinned host memory inside the timed region",
                 "distinct_inputs": inflight,
                 "library_mode": "TFC_MODE_THROUGHPUT handles (one code stream per lane), deferred errors, "
                                 "device finalize" if lanes else "TFC_MODE_LATENCY handles (one wave per stream)",
                 "operating_point": f"{inflight} batches (= {inflight * STREAMS} streams, {inflight * STREAMS // 64} chain waves) per "
                                    "launch group — fixed by --inflight (default 20), NOT by --steps: more steps are more "
                                    "groups of the same size.  A stream is a strict chain, so a group takes the same time for "
-                                   "1 ... ~100 batches; `saturation` gives the rate at 1, 2, 4, 8, 20, 64, 128 batches per "
-                                   "group and `single_batch` BASELINE config 2 as literally written (one batch at a time)",
+                                   "1 ... ~100 batches; with --full, `saturation` gives the rate at 1, 2, 4, 8, 20, 64, 128 "
+                                   "batches per group and `single_batch` BASELINE config 2 as literally written (one batch at a time)",
+                "parity": "after the timed region: every step's EntropyDecodeFinalize flags; decode == input and no deferred "
+                          "error on the last step of every distinct input",
             },
             "bits_per_pixel": round(8.0 * total_bytes / (STREAMS * PIXELS_PER_STREAM), 5),
             "bits_per_symbol": round(8.0 * total_bytes / symbols, 4),
             "gsymbols_per_s_roundtrip": round(world * symbols / 1e9 / (elapsed / args.steps), 3),
-            "host_enqueue_ms_per_step": round(1e3 * m["t_enqueued"] / args.steps, 4),
-            "kernels_ms": {"enc_kernel": round(enc_avg, 4), "dec_kernel": round(dec_avg, 4),
-                           "note": "latency-mode kernels, one launch at a time"},
-            "kernels_ms_in_flight": {"enc_kernel": round(enc_tr, 4), "dec_kernel": round(dec_tr, 4),
-                                     "stages": {k: round(v, 4) for k, v in stages.items()},
-                                     "note": "enc_kernel / dec_kernel: all launches of an encode / decode call of the group; "
-                                             "stages: its kernels (csrc/range_pipe.h) — enc_chain runs beside enc_expand and "
-                                             "dec_parse_next beside dec_chain on a second stream, dec_parse is the pass behind the chain"},
-            "single_batch": {
-                "note": "BASELINE config 2 as literally written: ONE 512-stream batch at a time, host waits for every step",
-                "latency_mode": {"ms_per_step": round(1e3 * ser["seconds"] / ser["steps"], 4),
-                                 "mpixels_s": round(pixels_all / 1e6 / (ser["seconds"] / ser["steps"]), 2),
-                                 "enc_kernel_ms": round(ser["enc_ms"], 4), "dec_kernel_ms": round(ser["dec_ms"], 4),
-                                 "kernels": "one wave per stream"},
-                "throughput_mode": None if ser_l is None else {
-                    "ms_per_step": round(1e3 * ser_l["seconds"] / ser_l["steps"], 4),
-                    "mpixels_s": round(pixels_all / 1e6 / (ser_l["seconds"] / ser_l["steps"]), 2),
-                    "enc_kernel_ms": round(ser_l["enc_ms"], 4), "dec_kernel_ms": round(ser_l["dec_ms"], 4),
-                    "kernels": "one lane per stream"},
-            },
-            "serial": {"ms_per_step": round(1e3 * ser["seconds"] / ser["steps"], 4),
-                       "mpixels_s": round(pixels_all / 1e6 / (ser["seconds"] / ser["steps"]), 2),
-                       "steps": ser["steps"], "library_mode": "TFC_MODE_LATENCY"},
-            "roofline": {
-                "bound": "hbm", "kernel": dom_symbol, "achieved": round(achieved, 2),
-                "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 5),
-                "traffic": pmc_traffic(dom_symbol, PMC_PROFILE, CODER_SOURCES, jobs_per_launch),
-                "traffic_source": f"stored: profiles/{PMC_PROFILE} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
-                                  "this command on these kernel sources, taken by the builder — not measured in this run; "
-                                  "2*FETCH + WRITE, KiB -> bytes); null = taken on other sources",
-                "algorithmic_bytes": int(dom_bytes),
-                "steps_per_launch": jobs_per_launch,
-                "note": "serial chain per stream: bound by the latency of a step's instruction chain at one or two "
-                        "waves per SIMD (a step = 64 streams of one wave), not by HBM; per-launch duration = "
-                        "HIP-event average over the timed region; the aggregate rate of both directions is "
-                        "path_gbytes_s_in_flight; see DESIGN.md",
-                "path_gbytes_s_in_flight": round((alg_enc + alg_dec) * args.steps / 1e9 / elapsed, 2),
-            },
+            "host_enqueue_ms_per_step": round(1e3 * h["t_enqueued"] / args.steps, 4),
         }
         if per_rank:
             out["per_rank"] = per_rank
-        out["valu_issue_bound"] = valu_issue_floor(
-            1e3 * elapsed / args.steps, ("enc_chain_kernel", "dec_chain_kernel") if lanes else ("enc_fast_kernel", "dec_fast_kernel"),
-            jobs_per_launch)
-        if world == 1:
-            out["gdn_fwd"] = gdn_forward_bandwidth(device)
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(lookup, m["slots"], m["slot_shas"])
-            out["speedup_vs_cpu_baseline"] = round(out["value"] / out["cpu_baseline"]["value"], 2)
-            out["single_batch"]["latency_mode"]["speedup_vs_cpu_baseline"] = round(
-                out["single_batch"]["latency_mode"]["mpixels_s"] / out["cpu_baseline"]["value"], 2)
-            if out["single_batch"]["throughput_mode"]:
-                out["single_batch"]["throughput_mode"]["speedup_vs_cpu_baseline"] = round(
-                    out["single_batch"]["throughput_mode"]["mpixels_s"] / out["cpu_baseline"]["value"], 2)
-            assert out["cpu_baseline"]["bytes_identical_to_gpu"], "GPU bytes differ from the CPU reference's"
-        lat = out["single_batch"]["latency_mode"]
-        out["config"]["single_batch"] = (
-            f"BASELINE config 2 as literally written — ONE 512-stream batch at a time, host waits for every step: "
-            f"{lat['mpixels_s']} Mpixels/s ({lat['ms_per_step']} ms per batch"
-            + (f", {lat['speedup_vs_cpu_baseline']}x the CPU reference" if "speedup_vs_cpu_baseline" in lat else "")
-            + f"); the headline `value` is {inflight} such batches per launch group")
-        bytes_per_batch = int(total_bytes)
-        del m
-        if extras and args.saturation:
-            points = sorted({int(v) for v in args.saturation.split(",") if v.strip()})
-            out["saturation"] = saturation_curve(lookup, lookup_t, device, points, bytes_per_batch,
-                                                 out.get("cpu_baseline", {}).get("value"))
-            out["saturation"]["headline_point"] = inflight
-            torch.cuda.empty_cache()
-            pipeline.empty_cache()
-        if extras:
-            torch.set_num_threads(1)
-            mh = c2_run(args, lookup, lookup_t, device, 1, 0, False, args.escape_fraction, args.steps, args.inflight,
-                        serial=False, to_host=True)
-            out["strings_to_host"] = {
-                "value": round(STREAMS * PIXELS_PER_STREAM / 1e6 / (mh["elapsed"] / args.steps), 2), "unit": "Mpixels/s",
-                "ms_per_step": round(1e3 * mh["elapsed"] / args.steps, 4),
-                "host_mbytes_per_step": round(mh["host_bytes"] / 1e6 / max(1, args.steps + args.steps), 3),
-                "note": "offsets, then exactly the bytes, device -> pinned host on a second stream while the decoders run; "
-                        "the host thread waits once per group, for the encoder"}
-            del mh
-            if args.escape_fraction == 0.0:
-                out["escapes"] = {
-                    "0.01": escape_object(args, lookup, lookup_t, device, 0.01, out.get("cpu_baseline", {}).get("value")),
-                    "escape_free": escape_object(args, lookup, lookup_t, device, 0.0,
-                                                 out.get("cpu_baseline", {}).get("value"), fold=True)}
-            torch.cuda.empty_cache()
-            out["conv"] = conv_layer_table(device)
-            torch.cuda.empty_cache()
-            out["training"] = training_figures(device)
-            torch.cuda.empty_cache()
-            out["models"] = {}
-            for name, key in (("bls2017", "c1"), ("bmshj2018", "c4")):
-                torch.cuda.empty_cache()
-                g = model_group(args, name)
-                out["models"][key] = model_bench(name, args.model_dtype, device,
-                                                 steps=args.model_steps or (32 if g == 1 else 16 * g),
-                                                 warmup=2, lanes=step_lanes, cpu=not args.no_cpu_baseline,
-                                                 group=g, queue=args.model_queue)
-            if args.model_dtype == "bf16":
-                # the reference's default policy: float32 transforms (v_mfma_f32_32x32x2_f32, first-generation kernel)
-                torch.cuda.empty_cache()
-                out["models"]["c1_f32"] = model_bench("bls2017", "f32", device, steps=8, warmup=1, lanes=step_lanes,
-                                                      cpu=False, group=1, queue=args.model_queue)
-                torch.cuda.empty_cache()
-                g = model_group(args, "bmshj2018")
-                # (two of the lanes — as fast as three, measured — a float32 step keeps ~25 GB of activations per stream
-                # live and torch's per-stream pools reserve ~70 GB for them: with three, the allocator ran out and
-                # retried inside the timed passes, memory_gb.torch_alloc_retries)
-                few = type("Lanes", (), {"lanes": step_lanes.lanes[:2]})()
-                out["models"]["c4_f32"] = model_bench("bmshj2018", "f32", device, steps=2 * g, warmup=1, lanes=few,
-                                                      cpu=False, group=g, queue=1, inflight_warmup=3)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, h["last"])
+    del h
+    if args.full:
+        full_figures(args, out, lookup, lookup_t, device, world, rank, distributed, elapsed, step_lanes, extras)
+    if rank == 0:
         print(json.dumps(out))
     if distributed:
         dist.destroy_process_group()
+
+
+def full_figures(args, out, lookup, lookup_t, device, world, rank, distributed, elapsed, step_lanes, extras):
+    """--full: everything besides the headline, added to its line `out` (rank 0).  The per-kernel figures come from
+    `--repeats` profiled timed regions of the headline's command (a run of their own: the library's event pair around
+    every launch); the figures derived from the step time use the headline's region."""
+    from compression_amd import pipeline
+    m = c2_run(args, lookup, lookup_t, device, world, rank, distributed, args.escape_fraction, args.steps,
+               args.inflight, serial=True, repeats=args.repeats)
+    if rank != 0:
+        return
+    inflight, total_bytes = m["inflight"], m["total_bytes"]
+    pixels_all = world * STREAMS * PIXELS_PER_STREAM
+    symbols = STREAMS * ELEMS
+    enc_avg, dec_avg = m["serial"]["enc_ms"], m["serial"]["dec_ms"]     # a launch has the GPU to itself
+    enc_tr, dec_tr = m["enc_tr"], m["dec_tr"]                           # profiled timed regions
+    # algorithmic bytes per launch (SURVEY.md §8d): encode reads 4 B/symbol and
+    # writes the code bytes; decode reads the code bytes and writes 4 B/symbol.
+    alg_dec = 4 * symbols + total_bytes
+    alg_enc = 4 * symbols + total_bytes
+    lanes = inflight > 1
+    jobs_per_launch = min(inflight, 64) if lanes else 1      # steps coded by one launch of the kernel
+    dom, dom_ms, dom_bytes = ("dec_kernel", dec_tr, alg_dec) if dec_tr >= enc_tr else (
+        "enc_kernel", enc_tr, alg_enc)
+    dom_bytes *= jobs_per_launch
+    achieved = dom_bytes / 1e9 / (dom_ms / 1e3) if dom_ms > 0 else 0.0
+    dom_symbol = {("dec_kernel", True): "dec_lanes_kernel", ("enc_kernel", True): "enc_lanes_kernel",
+                  ("dec_kernel", False): "dec_fast_kernel", ("enc_kernel", False): "enc_fast_kernel"}[(dom, lanes)]
+    stages = m.get("stages") or {}
+    if lanes and stages:
+        # throughput-mode calls run the pipelined kernels of csrc/range_pipe.h: the dominant KERNEL is one stage
+        # (dec_parse_next runs beside dec_chain from its first released rows to its last: its span is the chain's)
+        stage = max((k for k in stages if k != "dec_parse_next"), key=stages.get)
+        dom_symbol, dom_ms = stage + "_kernel", stages[stage]
+        dom_bytes = (alg_dec if stage.startswith("dec") else alg_enc) * jobs_per_launch
+        achieved = dom_bytes / 1e9 / (dom_ms / 1e3)
+    ser, ser_l = m["serial"], m["serial_lanes"]
+    out["timed_regions_ms_per_step"] = [round(1e3 * v / args.steps, 4) for v in m["repetitions"]]
+    out["config"]["timing_per_kernel"] = (
+        f"{len(m['repetitions'])} more timed regions of exactly --steps steps, each between its own barrier + synchronize, "
+        "with the library's event pair around every launch: kernels_ms_in_flight, roofline; timed_regions_ms_per_step = "
+        "their step times")
+    out.update({
+        "kernels_ms": {"enc_kernel": round(enc_avg, 4), "dec_kernel": round(dec_avg, 4),
+                       "note": "latency-mode kernels, one launch at a time"},
+        "kernels_ms_in_flight": {"enc_kernel": round(enc_tr, 4), "dec_kernel": round(dec_tr, 4),
+                                 "stages": {k: round(v, 4) for k, v in stages.items()},
+                                 "note": "enc_kernel / dec_kernel: all launches of an encode / decode call of the group; "
+                                         "stages: its kernels (csrc/range_pipe.h) — enc_chain runs beside enc_expand and "
+                                         "dec_parse_next beside dec_chain on a second stream, dec_parse is the pass behind the chain"},
+        "single_batch": {
+            "note": "BASELINE config 2 as literally written: ONE 512-stream batch at a time, host waits for every step",
+            "latency_mode": {"ms_per_step": round(1e3 * ser["seconds"] / ser["steps"], 4),
+                             "mpixels_s": round(pixels_all / 1e6 / (ser["seconds"] / ser["steps"]), 2),
+                             "enc_kernel_ms": round(ser["enc_ms"], 4), "dec_kernel_ms": round(ser["dec_ms"], 4),
+                             "kernels": "one wave per stream"},
+            "throughput_mode": None if ser_l is None else {
+                "ms_per_step": round(1e3 * ser_l["seconds"] / ser_l["steps"], 4),
+                "mpixels_s": round(pixels_all / 1e6 / (ser_l["seconds"] / ser_l["steps"]), 2),
+                "enc_kernel_ms": round(ser_l["enc_ms"], 4), "dec_kernel_ms": round(ser_l["dec_ms"], 4),
+                "kernels": "one lane per stream"},
+        },
+        "serial": {"ms_per_step": round(1e3 * ser["seconds"] / ser["steps"], 4),
+                   "mpixels_s": round(pixels_all / 1e6 / (ser["seconds"] / ser["steps"]), 2),
+                   "steps": ser["steps"], "library_mode": "TFC_MODE_LATENCY"},
+        "roofline": {
+            "bound": "hbm", "kernel": dom_symbol, "achieved": round(achieved, 2),
+            "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 5),
+            "traffic": pmc_traffic(dom_symbol, PMC_PROFILE, CODER_SOURCES, jobs_per_launch),
+            "traffic_source": f"stored: profiles/{PMC_PROFILE} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
+                              "this command on these kernel sources, taken by the builder — not measured in this run; "
+                              "2*FETCH + WRITE, KiB -> bytes); null = taken on other sources",
+            "algorithmic_bytes": int(dom_bytes),
+            "steps_per_launch": jobs_per_launch,
+            "note": "serial chain per stream: bound by the latency of a step's instruction chain at one or two "
+                    "waves per SIMD (a step = 64 streams of one wave), not by HBM; per-launch duration = "
+                    "HIP-event average over the profiled timed regions; the aggregate rate of both directions is "
+                    "path_gbytes_s_in_flight; see DESIGN.md",
+            "path_gbytes_s_in_flight": round((alg_enc + alg_dec) * args.steps / 1e9 / elapsed, 2),
+        },
+    })
+    out["valu_issue_bound"] = valu_issue_floor(
+        1e3 * elapsed / args.steps, ("enc_chain_kernel", "dec_chain_kernel") if lanes else ("enc_fast_kernel", "dec_fast_kernel"),
+        jobs_per_launch)
+    if world == 1:
+        out["gdn_fwd"] = gdn_forward_bandwidth(device)
+    if not args.no_cpu_baseline and world == 1:
+        out["cpu_baseline"] = cpu_baseline(lookup, m["slots"], m["slot_shas"])
+        out["speedup_vs_cpu_baseline"] = round(out["value"] / out["cpu_baseline"]["value"], 2)
+        out["single_batch"]["latency_mode"]["speedup_vs_cpu_baseline"] = round(
+            out["single_batch"]["latency_mode"]["mpixels_s"] / out["cpu_baseline"]["value"], 2)
+        if out["single_batch"]["throughput_mode"]:
+            out["single_batch"]["throughput_mode"]["speedup_vs_cpu_baseline"] = round(
+                out["single_batch"]["throughput_mode"]["mpixels_s"] / out["cpu_baseline"]["value"], 2)
+        assert out["cpu_baseline"]["bytes_identical_to_gpu"], "GPU bytes differ from the CPU reference's"
+    lat = out["single_batch"]["latency_mode"]
+    out["config"]["single_batch"] = (
+        f"BASELINE config 2 as literally written — ONE 512-stream batch at a time, host waits for every step: "
+        f"{lat['mpixels_s']} Mpixels/s ({lat['ms_per_step']} ms per batch"
+        + (f", {lat['speedup_vs_cpu_baseline']}x the CPU reference" if "speedup_vs_cpu_baseline" in lat else "")
+        + f"); the headline `value` is {inflight} such batches per launch group")
+    bytes_per_batch = int(total_bytes)
+    del m
+    if extras and args.saturation:
+        points = sorted({int(v) for v in args.saturation.split(",") if v.strip()})
+        out["saturation"] = saturation_curve(lookup, lookup_t, device, points, bytes_per_batch,
+                                             out.get("cpu_baseline", {}).get("value"))
+        out["saturation"]["headline_point"] = inflight
+        torch.cuda.empty_cache()
+        pipeline.empty_cache()
+    if extras:
+        torch.set_num_threads(1)
+        mh = c2_run(args, lookup, lookup_t, device, 1, 0, False, args.escape_fraction, args.steps, args.inflight,
+                    serial=False, to_host=True)
+        out["strings_to_host"] = {
+            "value": round(STREAMS * PIXELS_PER_STREAM / 1e6 / (mh["elapsed"] / args.steps), 2), "unit": "Mpixels/s",
+            "ms_per_step": round(1e3 * mh["elapsed"] / args.steps, 4),
+            "host_mbytes_per_step": round(mh["host_bytes"] / 1e6 / max(1, args.steps + args.steps), 3),
+            "note": "offsets, then exactly the bytes, device -> pinned host on a second stream while the decoders run; "
+                    "the host thread waits once per group, for the encoder"}
+        del mh
+        if args.escape_fraction == 0.0:
+            out["escapes"] = {
+                "0.01": escape_object(args, lookup, lookup_t, device, 0.01, out.get("cpu_baseline", {}).get("value")),
+                "escape_free": escape_object(args, lookup, lookup_t, device, 0.0,
+                                             out.get("cpu_baseline", {}).get("value"), fold=True)}
+        torch.cuda.empty_cache()
+        out["conv"] = conv_layer_table(device)
+        torch.cuda.empty_cache()
+        out["training"] = training_figures(device)
+        torch.cuda.empty_cache()
+        out["models"] = {}
+        for name, key in (("bls2017", "c1"), ("bmshj2018", "c4")):
+            torch.cuda.empty_cache()
+            g = model_group(args, name)
+            out["models"][key] = model_bench(name, args.model_dtype, device,
+                                             steps=args.model_steps or (32 if g == 1 else 16 * g),
+                                             warmup=2, lanes=step_lanes, cpu=not args.no_cpu_baseline,
+                                             group=g, queue=args.model_queue)
+        if args.model_dtype == "bf16":
+            # the reference's default policy: float32 transforms (v_mfma_f32_32x32x2_f32, first-generation kernel)
+            torch.cuda.empty_cache()
+            out["models"]["c1_f32"] = model_bench("bls2017", "f32", device, steps=8, warmup=1, lanes=step_lanes,
+                                                  cpu=False, group=1, queue=args.model_queue)
+            torch.cuda.empty_cache()
+            g = model_group(args, "bmshj2018")
+            # (two of the lanes — as fast as three, measured — a float32 step keeps ~25 GB of activations per stream
+            # live and torch's per-stream pools reserve ~70 GB for them: with three, the allocator ran out and
+            # retried inside the timed passes, memory_gb.torch_alloc_retries)
+            few = type("Lanes", (), {"lanes": step_lanes.lanes[:2]})()
+            out["models"]["c4_f32"] = model_bench("bmshj2018", "f32", device, steps=2 * g, warmup=1, lanes=few,
+                                                  cpu=False, group=g, queue=1, inflight_warmup=3)
 
 
 if __name__ == "__main__":

@@ -10,7 +10,7 @@ mkdir -p $R/gpurun_out/profiles
 for ctr in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_$ctr
   rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d /tmp/pmc_$ctr -- \
-      python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" > /tmp/pmc_$ctr.log 2>&1
+      python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --full "$@" > /tmp/pmc_$ctr.log 2>&1
   tail -2 /tmp/pmc_$ctr.log | cut -c1-300
 done
 python $R/tools/pmc_summary.py /tmp/pmc_FETCH_SIZE /tmp/pmc_WRITE_SIZE $R/gpurun_out/profiles/pmc

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp; export TMPDIR=/tmp
 OUT=$R/gpurun_out/profiles; mkdir -p $OUT
 # the driver's command (python bench.py --gpus 1 --steps 20 --warmup 5): 20 coding steps per lane-kernel launch
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline"
+ARGS="--steps 20 --warmup 5 --no-cpu-baseline --full"
 export TFC_PROFILE_STEPS_PER_LAUNCH=20
 rm -rf /tmp/st; timeout -s KILL 150 rocprofv3 --kernel-trace --stats -d /tmp/st -- python $R/bench.py $ARGS > /tmp/st.log 2>&1
 tail -1 /tmp/st.log | cut -c1-300

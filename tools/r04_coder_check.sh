@@ -9,7 +9,7 @@ cd $R
 timeout 420 python -m pytest tests/test_pipe_gpu.py tests/test_range_coder_gpu.py tests/test_pipeline_gpu.py tests/test_entropy_models_gpu.py -x -q 2>&1 | tail -15 | tee -a $LOG
 line() {  # label, env assignment, bench args
   label=$1; shift; envs=$1; shift
-  env $envs timeout 200 python bench.py --no-extras --no-cpu-baseline "$@" 2>/dev/null | grep '^{' | tail -1 | python -c "
+  env $envs timeout 200 python bench.py --no-extras --no-cpu-baseline --full "$@" 2>/dev/null | grep '^{' | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('$label', 'value', d['value'], 'ms', d['ms_per_step'], 'inflight', json.dumps(d.get('kernels_ms_in_flight')))" 2>&1 | tee -a $LOG

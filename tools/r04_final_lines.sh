@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp; export TMPDIR=/tmp
 OUT=$R/gpurun_out/profiles; mkdir -p $OUT
 for i in $(seq 1 ${1:-1}); do
-  ( cd $R && timeout -s KILL 600 python bench.py > $OUT/r04_bench_line_$i.json 2> /tmp/bench_$i.err ) || tail -3 /tmp/bench_$i.err
+  ( cd $R && timeout -s KILL 600 python bench.py --full > $OUT/r04_bench_line_$i.json 2> /tmp/bench_$i.err ) || tail -3 /tmp/bench_$i.err
   python - $OUT/r04_bench_line_$i.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

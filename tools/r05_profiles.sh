@@ -7,7 +7,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp; export TMPDIR=/tmp
 OUT=$R/gpurun_out/profiles; mkdir -p $OUT
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-extras"
+ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-extras --full"
 export TFC_PROFILE_STEPS_PER_LAUNCH=20
 rm -rf /tmp/st; timeout -s KILL 150 rocprofv3 --kernel-trace --stats -d /tmp/st -- python $R/bench.py $ARGS > /tmp/st.log 2>&1
 tail -1 /tmp/st.log | cut -c1-300
@@ -32,5 +32,5 @@ for wl in bls2017 bmshj2018; do
   python $R/tools/rocprof_summary.py /tmp/st_$wl $OUT/r05_${wl}_stats.md "Round 5: python bench.py --workload $wl --steps 16 --warmup 2 --no-cpu-baseline (rocprofv3 --kernel-trace --stats)" | head -8 || true
 done
 # the driver's default line of the same tree (bench_summary prints what the notes quote)
-( cd $R && timeout -s KILL 600 python bench.py > $OUT/r05_bench_line.json 2> /tmp/bench.err ) || tail -5 /tmp/bench.err
+( cd $R && timeout -s KILL 600 python bench.py --full > $OUT/r05_bench_line.json 2> /tmp/bench.err ) || tail -5 /tmp/bench.err
 python $R/tools/bench_summary.py $OUT/r05_bench_line.json 2>&1 | head -60

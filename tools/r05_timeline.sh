@@ -4,7 +4,7 @@
 set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp; export TMPDIR=/tmp
-rm -rf /tmp/tl; timeout -s KILL 200 rocprofv3 --kernel-trace --output-format csv -d /tmp/tl -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > /tmp/tl.log 2>&1
+rm -rf /tmp/tl; timeout -s KILL 200 rocprofv3 --kernel-trace --output-format csv -d /tmp/tl -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras --full > /tmp/tl.log 2>&1
 python - <<'PY'
 import csv, glob
 rows = []

@@ -48,5 +48,5 @@ for wl in bls2017 bmshj2018; do
   stats r06_${wl}_stats "Round 6: python bench.py --workload $wl --steps 16 --warmup 2 --no-cpu-baseline (rocprofv3 --kernel-trace --stats)" --workload $wl --steps 16 --warmup 2 --no-cpu-baseline
 done
 # the driver's default line of the same tree (bench_summary prints what the notes quote)
-( cd $R && timeout -s KILL 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r06_bench_line.json 2> /tmp/bench.err ) || tail -5 /tmp/bench.err
+( cd $R && timeout -s KILL 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/r06_bench_line.json 2> /tmp/bench.err ) || tail -5 /tmp/bench.err
 python $R/tools/bench_summary.py $OUT/r06_bench_line.json 2>&1 | head -60
