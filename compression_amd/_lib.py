@@ -78,6 +78,10 @@ SIGNATURES = {
                                                 _int, _vp, _vp]),
     "tfc_stochastic_round": (_int, [_vp, _int, _i64, C.c_float, _vp, _i64, _vp, _vp]),
     "tfc_free": (None, [_vp]),
+    "tfc_run_length_workspace": (_i64, [_i64, _i64]),
+    "tfc_run_length_encode_size": (_int, [_vp, _int, _i64, _i64, _int, _int, _int, _vp, _vp, C.POINTER(_i64), _vp]),
+    "tfc_run_length_encode_write": (_int, [_vp, _int, _i64, _i64, _int, _int, _int, _vp, _vp, _vp, _vp]),
+    "tfc_run_length_decode": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _vp, _vp, _vp]),
     "tfc_pmf_to_quantized_cdf": (_int, [_vp, _i64, _i64, _int, _vp, _vp]),
     "tfc_gdn_forward": (_int, [_vp, _vp, _int, _i64, _i64, _vp, _vp, _int, _int, _int, _int, _vp]),
     "tfc_gdn_params_create": (_int, [_vp, _vp, _i64, _int, _vp, C.POINTER(_vp)]),

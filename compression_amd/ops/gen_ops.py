@@ -33,6 +33,8 @@ __all__ = [
     "create_range_encoders", "create_range_decoders",
     "entropy_encode_finalize_device_many", "entropy_decode_finalize_device_many",
     "device_strings", "fetch_strings", "invalidate_table_cache",
+    "run_length_gamma_encode", "run_length_gamma_decode", "run_length_encode", "run_length_decode",
+    "run_length_encode_batched", "run_length_decode_batched",
 ]
 
 _MODES = {None: 0, "auto": 0, "latency": 1, "throughput": 2}
@@ -778,3 +780,149 @@ def set_default_mode(mode) -> None:
 
 def get_default_mode() -> str:
     return ("auto", "latency", "throughput")[_lib.lib().tfc_get_default_mode()]
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# Run-length gamma / Rice codec (cc/kernels/run_length_kernels.cc, cc/kernels/run_length_gamma_kernels.cc)
+
+_RL_IN_DTYPES = {torch.int32: 0, torch.float32: 1, torch.bfloat16: 2, torch.float16: 3}
+_RL_OUT_DTYPES = {torch.int32: 0, torch.float32: 1, torch.bfloat16: 2}
+_RL_ERRORS = {1: "Out of bits to read.", 2: "Exceeded maximum gamma bit width.",
+              3: "Decoded past end of tensor.",
+              4: "Rice code value overflows int32 (undefined in the reference; rejected)."}
+_RL_PAD = 16          # the decoder reads up to 16 bytes past the last string
+
+
+def _rl_codes(run_length_code, magnitude_code, use_run_length_for_non_zeros):
+    rl, mag = int(run_length_code), int(magnitude_code)
+    if rl > 31 or mag > 31:
+        raise ValueError("`run_length_code` and `magnitude_code` must be at most 31 (a Rice parameter above 31 "
+                         f"is undefined in the reference); got {rl} and {mag}")
+    return rl, mag, 1 if use_run_length_for_non_zeros else 0
+
+
+def run_length_encode_batched(data, run_length_code=-1, magnitude_code=-1, use_run_length_for_non_zeros=False,
+                              device_result=False):
+    """Encodes every row of `data` ([units, ...], int32 or float32 / bfloat16 / float16, which is rounded half
+    to even first) into its own string, in one launch sequence.  -> numpy object array of `units` byte strings,
+    or, with device_result, the device (blob, offsets, shape) (blob is padded for run_length_decode_batched).
+    Synchronises once, to size the blob."""
+    device = _lib.require_device()
+    codes = _rl_codes(run_length_code, magnitude_code, use_run_length_for_non_zeros)
+    x = torch.as_tensor(data)
+    if x.dim() < 1:
+        raise ValueError("run_length_encode_batched: `data` needs a leading units dimension")
+    if x.dtype not in _RL_IN_DTYPES:
+        raise TypeError(f"run_length_encode_batched: unsupported dtype {x.dtype}")
+    units = x.shape[0]
+    x = x.to(device).contiguous()
+    unit_len = x.numel() // units if units else 0
+    lib = _lib.lib()
+    ws = torch.empty(max(1, lib.tfc_run_length_workspace(units, unit_len)), dtype=torch.int64, device=device)
+    offsets = torch.empty(units + 1, dtype=torch.int64, device=device)
+    total = C.c_int64()
+    st = _lib.stream_ptr()
+    dt = _RL_IN_DTYPES[x.dtype]
+    _lib.check(lib.tfc_run_length_encode_size(x.data_ptr(), dt, units, unit_len, *codes, ws.data_ptr(),
+                                              offsets.data_ptr(), C.byref(total), st))
+    storage = torch.zeros((total.value + _RL_PAD + 3) // 4 * 4, dtype=torch.uint8, device=device)
+    _lib.check(lib.tfc_run_length_encode_write(x.data_ptr(), dt, units, unit_len, *codes, ws.data_ptr(),
+                                               offsets.data_ptr(), storage.data_ptr(), st))
+    blob = storage[:total.value]
+    if device_result:
+        return blob, offsets, (units,)
+    return strings_from_blob(blob, offsets, (units,))
+
+
+def _rl_padded(blob):
+    """A device blob with _RL_PAD readable bytes behind it (copies only when the storage has none)."""
+    room = blob.untyped_storage().nbytes() - blob.storage_offset() - blob.numel()
+    if blob.is_contiguous() and room >= _RL_PAD:
+        return blob
+    out = torch.zeros(blob.numel() + _RL_PAD, dtype=torch.uint8, device=blob.device)
+    out[:blob.numel()] = blob.reshape(-1)
+    return out
+
+
+def run_length_decode_batched(strings, unit_shape, run_length_code=-1, magnitude_code=-1,
+                              use_run_length_for_non_zeros=False, dtype=torch.int32):
+    """Decodes strings (bytes container, or the device (blob, offsets[, shape]) of run_length_encode_batched) into
+    a device tensor of shape strings.shape + unit_shape and `dtype` (int32, float32 or bfloat16).  Raises
+    ValueError with the reference's text when a string does not parse."""
+    device = _lib.require_device()
+    codes = _rl_codes(run_length_code, magnitude_code, use_run_length_for_non_zeros)
+    if dtype not in _RL_OUT_DTYPES:
+        raise TypeError(f"run_length_decode_batched: unsupported dtype {dtype}")
+    unit_shape = _shape_list(unit_shape)
+    if isinstance(strings, tuple) and len(strings) in (2, 3) and isinstance(strings[0], torch.Tensor):
+        blob, offsets = strings[0], strings[1]
+        shape = tuple(strings[2]) if len(strings) == 3 else (offsets.numel() - 1,)
+        blob = _rl_padded(blob.to(device))
+        offsets = offsets.to(device=device, dtype=torch.int64).contiguous()
+        host_off = offsets.cpu().numpy()
+    else:
+        b, host_off, shape = blob_from_strings(strings)
+        buf = np.zeros(b.size + _RL_PAD, np.uint8)
+        buf[:b.size] = b
+        blob = torch.from_numpy(buf).to(device)
+        offsets = torch.from_numpy(host_off).to(device)
+    host_off = np.ascontiguousarray(host_off, np.int64)
+    units = int(np.prod(shape, dtype=np.int64))
+    unit_len = int(np.prod(unit_shape, dtype=np.int64))
+    out = torch.empty([units, unit_len], dtype=dtype, device=device)
+    status = torch.empty(max(units, 1), dtype=torch.int32, device=device)
+    _lib.check(_lib.lib().tfc_run_length_decode(
+        blob.data_ptr(), offsets.data_ptr(), host_off.ctypes.data, units, unit_len, *codes,
+        _RL_OUT_DTYPES[dtype], out.data_ptr(), status.data_ptr(), _lib.stream_ptr()))
+    st = status[:units].cpu().numpy()
+    bad = np.flatnonzero(st)
+    if bad.size:
+        raise ValueError(_RL_ERRORS.get(int(st[bad[0]]), "run-length decode failed"))
+    return out.reshape(list(shape) + unit_shape)
+
+
+def _rl_scalar_code(code):
+    if isinstance(code, np.ndarray):
+        if code.shape != ():
+            raise ValueError(f"Invalid `code` shape: {list(code.shape)}")
+        code = code[()]
+    if not isinstance(code, (bytes, bytearray)):
+        raise ValueError("Invalid `code` shape: expected a scalar byte string")
+    return bytes(code)
+
+
+def _rl_shape(shape):
+    if isinstance(shape, (torch.Tensor, np.ndarray)) and shape.ndim != 1:
+        raise ValueError(f"Invalid `shape` shape: {list(shape.shape)}")
+    if isinstance(shape, (int, np.integer)):
+        raise ValueError("Invalid `shape` shape: []")
+    return _shape_list(shape)
+
+
+def run_length_encode(data, run_length_code, magnitude_code, use_run_length_for_non_zeros) -> bytes:
+    """RunLengthEncode(data; run_length_code, magnitude_code, use_run_length_for_non_zeros) -> one string for the
+    whole int32 tensor (cc/ops/run_length_ops.cc)."""
+    x = torch.as_tensor(data)
+    if x.dtype != torch.int32:
+        raise TypeError("run_length_encode expects int32 data")
+    return run_length_encode_batched(x.reshape(1, -1), run_length_code, magnitude_code,
+                                     use_run_length_for_non_zeros)[0]
+
+
+def run_length_decode(code, shape, run_length_code, magnitude_code, use_run_length_for_non_zeros) -> torch.Tensor:
+    """RunLengthDecode(code, shape; ...) -> int32 tensor of `shape`."""
+    code = _rl_scalar_code(code)
+    shape = _rl_shape(shape)
+    return run_length_decode_batched([code], shape, run_length_code, magnitude_code,
+                                     use_run_length_for_non_zeros)[0]
+
+
+def run_length_gamma_encode(data) -> bytes:
+    """RunLengthGammaEncode(data) -> one string (cc/ops/run_length_gamma_ops.cc); the bytes of
+    RunLengthEncode(-1, -1, False)."""
+    return run_length_encode(data, -1, -1, False)
+
+
+def run_length_gamma_decode(code, shape) -> torch.Tensor:
+    """RunLengthGammaDecode(code, shape) -> int32 tensor of `shape`."""
+    return run_length_decode(code, shape, -1, -1, False)

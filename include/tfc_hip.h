@@ -339,6 +339,41 @@ int tfc_stochastic_round(const void* inputs, int dtype, int64_t n, float step_si
 void tfc_free(void* p);
 
 /* ------------------------------------------------------------------------ */
+/* Run-length gamma / Rice codec                                            */
+/* ------------------------------------------------------------------------ */
+
+/* RunLengthEncode / RunLengthGammaEncode — cc/kernels/run_length_kernels.cc (RunLengthEncodeOp),
+ * cc/kernels/run_length_gamma_kernels.cc (RunLengthGammaEncodeOp), bits as cc/lib/bit_coder.cc writes them
+ * (LSB-first, last byte zero-padded).  `units` coding units of `unit_len` symbols each, data DEV of dtype 0 int32,
+ * 1 float32, 2 bfloat16, 3 float16 (floats are rounded half-to-even, then cast to int32, as tf.round + tf.cast).
+ * run_length_code / magnitude_code: a Rice parameter in [0, 31], or negative for the gamma code;
+ * RunLengthGammaEncode is (-1, -1, nonzero_runs = 0).  Rice parameters above 31 are rejected (undefined in the
+ * reference).  Two calls: _size writes offsets DEV int64 [units + 1] (byte offsets of the strings, the layout of
+ * tfc_encoder_result) and *total_bytes HOST — it synchronises once, to size the blob; _write fills blob DEV, which
+ * the caller zero-fills beforehand with room for total_bytes + 8 bytes and aligns to 4 bytes.  workspace DEV int64
+ * [tfc_run_length_workspace(units, unit_len)] carries the per-tile scans from the first call to the second. */
+int64_t tfc_run_length_workspace(int64_t units, int64_t unit_len);
+int tfc_run_length_encode_size(const void* data, int dtype, int64_t units, int64_t unit_len, int run_length_code,
+                               int magnitude_code, int nonzero_runs, int64_t* workspace, int64_t* offsets,
+                               int64_t* total_bytes, void* stream);
+int tfc_run_length_encode_write(const void* data, int dtype, int64_t units, int64_t unit_len, int run_length_code,
+                                int magnitude_code, int nonzero_runs, const int64_t* workspace,
+                                const int64_t* offsets, uint8_t* blob, void* stream);
+/* RunLengthDecode / RunLengthGammaDecode — cc/kernels/run_length_kernels.cc (RunLengthDecodeOp),
+ * cc/kernels/run_length_gamma_kernels.cc (RunLengthGammaDecodeOp), cc/lib/bit_coder.cc (BitReader).
+ * blob DEV (readable 16 bytes past offsets[units]), offsets DEV and host_offsets HOST int64 [units + 1];
+ * out DEV [units, unit_len] of out_dtype 0 int32, 1 float32, 2 bfloat16 (zero-filled, then the non-zeros).
+ * status DEV int32 [units]: 0 OK, 1 "Out of bits to read.", 2 "Exceeded maximum gamma bit width.",
+ * 3 "Decoded past end of tensor.", 4 a Rice value that overflows int32 (undefined in the reference; rejected).
+ * Kernel family by mean string length: a lane per string, or a chunk-parallel self-synchronising decode for
+ * long strings (TFC_RL_DECODER = lane | chunk forces one; TFC_RL_LONG_BITS, default 16384, is the threshold in
+ * bits; TFC_RL_CHUNK_BITS, default 1024, the chunk size; TFC_RL_SYNC_ROUNDS, default 2, the speculative
+ * rounds).  The chunked family synchronises. */
+int tfc_run_length_decode(const uint8_t* blob, const int64_t* offsets, const int64_t* host_offsets, int64_t units,
+                          int64_t unit_len, int run_length_code, int magnitude_code, int nonzero_runs,
+                          int out_dtype, void* out, int* status, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* PmfToQuantizedCdf                                                        */
 /* ------------------------------------------------------------------------ */
 
