@@ -366,7 +366,7 @@ extern "C" int tfc_tables_create(const int32_t* lookup, int rank, int64_t rows, 
     const size_t enc_bytes = dir_bytes + cdf_bytes;
     const size_t dec_bytes = enc_bytes + 8 * words + ((2 * counts + 15) & ~size_t{15});
     // (the encoder needs directory + cdf entries only; a decoder image over the CU's LDS keeps the decoder on the
-    // wave-per-stream kernels — decoder_family checks — and the encoder may still run lane-per-stream)
+    // wave-per-stream kernels — decodes_on_lanes checks — and the encoder may still run lane-per-stream)
     if (enc_bytes > 128 * 1024) ok = false;
     if (ok) {
       std::vector<uint8_t> image(dec_bytes, 0);
@@ -2092,8 +2092,18 @@ __global__ void __launch_bounds__(256) lanes_dequantize_kernel(Dst dst, const in
   }
 }
 
-template <typename Src> struct is_plain_symbols : std::false_type {};
+// Jobs on plain int32 symbols; the others quantise on load (SymQuant) or dequantise on store (OutDequant).
+template <typename Job> struct is_plain_symbols : std::false_type {};
 template <> struct is_plain_symbols<tfc::SymInt32> : std::true_type {};
+template <> struct is_plain_symbols<tfc::OutInt32> : std::true_type {};
+
+// Jobs per call of the lane path: a channel-mode batch that quantises or dequantises goes kMaxFinalizeJobs at a time
+// (without the pipelined kernels it converts through an int32 temporary of the whole call); any other batch is one
+// call, which the lane path splits into launches itself.
+template <typename Job>
+int lane_call_jobs(int n, bool indexed) {
+  return is_plain_symbols<Job>::value || indexed ? n : std::min(n, kMaxFinalizeJobs);
+}
 
 // channel mode, bottleneck values: quantise pass, then the int32 blocks
 template <typename Src>
@@ -2115,29 +2125,35 @@ int encode_lanes_prequantized(tfc_encoder* const* es, int n, const Src* srcs, in
   // `tmp` goes back to the pool in stream order, behind the coding launch
 }
 
-int encode_precheck(tfc_encoder* e, int64_t elems) {
-  if (e->finalized) return fail("encoder handle was already finalized");
-  if (e->poisoned) return fail("encoder handle met a range error in an earlier call");
-  if (elems < 0) return fail("negative element count");
+// n lane-family handles (same tables, same stream count), lane_call_jobs of them per call
+template <typename Src>
+int encode_lanes(tfc_encoder* const* es, int n, const Src* srcs, const int32_t* const* indexes, int64_t elems,
+                 hipStream_t st) {
+  const bool indexed = indexes && indexes[0];
+  const int per_call = lane_call_jobs<Src>(n, indexed);
+  for (int g0 = 0; g0 < n; g0 += per_call) {
+    const int gn = std::min(per_call, n - g0);
+    if constexpr (!is_plain_symbols<Src>::value) {
+      // (the pipelined kernels quantise in their expansion pass)
+      if (!indexed && !pipe_enabled()) {
+        if (encode_lanes_prequantized(es + g0, gn, srcs + g0, elems, st)) return 1;
+        continue;
+      }
+    }
+    if (encode_lanes_many(es + g0, gn, srcs + g0, indexed ? indexes + g0 : nullptr, elems, st, false)) return 1;
+  }
   return 0;
 }
 
+// One handle that encode_jobs did not batch (checked and touched there)
 template <typename Src>
 int run_encode(tfc_encoder* e, const int32_t* index, int64_t elems, const Src& src, hipStream_t st) {
-  if (encode_precheck(e, elems)) return 1;
-  e->touch(st);
   if (e->streams == 0 || elems == 0) return 0;
   const tfc_tables* t = e->tables;
   if (t->rows.empty()) return fail("index=0 not in range [0, 0)");
   if (e->family < 0) e->family = select_family(t, e->mode, e->streams, elems, e->fast);
   if (e->family == kLanes && elems >= (int64_t{1} << 29)) return fail("encode call too large for this handle");
-  if (e->family == kLanes) {
-    if constexpr (!is_plain_symbols<Src>::value) {
-      // (the pipelined kernels quantise in their expansion pass)
-      if (!index && !pipe_enabled()) return encode_lanes_prequantized(&e, 1, &src, elems, st);
-    }
-    return encode_lanes_many(&e, 1, &src, &index, elems, st, false);
-  }
+  if (e->family == kLanes) return encode_lanes(&e, 1, &src, &index, elems, st);
   e->elems_last = elems;
   e->indexed_last = index != nullptr;
 
@@ -2182,6 +2198,16 @@ int run_encode(tfc_encoder* e, const int32_t* index, int64_t elems, const Src& s
                      e->family == kFast ? 1 : 0, e->streams, ch.off.as<long long>(),
                      cstat.as<unsigned long long>() + 1);
   unsigned long long count_status[3] = {~0ull, 0ull, 0ull};
+  auto record_error = [&] {      // value / index behind the handle's first error position
+    EncErrJobs<Src> errs;
+    errs.elems = elems;
+    errs.ntab = p.tab.ntab;
+    errs.n = 1;
+    errs.job[0].status = e->status.as<unsigned long long>();
+    errs.job[0].src = src;
+    errs.job[0].index = index;
+    hipLaunchKernelGGL((enc_error_kernel<Src>), dim3(1), dim3(64), 0, st, errs);
+  };
   if (e->deferred) {
     // no read-back: the slab is sized from the geometry alone and the coding pass checks the counting
     // pass's verdict on the device (EncParams::guard); an error or an outgrown slab surfaces at
@@ -2191,28 +2217,14 @@ int run_encode(tfc_encoder* e, const int32_t* index, int64_t elems, const Src& s
     p.cap_total = count_status[1];
     hipLaunchKernelGGL(enc_defer_kernel, dim3(1), dim3(1), 0, st, cstat.as<unsigned long long>(),
                        e->status.as<unsigned long long>());
-    EncErrJobs<Src> errs;
-    errs.elems = elems;
-    errs.ntab = p.tab.ntab;
-    errs.n = 1;
-    errs.job[0].status = e->status.as<unsigned long long>();
-    errs.job[0].src = src;
-    errs.job[0].index = index;
-    hipLaunchKernelGGL((enc_error_kernel<Src>), dim3(1), dim3(64), 0, st, errs);
+    record_error();
   } else {
   TFC_HIP(hipMemcpyAsync(count_status, cstat.p, sizeof(count_status), hipMemcpyDeviceToHost, st));
   TFC_HIP(hipStreamSynchronize(st));
   if (count_status[0] != ~0ull) {
     // nothing was appended; fetch the offending element for the message
     TFC_HIP(hipMemcpyAsync(e->status.p, count_status, sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-    EncErrJobs<Src> errs;
-    errs.elems = elems;
-    errs.ntab = p.tab.ntab;
-    errs.n = 1;
-    errs.job[0].status = e->status.as<unsigned long long>();
-    errs.job[0].src = src;
-    errs.job[0].index = index;
-    hipLaunchKernelGGL((enc_error_kernel<Src>), dim3(1), dim3(64), 0, st, errs);
+    record_error();
     TFC_HIP(hipMemcpyAsync(host_status, e->status.p, sizeof(host_status), hipMemcpyDeviceToHost, st));
     const unsigned long long clear[4] = {~0ull, 0ull, 0ull, 0ull};
     TFC_HIP(hipStreamSynchronize(st));
@@ -2252,6 +2264,85 @@ int run_encode(tfc_encoder* e, const int32_t* index, int64_t elems, const Src& s
   return 0;
 }
 
+// Every encode entry: n handles (same tables, same stream count) as one lane-path batch where all of them code on the
+// lane family, else handle by handle.  `name` is the entry's, for its error texts.
+template <typename Src>
+int encode_jobs(tfc_encoder* const* es, int n, const Src* srcs, const int32_t* const* indexes, int64_t elems,
+                hipStream_t st, const char* name) {
+  bool batch = elems > 0 && elems < (int64_t{1} << 29);
+  for (int k = 0; k < n; ++k) {
+    tfc_encoder* e = es[k];
+    if (e->finalized) return fail("encoder handle was already finalized");
+    if (e->poisoned) return fail("encoder handle met a range error in an earlier call");
+    if (elems < 0) return fail("negative element count");
+    e->touch(st);
+    if (e->tables != es[0]->tables || e->streams != es[0]->streams)
+      return fail("%s: handles must share tables and stream count", name);
+    if ((indexes && indexes[k]) != (indexes && indexes[0]))
+      return fail("%s: either all jobs carry an index or none", name);
+    if (e->streams == 0 || e->tables->rows.empty()) batch = false;
+    if (batch && e->family < 0) e->family = select_family(e->tables, e->mode, e->streams * n, elems, e->fast);
+    if (e->family != kLanes) batch = false;
+  }
+  if (batch) return encode_lanes(es, n, srcs, indexes, elems, st);
+  for (int k = 0; k < n; ++k)
+    if (run_encode(es[k], indexes ? indexes[k] : nullptr, elems, srcs[k], st)) return 1;
+  return 0;
+}
+
+// Calls f(Dtype<T>{}) for the element type of a dtype code (0 float32, 1 bfloat16, 2 float16).
+template <typename T> struct Dtype { using type = T; };
+template <typename F>
+int with_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case 0: return f(Dtype<float>{});
+    case 1: return f(Dtype<__hip_bfloat16>{});
+    case 2: return f(Dtype<__half>{});
+    default: return fail("unsupported dtype code %d", dtype);
+  }
+}
+
+// The quantising encode entries: channel mode (indexes null) or index mode
+int encode_values(int n, tfc_encoder* const* es, const void* const* ys, int dtype, const float* qoffset,
+                  const int32_t* const* indexes, const int32_t* cdf_offset, int64_t elems, void* stream,
+                  const char* name) {
+  return with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    std::vector<SymQuant<T>> srcs(n);
+    for (int k = 0; k < n; ++k) srcs[k] = SymQuant<T>{static_cast<const T*>(ys[k]), qoffset, cdf_offset};
+    return encode_jobs(es, n, srcs.data(), indexes, elems, static_cast<hipStream_t>(stream), name);
+  });
+}
+
+int check_channels(const tfc_tables* t, int64_t channels) {
+  if (channels != static_cast<int64_t>(t->rows.size()))
+    return fail("channel count %lld does not match table count %lld",
+                static_cast<long long>(channels), static_cast<long long>(t->rows.size()));
+  return 0;
+}
+
+int check_indexes(int n, const int32_t* const* indexes) {
+  if (!indexes) return fail("index is null");
+  for (int k = 0; k < n; ++k)
+    if (!indexes[k]) return fail("index is null");
+  return 0;
+}
+
+// A new handle's tables, stream count and LDS plan of enc_fast_kernel: tables + row directory + one call ring per wave.
+void plan_encoder(tfc_encoder* e, const tfc_tables* tables, int64_t streams) {
+  e->tables = tables;
+  e->streams = streams;
+  const size_t fixed = sizeof(uint16_t) * ((tables->host.size() + 3) & ~size_t{3}) + sizeof(int2) * tables->rows.size();
+  const size_t ring = sizeof(unsigned int) * kRingWords;
+  if (!tables->rows.empty() && fixed + ring <= 160 * 1024) {
+    e->fast = true;
+    const size_t fit = (160 * 1024 - fixed) / ring;
+    const size_t want = static_cast<size_t>(waves_wanted(streams));
+    e->fast_waves = static_cast<int>(std::min(fit, want));
+    e->fast_lds = fixed + ring * e->fast_waves;
+  }
+}
+
 }  // namespace
 
 extern "C" int tfc_encoder_create(const tfc_tables* tables, int64_t streams, void* stream,
@@ -2261,21 +2352,7 @@ extern "C" int tfc_encoder_create(const tfc_tables* tables, int64_t streams, voi
   if (streams < 0) return fail("negative stream count");
   hipStream_t st = static_cast<hipStream_t>(stream);
   std::unique_ptr<tfc_encoder> e(new tfc_encoder);
-  e->tables = tables;
-  e->streams = streams;
-  {
-    // LDS plan of enc_fast_kernel: tables + row directory + one call ring per wave.
-    const size_t fixed = sizeof(uint16_t) * ((tables->host.size() + 3) & ~size_t{3}) +
-                         sizeof(int2) * tables->rows.size();
-    const size_t ring = sizeof(unsigned int) * kRingWords;
-    if (!tables->rows.empty() && fixed + ring <= 160 * 1024) {
-      e->fast = true;
-      const size_t fit = (160 * 1024 - fixed) / ring;
-      const size_t want = static_cast<size_t>(waves_wanted(streams));
-      e->fast_waves = static_cast<int>(std::min(fit, want));
-      e->fast_lds = fixed + ring * e->fast_waves;
-    }
-  }
+  plan_encoder(e.get(), tables, streams);
   TFC_HIP(e->ctl.alloc(64 + sizeof(uint4) * std::max<int64_t>(streams, 1), st));
   e->status.p = e->ctl.p;
   e->oflag.p = e->ctl.as<uint8_t>() + 32;
@@ -2302,17 +2379,7 @@ extern "C" int tfc_encoder_create_many(const tfc_tables* tables, int64_t streams
   std::vector<std::unique_ptr<tfc_encoder>> made;
   for (int k = 0; k < n; ++k) {
     std::unique_ptr<tfc_encoder> e(new tfc_encoder);
-    e->tables = tables;
-    e->streams = streams;
-    const size_t fixed = sizeof(uint16_t) * ((tables->host.size() + 3) & ~size_t{3}) + sizeof(int2) * tables->rows.size();
-    const size_t ring = sizeof(unsigned int) * kRingWords;
-    if (!tables->rows.empty() && fixed + ring <= 160 * 1024) {
-      e->fast = true;
-      const size_t fit = (160 * 1024 - fixed) / ring;
-      const size_t want = static_cast<size_t>(waves_wanted(streams));
-      e->fast_waves = static_cast<int>(std::min(fit, want));
-      e->fast_lds = fixed + ring * e->fast_waves;
-    }
+    plan_encoder(e.get(), tables, streams);
     e->ctl_group = group;
     uint8_t* c = group->as<uint8_t>() + k * ctl_bytes;
     e->status.p = c;
@@ -2430,152 +2497,44 @@ extern "C" int tfc_encoder_set_deferred_errors(tfc_encoder* e, int on) {
 
 extern "C" int tfc_encoder_encode(tfc_encoder* e, const int32_t* value, const int32_t* index,
                                   int64_t elems, void* stream) {
-  return run_encode(e, index, elems, SymInt32{value}, static_cast<hipStream_t>(stream));
+  const SymInt32 src{value};
+  return encode_jobs(&e, 1, &src, &index, elems, static_cast<hipStream_t>(stream), "tfc_encoder_encode");
 }
 
 extern "C" int tfc_encoder_encode_many(int n, tfc_encoder* const* es, const int32_t* const* values,
                                        const int32_t* const* indexes, int64_t elems, void* stream) {
-  hipStream_t st = static_cast<hipStream_t>(stream);
   if (n <= 0) return 0;
-  bool batch = elems > 0 && elems < (int64_t{1} << 29);
-  for (int k = 0; k < n; ++k) {
-    tfc_encoder* e = es[k];
-    if (encode_precheck(e, elems)) return 1;
-    e->touch(st);
-    if (e->tables != es[0]->tables || e->streams != es[0]->streams)
-      return fail("tfc_encoder_encode_many: handles must share tables and stream count");
-    if ((indexes && indexes[k]) != (indexes && indexes[0]))
-      return fail("tfc_encoder_encode_many: either all jobs carry an index or none");
-    if (e->streams == 0 || e->tables->rows.empty()) batch = false;
-    if (batch && e->family < 0) e->family = select_family(e->tables, e->mode, e->streams * n, elems, e->fast);
-    if (e->family != kLanes) batch = false;
-  }
-  if (!batch) {
-    for (int k = 0; k < n; ++k)
-      if (tfc_encoder_encode(es[k], values[k], indexes ? indexes[k] : nullptr, elems, stream)) return 1;
-    return 0;
-  }
   std::vector<SymInt32> srcs(n);
   for (int k = 0; k < n; ++k) srcs[k] = SymInt32{values[k]};
-  return encode_lanes_many(es, n, srcs.data(), indexes, elems, st, false);
+  return encode_jobs(es, n, srcs.data(), indexes, elems, static_cast<hipStream_t>(stream), "tfc_encoder_encode_many");
 }
-
-namespace {
-
-int dispatch_quantized(tfc_encoder* e, const void* y, int dtype, const float* qoffset,
-                       const int32_t* index, const int32_t* cdf_offset, int64_t elems,
-                       hipStream_t st) {
-  switch (dtype) {
-    case 0: return run_encode(e, index, elems, SymQuant<float>{static_cast<const float*>(y), qoffset, cdf_offset}, st);
-    case 1: return run_encode(e, index, elems, SymQuant<__hip_bfloat16>{static_cast<const __hip_bfloat16*>(y), qoffset, cdf_offset}, st);
-    case 2: return run_encode(e, index, elems, SymQuant<__half>{static_cast<const __half*>(y), qoffset, cdf_offset}, st);
-    default: return fail("unsupported dtype code %d", dtype);
-  }
-}
-
-}  // namespace
 
 extern "C" int tfc_encoder_encode_quantized(tfc_encoder* e, const void* y, int dtype,
                                             const float* qoffset, const int32_t* cdf_offset,
                                             int64_t channels, int64_t elems, void* stream) {
-  if (channels != static_cast<int64_t>(e->tables->rows.size()))
-    return fail("channel count %lld does not match table count %lld",
-                static_cast<long long>(channels), static_cast<long long>(e->tables->rows.size()));
-  return dispatch_quantized(e, y, dtype, qoffset, nullptr, cdf_offset, elems,
-                            static_cast<hipStream_t>(stream));
+  if (check_channels(e->tables, channels)) return 1;
+  return encode_values(1, &e, &y, dtype, qoffset, nullptr, cdf_offset, elems, stream, "tfc_encoder_encode_quantized");
 }
 
 extern "C" int tfc_encoder_encode_quantized_indexed(tfc_encoder* e, const void* y, int dtype,
                                                     const int32_t* index,
                                                     const int32_t* cdf_offset, int64_t elems,
                                                     void* stream) {
-  if (!index) return fail("index is null");
-  return dispatch_quantized(e, y, dtype, nullptr, index, cdf_offset, elems,
-                            static_cast<hipStream_t>(stream));
+  if (check_indexes(1, &index)) return 1;
+  return encode_values(1, &e, &y, dtype, nullptr, &index, cdf_offset, elems, stream,
+                       "tfc_encoder_encode_quantized_indexed");
 }
-
-namespace {
-template <typename T>
-int encode_quantized_many(int n, tfc_encoder* const* es, const void* const* ys, const float* qoffset,
-                          const int32_t* cdf_offset, int64_t elems, hipStream_t st) {
-  bool batch = elems > 0 && elems < (int64_t{1} << 29);
-  for (int k = 0; k < n; ++k) {
-    tfc_encoder* e = es[k];
-    if (encode_precheck(e, elems)) return 1;
-    e->touch(st);
-    if (e->tables != es[0]->tables || e->streams != es[0]->streams)
-      return fail("tfc_encoder_encode_quantized_many: handles must share tables and stream count");
-    if (e->streams == 0 || e->tables->rows.empty()) batch = false;
-    if (batch && e->family < 0) e->family = select_family(e->tables, e->mode, e->streams * n, elems, e->fast);
-    if (e->family != kLanes) batch = false;
-  }
-  std::vector<tfc::SymQuant<T>> srcs(n);
-  for (int k = 0; k < n; ++k) srcs[k] = tfc::SymQuant<T>{static_cast<const T*>(ys[k]), qoffset, cdf_offset};
-  if (!batch) {
-    for (int k = 0; k < n; ++k)
-      if (run_encode(es[k], nullptr, elems, srcs[k], st)) return 1;
-    return 0;
-  }
-  for (int g0 = 0; g0 < n; g0 += kMaxFinalizeJobs) {      // bounded temporaries: <= 64 batches of symbols at a time
-    const int gn = std::min(kMaxFinalizeJobs, n - g0);
-    for (int k = 0; k < gn; ++k) {
-      es[g0 + k]->elems_last = elems;
-      es[g0 + k]->indexed_last = false;
-    }
-    if (pipe_enabled()) {
-      if (encode_lanes_many(es + g0, gn, srcs.data() + g0, static_cast<const int32_t* const*>(nullptr), elems, st, false)) return 1;
-    } else if (encode_lanes_prequantized(es + g0, gn, srcs.data() + g0, elems, st)) {
-      return 1;
-    }
-  }
-  return 0;
-}
-}  // namespace
 
 // EntropyEncodeChannel with the quantise prologue for n independent handles (same tables, same geometry) as one
 // coding launch — tfc_encoder_encode_quantized x tfc_encoder_encode_many.
 extern "C" int tfc_encoder_encode_quantized_many(int n, tfc_encoder* const* es, const void* const* ys, int dtype,
                                                  const float* qoffset, const int32_t* cdf_offset,
                                                  int64_t channels, int64_t elems, void* stream) {
-  hipStream_t st = static_cast<hipStream_t>(stream);
   if (n <= 0) return 0;
-  if (channels != static_cast<int64_t>(es[0]->tables->rows.size()))
-    return fail("channel count %lld does not match table count %lld",
-                static_cast<long long>(channels), static_cast<long long>(es[0]->tables->rows.size()));
-  switch (dtype) {
-    case 0: return encode_quantized_many<float>(n, es, ys, qoffset, cdf_offset, elems, st);
-    case 1: return encode_quantized_many<__hip_bfloat16>(n, es, ys, qoffset, cdf_offset, elems, st);
-    case 2: return encode_quantized_many<__half>(n, es, ys, qoffset, cdf_offset, elems, st);
-    default: return fail("unsupported dtype code %d", dtype);
-  }
+  if (check_channels(es[0]->tables, channels)) return 1;
+  return encode_values(n, es, ys, dtype, qoffset, nullptr, cdf_offset, elems, stream,
+                       "tfc_encoder_encode_quantized_many");
 }
-
-namespace {
-template <typename T>
-int encode_quantized_indexed_many(int n, tfc_encoder* const* es, const void* const* ys, const int32_t* const* indexes,
-                                  const int32_t* cdf_offset, int64_t elems, hipStream_t st) {
-  bool batch = elems > 0 && elems < (int64_t{1} << 29);
-  for (int k = 0; k < n; ++k) {
-    tfc_encoder* e = es[k];
-    if (!indexes[k]) return fail("index is null");
-    if (encode_precheck(e, elems)) return 1;
-    e->touch(st);
-    if (e->tables != es[0]->tables || e->streams != es[0]->streams)
-      return fail("tfc_encoder_encode_quantized_indexed_many: handles must share tables and stream count");
-    if (e->streams == 0 || e->tables->rows.empty()) batch = false;
-    if (batch && e->family < 0) e->family = select_family(e->tables, e->mode, e->streams * n, elems, e->fast);
-    if (e->family != kLanes) batch = false;
-  }
-  std::vector<tfc::SymQuant<T>> srcs(n);
-  for (int k = 0; k < n; ++k) srcs[k] = tfc::SymQuant<T>{static_cast<const T*>(ys[k]), nullptr, cdf_offset};
-  if (!batch) {
-    for (int k = 0; k < n; ++k)
-      if (run_encode(es[k], indexes[k], elems, srcs[k], st)) return 1;
-    return 0;
-  }
-  return encode_lanes_many(es, n, srcs.data(), indexes, elems, st, false);
-}
-}  // namespace
 
 // EntropyEncodeIndex with the quantise prologue for n independent handles (same tables, same geometry) as one
 // coding launch — tfc_encoder_encode_quantized_indexed x tfc_encoder_encode_many: the main latents of several
@@ -2583,15 +2542,10 @@ int encode_quantized_indexed_many(int n, tfc_encoder* const* es, const void* con
 extern "C" int tfc_encoder_encode_quantized_indexed_many(int n, tfc_encoder* const* es, const void* const* ys, int dtype,
                                                          const int32_t* const* indexes, const int32_t* cdf_offset,
                                                          int64_t elems, void* stream) {
-  hipStream_t st = static_cast<hipStream_t>(stream);
   if (n <= 0) return 0;
-  if (!indexes) return fail("index is null");
-  switch (dtype) {
-    case 0: return encode_quantized_indexed_many<float>(n, es, ys, indexes, cdf_offset, elems, st);
-    case 1: return encode_quantized_indexed_many<__hip_bfloat16>(n, es, ys, indexes, cdf_offset, elems, st);
-    case 2: return encode_quantized_indexed_many<__half>(n, es, ys, indexes, cdf_offset, elems, st);
-    default: return fail("unsupported dtype code %d", dtype);
-  }
+  if (check_indexes(n, indexes)) return 1;
+  return encode_values(n, es, ys, dtype, nullptr, indexes, cdf_offset, elems, stream,
+                       "tfc_encoder_encode_quantized_indexed_many");
 }
 
 namespace {
@@ -2745,7 +2699,6 @@ struct tfc_decoder {
   const tfc_tables* tables = nullptr;
   int64_t streams = 0;
   int mode = TFC_MODE_AUTO;
-  int family = -1;
   DevBuf blob, offsets, ctl;               // blob / offsets: owned copies of host input only
   std::shared_ptr<DevBuf> ctl_group;       // create_many: ctl is a slice of a shared allocation
   DevView state, status;                   // uint4 [streams]; u64 first index error (views of ctl)
@@ -2881,11 +2834,16 @@ extern "C" int tfc_decoder_set_mode(tfc_decoder* d, int mode) {
   if (mode != TFC_MODE_AUTO && mode != TFC_MODE_LATENCY && mode != TFC_MODE_THROUGHPUT)
     return fail("unknown mode %d", mode);
   d->mode = mode;      // the decoder state has one encoding: the mode may change between calls
-  d->family = -1;
   return 0;
 }
 
 namespace {
+
+// LDS bytes of dec_fast_kernel (decoder image + row directory), or 0 where the tables cannot take that kernel.
+size_t dec_fast_lds(const tfc_tables* t) {
+  const size_t b = sizeof(int32_t) * ((t->dec_words + 3) & ~3) + sizeof(int4) * t->rows.size();
+  return t->dec_fast_ok && b <= 160 * 1024 ? b : 0;
+}
 
 // One wave per stream (dec_fast_kernel where the tables qualify, else dec_kernel) for ONE handle; `job_guard` (or null): a
 // device flag without which the launch does nothing.
@@ -2907,9 +2865,8 @@ int launch_wave_decoder(tfc_decoder* d, const int32_t* index, int64_t elems, con
   p.blocks_after_escape = 64;
   const size_t lds = table_lds_bytes(t);
   const unsigned blocks = static_cast<unsigned>(ceil_div(d->streams, kWavesPerBlock));
-  const size_t fast_lds = sizeof(int32_t) * ((t->dec_words + 3) & ~3) + sizeof(int4) * t->rows.size();
-  const bool fast_ok = t->dec_fast_ok && fast_lds <= 160 * 1024;
-  if (fast_ok) {
+  const size_t fast_lds = dec_fast_lds(t);
+  if (fast_lds) {
     const int waves = static_cast<int>(waves_wanted(d->streams));
     TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_fast_kernel<Dst>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -3025,7 +2982,6 @@ int decode_lanes_many(tfc_decoder* const* ds, int n, const Dst* dsts, const int3
   if (!pipe && !lanes_fit) {
     // neither the pipelined kernels nor the lane-per-stream kernel can take the call: one wave per stream
     for (int k = 0; k < n; ++k) {
-      ds[k]->family = kFast;
       KernelTimer timer("dec_kernel", st);
       if (launch_wave_decoder(ds[k], indexed ? indexes[k] : nullptr, elems, dsts[k], st, nullptr)) return 1;
     }
@@ -3041,7 +2997,6 @@ int decode_lanes_many(tfc_decoder* const* ds, int n, const Dst* dsts, const int3
     jobs.n = gn;
     for (int k = 0; k < gn; ++k) {
       tfc_decoder* d = ds[g0 + k];
-      d->family = kLanes;
       DecLaneJob<Dst>& J = jobs.job[k];
       J.dst = dsts[g0 + k];
       J.index = indexed ? indexes[g0 + k] : nullptr;
@@ -3185,183 +3140,129 @@ int decode_lanes_dequantized(tfc_decoder* const* ds, int n, const Dst* dsts, int
   return 0;
 }
 
-// Family of a decode call; lanes only when the tables' image plus one wave's staging fits the CU — the lane-per-stream
-// kernels' own image, or (round 6) the compact image of the pipelined decoder, whose fallback is then the wave-per-stream
-// kernel (decode_lanes_many).
+// n lane-path handles (same tables, same stream count), lane_call_jobs of them per call
+template <typename Dst>
+int decode_lanes(tfc_decoder* const* ds, int n, const Dst* dsts, const int32_t* const* indexes, int64_t elems,
+                 hipStream_t st) {
+  const bool indexed = indexes && indexes[0];
+  const int per_call = lane_call_jobs<Dst>(n, indexed);
+  for (int g0 = 0; g0 < n; g0 += per_call) {
+    const int gn = std::min(per_call, n - g0);
+    if constexpr (!is_plain_symbols<Dst>::value) {
+      // (the pipelined kernels dequantise in their parse pass)
+      if (!indexed && !pipe_enabled()) {
+        if (decode_lanes_dequantized(ds + g0, gn, dsts + g0, elems, st)) return 1;
+        continue;
+      }
+    }
+    if (decode_lanes_many(ds + g0, gn, dsts + g0, indexed ? indexes + g0 : nullptr, elems, st)) return 1;
+  }
+  return 0;
+}
+
+// Whether a decode call runs on the lane path: select_family chooses the lane family, and the tables' image plus one
+// wave's staging fits the CU — the lane-per-stream kernels' own image, or (round 6) the compact image of the pipelined
+// decoder, whose fallback is then the wave-per-stream kernel (decode_lanes_many).
 template <typename Elem>
-int decoder_family(const tfc_decoder* d, int64_t streams_in_launch, int64_t elems, bool indexed, bool fast_ok) {
+bool decodes_on_lanes(const tfc_decoder* d, int64_t streams_in_launch, int64_t elems, bool indexed) {
   const tfc_tables* t = d->tables;
-  int family = select_family(t, d->mode, streams_in_launch, elems, fast_ok);
+  // (which wave-per-stream kernel runs otherwise is launch_wave_decoder's choice)
+  if (select_family(t, d->mode, streams_in_launch, elems, false) != kLanes) return false;
   using WaveLds = DecWaveLds<Elem>;
   const int need = ((t->lane_dec_bytes + 1023) & ~1023) + (indexed ? WaveLds::kBytes : WaveLds::kIndex);
   const int need_pairs = ((t->pair_dec_bytes + 1023) & ~1023) + (indexed ? PipeDecLds::kBytes : PipeDecLds::kRows) + PipeDecLds::kStage;
   const bool compact_ok = t->pairs_ok && pipe_enabled() && pipe_format() != 1 && need_pairs <= 160 * 1024;
-  if (family == kLanes && need > 160 * 1024 && !compact_ok) family = fast_ok ? kFast : kGeneric;
-  return family;
+  return need <= 160 * 1024 || compact_ok;
 }
 
+// One handle that decode_jobs did not batch (checked and touched there)
 template <typename Dst>
-int run_decode(tfc_decoder* d, const int32_t* index, int64_t elems, const Dst& dst,
-               hipStream_t st) {
-  if (elems < 0) return fail("negative element count");
-  d->touch(st);
+int run_decode(tfc_decoder* d, const int32_t* index, int64_t elems, const Dst& dst, hipStream_t st) {
   if (d->streams == 0 || elems == 0) return 0;
-  const tfc_tables* t = d->tables;
-  if (t->rows.empty()) return fail("index=0 not in range [0, 0)");
-  const size_t fast_lds = sizeof(int32_t) * ((t->dec_words + 3) & ~3) + sizeof(int4) * t->rows.size();
-  const bool fast_ok = t->dec_fast_ok && fast_lds <= 160 * 1024;
-  const int family = decoder_family<typename Dst::elem>(d, d->streams, elems, index != nullptr, fast_ok);
-  d->family = family;
-  if (family == kLanes) {
-    if constexpr (!std::is_same<Dst, OutInt32>::value) {
-      // (the pipelined kernels dequantise in their parse pass)
-      if (!index && !pipe_enabled()) return decode_lanes_dequantized(&d, 1, &dst, elems, st);
-    }
-    return decode_lanes_many(&d, 1, &dst, &index, elems, st);
-  }
+  if (d->tables->rows.empty()) return fail("index=0 not in range [0, 0)");
+  if (decodes_on_lanes<typename Dst::elem>(d, d->streams, elems, index != nullptr))
+    return decode_lanes(&d, 1, &dst, &index, elems, st);
   KernelTimer timer("dec_kernel", st);
   return launch_wave_decoder(d, index, elems, dst, st, nullptr);
 }
 
-}  // namespace
-
-extern "C" int tfc_decoder_decode_many(int n, tfc_decoder* const* ds, const int32_t* const* indexes,
-                                       int32_t* const* outs, int64_t elems, void* stream) {
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (n <= 0) return 0;
+// Every decode entry: n handles (same tables, same stream count) as one lane-path batch where all of them decode on
+// the lane path, else handle by handle.  `name` is the entry's, for its error texts.
+template <typename Dst>
+int decode_jobs(tfc_decoder* const* ds, int n, const Dst* dsts, const int32_t* const* indexes, int64_t elems,
+                hipStream_t st, const char* name) {
   if (elems < 0) return fail("negative element count");
-  bool batch = elems > 0 && elems < (int64_t{1} << 29);
   for (int k = 0; k < n; ++k) ds[k]->touch(st);
+  const bool indexed = indexes && indexes[0];
+  bool batch = elems > 0 && elems < (int64_t{1} << 29);
   for (int k = 0; k < n; ++k) {
     const tfc_decoder* d = ds[k];
     if (d->tables != ds[0]->tables || d->streams != ds[0]->streams)
-      return fail("tfc_decoder_decode_many: handles must share tables and stream count");
-    if ((indexes && indexes[k]) != (indexes && indexes[0]))
-      return fail("tfc_decoder_decode_many: either all jobs carry an index or none");
+      return fail("%s: handles must share tables and stream count", name);
+    if ((indexes && indexes[k]) != indexed) return fail("%s: either all jobs carry an index or none", name);
     if (d->streams == 0 || d->tables->rows.empty()) batch = false;
-    if (batch && decoder_family<int32_t>(d, d->streams * n, elems, indexes && indexes[0], true) != kLanes) batch = false;
+    if (batch && !decodes_on_lanes<typename Dst::elem>(d, d->streams * n, elems, indexed)) batch = false;
   }
-  if (!batch) {
-    for (int k = 0; k < n; ++k)
-      if (tfc_decoder_decode(ds[k], indexes ? indexes[k] : nullptr, outs[k], elems, stream)) return 1;
-    return 0;
-  }
-  std::vector<OutInt32> dsts(n);
-  for (int k = 0; k < n; ++k) dsts[k] = OutInt32{outs[k]};
-  return decode_lanes_many(ds, n, dsts.data(), indexes, elems, st);
+  if (batch) return decode_lanes(ds, n, dsts, indexes, elems, st);
+  for (int k = 0; k < n; ++k)
+    if (run_decode(ds[k], indexes ? indexes[k] : nullptr, elems, dsts[k], st)) return 1;
+  return 0;
 }
+
+// The dequantising decode entries: channel mode (indexes null) or index mode
+int decode_values(int n, tfc_decoder* const* ds, const int32_t* const* indexes, void* const* ys, int dtype,
+                  const float* qoffset, const int32_t* cdf_offset, int64_t elems, void* stream, const char* name) {
+  return with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    std::vector<OutDequant<T>> dsts(n);
+    for (int k = 0; k < n; ++k) dsts[k] = OutDequant<T>{static_cast<T*>(ys[k]), qoffset, cdf_offset};
+    return decode_jobs(ds, n, dsts.data(), indexes, elems, static_cast<hipStream_t>(stream), name);
+  });
+}
+
+}  // namespace
 
 extern "C" int tfc_decoder_decode(tfc_decoder* d, const int32_t* index, int32_t* out,
                                   int64_t elems, void* stream) {
-  return run_decode(d, index, elems, OutInt32{out}, static_cast<hipStream_t>(stream));
+  const OutInt32 dst{out};
+  return decode_jobs(&d, 1, &dst, &index, elems, static_cast<hipStream_t>(stream), "tfc_decoder_decode");
+}
+
+extern "C" int tfc_decoder_decode_many(int n, tfc_decoder* const* ds, const int32_t* const* indexes,
+                                       int32_t* const* outs, int64_t elems, void* stream) {
+  if (n <= 0) return 0;
+  std::vector<OutInt32> dsts(n);
+  for (int k = 0; k < n; ++k) dsts[k] = OutInt32{outs[k]};
+  return decode_jobs(ds, n, dsts.data(), indexes, elems, static_cast<hipStream_t>(stream), "tfc_decoder_decode_many");
 }
 
 extern "C" int tfc_decoder_decode_dequantized(tfc_decoder* d, const int32_t* index, void* y,
                                               int dtype, const float* qoffset,
                                               const int32_t* cdf_offset, int64_t channels,
                                               int64_t elems, void* stream) {
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (!index && channels != static_cast<int64_t>(d->tables->rows.size()))
-    return fail("channel count %lld does not match table count %lld",
-                static_cast<long long>(channels), static_cast<long long>(d->tables->rows.size()));
+  if (!index && check_channels(d->tables, channels)) return 1;
   if (index && qoffset) return fail("qoffset is not supported in index mode");
-  switch (dtype) {
-    case 0: return run_decode(d, index, elems, OutDequant<float>{static_cast<float*>(y), qoffset, cdf_offset}, st);
-    case 1: return run_decode(d, index, elems, OutDequant<__hip_bfloat16>{static_cast<__hip_bfloat16*>(y), qoffset, cdf_offset}, st);
-    case 2: return run_decode(d, index, elems, OutDequant<__half>{static_cast<__half*>(y), qoffset, cdf_offset}, st);
-    default: return fail("unsupported dtype code %d", dtype);
-  }
+  return decode_values(1, &d, &index, &y, dtype, qoffset, cdf_offset, elems, stream, "tfc_decoder_decode_dequantized");
 }
-
-namespace {
-template <typename T>
-int decode_dequantized_many(int n, tfc_decoder* const* ds, void* const* ys, const float* qoffset,
-                            const int32_t* cdf_offset, int64_t elems, hipStream_t st) {
-  bool batch = elems > 0 && elems < (int64_t{1} << 29);
-  for (int k = 0; k < n; ++k) ds[k]->touch(st);
-  for (int k = 0; k < n; ++k) {
-    const tfc_decoder* d = ds[k];
-    if (d->tables != ds[0]->tables || d->streams != ds[0]->streams)
-      return fail("tfc_decoder_decode_dequantized_many: handles must share tables and stream count");
-    if (d->streams == 0 || d->tables->rows.empty()) batch = false;
-    if (batch && decoder_family<int32_t>(d, d->streams * n, elems, false, true) != kLanes) batch = false;
-  }
-  std::vector<OutDequant<T>> dsts(n);
-  for (int k = 0; k < n; ++k) dsts[k] = OutDequant<T>{static_cast<T*>(ys[k]), qoffset, cdf_offset};
-  if (!batch) {
-    for (int k = 0; k < n; ++k)
-      if (run_decode(ds[k], nullptr, elems, dsts[k], st)) return 1;
-    return 0;
-  }
-  for (int g0 = 0; g0 < n; g0 += kMaxFinalizeJobs) {
-    const int gn = std::min(kMaxFinalizeJobs, n - g0);
-    if (pipe_enabled()) {
-      if (decode_lanes_many(ds + g0, gn, dsts.data() + g0, static_cast<const int32_t* const*>(nullptr), elems, st)) return 1;
-    } else if (decode_lanes_dequantized(ds + g0, gn, dsts.data() + g0, elems, st)) {
-      return 1;
-    }
-  }
-  return 0;
-}
-}  // namespace
 
 // EntropyDecodeChannel with the dequantise epilogue for n independent handles as one coding launch.
 extern "C" int tfc_decoder_decode_dequantized_many(int n, tfc_decoder* const* ds, void* const* ys, int dtype,
                                                    const float* qoffset, const int32_t* cdf_offset,
                                                    int64_t channels, int64_t elems, void* stream) {
-  hipStream_t st = static_cast<hipStream_t>(stream);
   if (n <= 0) return 0;
-  if (elems < 0) return fail("negative element count");
-  if (channels != static_cast<int64_t>(ds[0]->tables->rows.size()))
-    return fail("channel count %lld does not match table count %lld",
-                static_cast<long long>(channels), static_cast<long long>(ds[0]->tables->rows.size()));
-  switch (dtype) {
-    case 0: return decode_dequantized_many<float>(n, ds, ys, qoffset, cdf_offset, elems, st);
-    case 1: return decode_dequantized_many<__hip_bfloat16>(n, ds, ys, qoffset, cdf_offset, elems, st);
-    case 2: return decode_dequantized_many<__half>(n, ds, ys, qoffset, cdf_offset, elems, st);
-    default: return fail("unsupported dtype code %d", dtype);
-  }
+  if (check_channels(ds[0]->tables, channels)) return 1;
+  return decode_values(n, ds, nullptr, ys, dtype, qoffset, cdf_offset, elems, stream,
+                       "tfc_decoder_decode_dequantized_many");
 }
-
-namespace {
-template <typename T>
-int decode_dequantized_indexed_many(int n, tfc_decoder* const* ds, const int32_t* const* indexes, void* const* ys,
-                                    const int32_t* cdf_offset, int64_t elems, hipStream_t st) {
-  bool batch = elems > 0 && elems < (int64_t{1} << 29);
-  for (int k = 0; k < n; ++k) ds[k]->touch(st);
-  for (int k = 0; k < n; ++k) {
-    const tfc_decoder* d = ds[k];
-    if (!indexes[k]) return fail("index is null");
-    if (d->tables != ds[0]->tables || d->streams != ds[0]->streams)
-      return fail("tfc_decoder_decode_dequantized_indexed_many: handles must share tables and stream count");
-    if (d->streams == 0 || d->tables->rows.empty()) batch = false;
-    if (batch && decoder_family<int32_t>(d, d->streams * n, elems, true, true) != kLanes) batch = false;
-  }
-  std::vector<OutDequant<T>> dsts(n);
-  for (int k = 0; k < n; ++k) dsts[k] = OutDequant<T>{static_cast<T*>(ys[k]), nullptr, cdf_offset};
-  if (!batch) {
-    for (int k = 0; k < n; ++k)
-      if (run_decode(ds[k], indexes[k], elems, dsts[k], st)) return 1;
-    return 0;
-  }
-  return decode_lanes_many(ds, n, dsts.data(), indexes, elems, st);
-}
-}  // namespace
 
 // EntropyDecodeIndex with the dequantise epilogue for n independent handles as one coding launch.
 extern "C" int tfc_decoder_decode_dequantized_indexed_many(int n, tfc_decoder* const* ds, const int32_t* const* indexes,
                                                            void* const* ys, int dtype, const int32_t* cdf_offset,
                                                            int64_t elems, void* stream) {
-  hipStream_t st = static_cast<hipStream_t>(stream);
   if (n <= 0) return 0;
-  if (elems < 0) return fail("negative element count");
-  if (!indexes) return fail("index is null");
-  switch (dtype) {
-    case 0: return decode_dequantized_indexed_many<float>(n, ds, indexes, ys, cdf_offset, elems, st);
-    case 1: return decode_dequantized_indexed_many<__hip_bfloat16>(n, ds, indexes, ys, cdf_offset, elems, st);
-    case 2: return decode_dequantized_indexed_many<__half>(n, ds, indexes, ys, cdf_offset, elems, st);
-    default: return fail("unsupported dtype code %d", dtype);
-  }
+  if (check_indexes(n, indexes)) return 1;
+  return decode_values(n, ds, indexes, ys, dtype, nullptr, cdf_offset, elems, stream,
+                       "tfc_decoder_decode_dequantized_indexed_many");
 }
 
 extern "C" int tfc_decoder_finalize_device(tfc_decoder* d, uint8_t* ok_dev, void* stream) {

@@ -8,6 +8,9 @@ the oracle's (cc/kernels/range_coder_kernels.cc:360-471, cc/lib/range_coder.h:19
    by the wave-per-stream kernel under the job's flag;
  * several chain waves behind one copy of the image (64 batches of BASELINE config 2 as one launch)."""
 import ctypes as C
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -120,15 +123,46 @@ def test_tables_too_wide_for_the_full_image_decode_on_the_pipelined_chain(tfc, p
     assert l1 - l0 >= 1 and f1 == f0
 
 
-def test_what_the_chain_gives_up_on_goes_to_the_wave_decoder(tfc, port):
+# Decodes the strings of an .npz with TFC_PIPE_NOFALLBACK=1 (the library reads it once, hence a process of its own):
+# prints whether the decoded values equal the input.
+_DECODE_WITHOUT_FALLBACK = """
+import sys
+import numpy as np
+import torch
+import compression_amd as tfc
+z = np.load(sys.argv[1])
+tfc.set_default_mode("throughput")
+h = tfc.create_range_decoder((torch.from_numpy(z["blob"]), torch.from_numpy(z["off"]), (len(z["off"]) - 1,)),
+                             torch.from_numpy(z["lookup"]))
+h, out = tfc.entropy_decode_channel(h, [int(z["elems"])], torch.int32)
+print("EQUAL" if np.array_equal(out.cpu().numpy(), z["value"]) else "DIFFERENT")
+"""
+
+
+def test_what_the_chain_gives_up_on_goes_to_the_wave_decoder(tfc, port, tmp_path):
     """One value in five far out: tiles with more escape codes than the launch plans rows for — the chain raises the job's
-    flag; with no lane-per-stream image that fits, the wave-per-stream kernel decodes the job under that flag."""
+    flag; with no lane-per-stream image that fits, the wave-per-stream kernel decodes the job under that flag.
+    (tfc_pipe_counters' fallback_blocks counts workgroups of the lane-per-stream kernels only, so it stays put here: the
+    chain's launch shows in `launches`, and the same decode without the fallback launch, TFC_PIPE_NOFALLBACK=1, comes
+    out wrong — the wave-per-stream kernel under the flag is what decoded the job.)"""
     lookup = wide_tables(port, seed=1)
     streams, elems = 70, 700
     value = synthetic.sample_symbols(lookup, streams, elems, seed=9, escape_fraction=0.3)
     strings = port.encode(lookup, value)[0]
+    l0, _ = counters()
     out, ok = decode_oracle_strings(tfc, lookup, strings, elems)
+    l1, _ = counters()
     assert np.array_equal(out, value) and ok
+    assert l1 - l0 >= 1, "the decode call did not run on dec_chain_kernel"
+    off = np.concatenate([[0], np.cumsum([len(x) for x in strings])]).astype(np.int64)
+    np.savez(tmp_path / "case.npz", lookup=lookup, value=value, elems=elems, off=off,
+             blob=np.frombuffer(b"".join(strings), np.uint8))
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, TFC_PIPE_NOFALLBACK="1", PYTHONPATH=root)
+    r = subprocess.run([sys.executable, "-c", _DECODE_WITHOUT_FALLBACK, str(tmp_path / "case.npz")], cwd=root, env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert r.stdout.split()[-1] == "DIFFERENT", "the chain gave up on nothing: the wave-per-stream fallback did not run"
 
 
 @pytest.mark.parametrize("waves", [1, 2, 4, 8])

@@ -235,3 +235,114 @@ def test_more_groups_than_the_chip_hosts_at_once(tfc, port):
             assert [bytes(s) for s in tfc.fetch_strings(h)] == port.encode(lookup, v)[0], k
     l1, f1 = counters()
     assert l1 - l0 >= 3 and f1 - f0 == 0, (l1 - l0, f1 - f0)
+
+
+@pytest.fixture(params=[1, 2], ids=["full", "compact"])
+def pipe_format(request):
+    """The chain's image for the decode launches of a test: 1 full, 2 compact (tfc_set_pipe_format)."""
+    from compression_amd import _lib
+    prev = _lib.lib().tfc_set_pipe_format(request.param, 0)
+    assert prev >= 0
+    yield request.param
+    _lib.lib().tfc_set_pipe_format(prev, 0)
+
+
+DTYPE_CODE = {"float32": (torch.float32, 0), "bfloat16": (torch.bfloat16, 1), "float16": (torch.float16, 2)}
+
+
+@pytest.mark.parametrize("n", [1, 3, 65])
+@pytest.mark.parametrize("form", ["int32", "int32-indexed", "float32", "bfloat16", "float16", "float32-indexed",
+                                  "bfloat16-indexed"])
+def test_many_entries_match_single_entries(tfc, port, pipe_format, form, n):
+    """Every `*_many` entry of the C ABI against its single-handle entry on the same inputs: per handle the same strings,
+    the same decoded values and the same Finalize flags.  n = 65 crosses the 64-job grouping of the channel forms that
+    quantise / dequantise."""
+    from compression_amd import _lib
+    lib, st = _lib.lib(), _lib.stream_ptr()
+    ntab, streams, elems = 12, 64, 300
+    lookup = tables(port, ntab)
+    lt = torch.from_numpy(lookup)
+    rng = np.random.default_rng(n)
+    dtype, indexed = form.split("-")[0], form.endswith("-indexed")
+    ptrs = lambda xs: (C.c_void_p * n)(*xs)                      # noqa: E731
+    index = [rng.integers(0, ntab, (streams, elems)).astype(np.int32) for _ in range(n)] if indexed else [None] * n
+    syms = [synthetic.sample_symbols(lookup, streams, elems, seed=100 * n + k, escape_fraction=0.01) for k in range(n)]
+    di = [dev(i) if indexed else None for i in index]
+    ip = [i.data_ptr() if indexed else None for i in di]
+    cdf_offset = np.arange(ntab, dtype=np.int32) % 5 - 7
+    qoffset = None if indexed or dtype == "int32" else rng.uniform(-0.4, 0.4, ntab).astype(np.float32)
+    d_cdf = dev(cdf_offset)
+    d_q = None if qoffset is None else dev(qoffset, torch.float32)
+    qp = None if d_q is None else d_q.data_ptr()
+    if dtype == "int32":
+        xs = [dev(s) for s in syms]
+    else:
+        tdtype, code = DTYPE_CODE[dtype]
+        tab = [i if indexed else np.broadcast_to(np.arange(elems) % ntab, (streams, elems)) for i in index]
+        xs = [dev(s + cdf_offset[t] + (0 if qoffset is None else qoffset[t]), torch.float32).to(tdtype)
+              for s, t in zip(syms, tab)]
+
+    def encode(many):
+        hs = [tfc.create_range_encoder([streams], lt) for _ in range(n)]
+        if dtype == "int32" and many:
+            _lib.check(lib.tfc_encoder_encode_many(n, ptrs([h.ptr for h in hs]), ptrs([x.data_ptr() for x in xs]),
+                                                   ptrs(ip) if indexed else None, elems, st))
+        elif dtype == "int32":
+            for h, x, i in zip(hs, xs, ip):
+                _lib.check(lib.tfc_encoder_encode(h.ptr, x.data_ptr(), i, elems, st))
+        elif indexed and many:
+            _lib.check(lib.tfc_encoder_encode_quantized_indexed_many(
+                n, ptrs([h.ptr for h in hs]), ptrs([x.data_ptr() for x in xs]), code, ptrs(ip), d_cdf.data_ptr(), elems,
+                st))
+        elif indexed:
+            for h, x, i in zip(hs, xs, ip):
+                _lib.check(lib.tfc_encoder_encode_quantized_indexed(h.ptr, x.data_ptr(), code, i, d_cdf.data_ptr(),
+                                                                    elems, st))
+        elif many:
+            _lib.check(lib.tfc_encoder_encode_quantized_many(
+                n, ptrs([h.ptr for h in hs]), ptrs([x.data_ptr() for x in xs]), code, qp, d_cdf.data_ptr(), ntab, elems,
+                st))
+        else:
+            for h, x in zip(hs, xs):
+                _lib.check(lib.tfc_encoder_encode_quantized(h.ptr, x.data_ptr(), code, qp, d_cdf.data_ptr(), ntab,
+                                                            elems, st))
+        return [[bytes(s) for s in tfc.entropy_encode_finalize(h).reshape(-1)] for h in hs]
+
+    strings = encode(many=False)
+    assert encode(many=True) == strings
+    if dtype == "int32" and not indexed:
+        assert strings[0] == port.encode(lookup, syms[0])[0]
+
+    def decode(many):
+        ds = []
+        for s in strings:
+            arr = np.empty(len(s), dtype=object)
+            for i, x in enumerate(s):
+                arr[i] = x
+            ds.append(tfc.create_range_decoder(arr, lt))
+        outs = [torch.empty((streams, elems), dtype=xs[0].dtype, device="cuda") for _ in range(n)]
+        dp, op = ptrs([d.ptr for d in ds]), ptrs([o.data_ptr() for o in outs])
+        if dtype == "int32" and many:
+            _lib.check(lib.tfc_decoder_decode_many(n, dp, ptrs(ip) if indexed else None, op, elems, st))
+        elif dtype == "int32":
+            for d, i, o in zip(ds, ip, outs):
+                _lib.check(lib.tfc_decoder_decode(d.ptr, i, o.data_ptr(), elems, st))
+        elif indexed and many:
+            _lib.check(lib.tfc_decoder_decode_dequantized_indexed_many(n, dp, ptrs(ip), op, code, d_cdf.data_ptr(),
+                                                                       elems, st))
+        elif many:
+            _lib.check(lib.tfc_decoder_decode_dequantized_many(n, dp, op, code, qp, d_cdf.data_ptr(), ntab, elems, st))
+        else:
+            for d, i, o in zip(ds, ip, outs):
+                _lib.check(lib.tfc_decoder_decode_dequantized(d.ptr, i, o.data_ptr(), code, qp, d_cdf.data_ptr(), ntab,
+                                                              elems, st))
+        oks = [tfc.entropy_decode_finalize(d) for d in ds]
+        return outs, oks
+
+    want, want_ok = decode(many=False)
+    got, got_ok = decode(many=True)
+    for k in range(n):
+        assert torch.equal(got[k], want[k]), k
+        assert np.array_equal(np.asarray(got_ok[k]), np.asarray(want_ok[k])) and bool(np.asarray(want_ok[k]).all()), k
+    if dtype == "int32":
+        assert all(np.array_equal(w.cpu().numpy(), s) for w, s in zip(want, syms))
