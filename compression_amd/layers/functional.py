@@ -219,6 +219,135 @@ def conv2d_up(x, kernel, bias=None, stride=1, activation=None, weights_key=0):
     return _conv_dispatch(x, kernel, bias, stride, activation, True, weights_key)
 
 
+def _triple(v):
+    return (int(v),) * 3 if isinstance(v, int) else tuple(int(s) for s in v)
+
+
+def _pad_channels(t, multiple=16, dim=-1):
+    """Zero channels up to a multiple of 16 along `dim` (the rank-3 kernels take such counts only)."""
+    extra = -t.shape[dim] % multiple
+    if not extra:
+        return t
+    pad = [0, 0] * (t.dim() - 1 - (dim % t.dim())) + [0, extra]
+    return torch.nn.functional.pad(t, pad)
+
+
+def _conv3d(fn_name, x, kernel, bias, strides, activation, up):
+    _lib.require_device()
+    if x.dtype not in _DTYPE_CODE:
+        raise TypeError(f"conv kernel supports float32 and bfloat16, got {x.dtype}")
+    if x.dim() != 5:
+        raise ValueError(f"Input tensor must have rank 5, received shape {tuple(x.shape)}.")
+    kd, kh, kw, kcin, cout = kernel.shape
+    if kcin != x.shape[-1]:
+        raise ValueError(f"kernel expects {kcin} input channels, input has {x.shape[-1]}")
+    kernel = kernel.detach().to(x.device, torch.float32)
+    x, kernel = _pad_channels(x).contiguous(), _pad_channels(kernel, dim=-2).contiguous()
+    if bias is not None:
+        bias = bias.detach().to(x.device, torch.float32).contiguous()
+    n, d, h, w, cin = x.shape
+    sd, sh, sw = strides
+    if up:
+        out = (d * sd, h * sh, w * sw)
+    else:
+        out = (-(-d // sd), -(-h // sh), -(-w // sw))
+    y = torch.empty((n,) + out + (cout,), dtype=x.dtype, device=x.device)
+    act = {None: 0, "relu": 1}[activation]
+    _lib.check(getattr(_lib.lib(), fn_name)(
+        x.data_ptr(), kernel.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(),
+        _DTYPE_CODE[x.dtype], n, d, h, w, cin, cout, kd, kh, kw, sd, sh, sw, act, _lib.stream_ptr()))
+    return y
+
+
+def conv3d_wgrad(a, b, kernel_support, strides, transpose):
+    """Weight gradient kernel (include/tfc_hip.h, tfc_conv3d_wgrad): G[t][ca][cb] = sum A[n, q*s + t - k/2, ca] B[n, q, cb]
+    as a float32 [kd, kh, kw, Cin, Cout] tensor (transpose=True: A carries Cout, B carries Cin).  Channel counts that
+    are not multiples of 16 are padded with zeros and sliced off."""
+    _lib.require_device()
+    kd, kh, kw = kernel_support
+    sd, sh, sw = strides
+    ca, cb = a.shape[-1], b.shape[-1]
+    a, b = _pad_channels(a).contiguous(), _pad_channels(b.to(a.dtype)).contiguous()
+    n, da, ha, wa, cap = a.shape
+    _, db, hb, wb, cbp = b.shape
+    shape = (kd, kh, kw, cbp, cap) if transpose else (kd, kh, kw, cap, cbp)
+    dw = torch.empty(shape, dtype=torch.float32, device=a.device)
+    _lib.check(_lib.lib().tfc_conv3d_wgrad(
+        a.data_ptr(), b.data_ptr(), dw.data_ptr(), _DTYPE_CODE[a.dtype], n, da, ha, wa, cap, db, hb, wb, cbp,
+        kd, kh, kw, sd, sh, sw, int(bool(transpose)), _lib.stream_ptr()))
+    return dw[..., :cb, :ca] if transpose else dw[..., :ca, :cb]
+
+
+class _Conv3dFunction(torch.autograd.Function):
+    """Differentiable wrapper of tfc_conv3d_down / tfc_conv3d_up, as _ConvFunction for rank 2:
+      dx  = the OTHER direction's forward kernel on dy with the kernel's channel axes swapped (cropped after up),
+      dw  = tfc_conv3d_wgrad,   dbias = sum of dy over pixels."""
+
+    @staticmethod
+    def forward(ctx, x, kernel, bias, strides, activation, up):
+        y = _conv3d("tfc_conv3d_up" if up else "tfc_conv3d_down", x, kernel, bias, strides, activation, up)
+        ctx.save_for_backward(x, kernel, y if activation == "relu" else None)
+        ctx.meta = (strides, activation, up, bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, kernel, y = ctx.saved_tensors
+        strides, activation, up, has_bias = ctx.meta
+        gy = gy.to(x.dtype).contiguous()
+        if activation == "relu":
+            gy = gy * (y > 0)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            kt = kernel.transpose(3, 4)
+            if up:
+                dx = _conv3d("tfc_conv3d_down", gy, kt, None, strides, None, False)
+            else:
+                dx = _conv3d("tfc_conv3d_up", gy, kt, None, strides, None, True)
+                dx = dx[:, :x.shape[1], :x.shape[2], :x.shape[3]]
+        if ctx.needs_input_grad[1]:
+            support = tuple(kernel.shape[:3])
+            dw = conv3d_wgrad(gy, x, support, strides, True) if up else conv3d_wgrad(x, gy, support, strides, False)
+            dw = dw.to(kernel.dtype)
+        if has_bias and ctx.needs_input_grad[2]:
+            db = gy.float().sum(dim=(0, 1, 2, 3))
+        return dx, dw, db, None, None, None
+
+
+def _conv3d_dispatch(x, kernel, bias, strides, activation, up):
+    strides = _triple(strides)
+    needs = torch.is_grad_enabled() and (x.requires_grad or kernel.requires_grad
+                                         or (bias is not None and bias.requires_grad))
+    if needs:
+        return _Conv3dFunction.apply(x, kernel, bias, strides, activation, up)
+    return _conv3d("tfc_conv3d_up" if up else "tfc_conv3d_down", x, kernel, bias, strides, activation, up)
+
+
+def conv3d_down(x, kernel, bias=None, strides=1, activation=None):
+    """Analysis correlation of rank 3 (signal_conv.py:663-690): NDHWC x, DHWIO kernel, `same_zeros`, one stride per
+    axis; out = ceil(in / s).  Rank 1 is d = h = 1."""
+    return _conv3d_dispatch(x, kernel, bias, strides, activation, False)
+
+
+def conv3d_up(x, kernel, bias=None, strides=1, activation=None):
+    """Synthesis transposed convolution of rank 3 (signal_conv.py:778-847, extra_pad_end=True); out = in * s."""
+    return _conv3d_dispatch(x, kernel, bias, strides, activation, True)
+
+
+def pad3d(x, pads, reflect=False):
+    """Padding of an NDHWC tensor, ((front, back), (top, bottom), (left, right)), as two pad2d calls: depth on the
+    [n, d, 1, h*w*c] view, then H and W on the [n*d, h, w, c] view."""
+    (f, k), ph, pw = pads
+    n, d, h, w, c = x.shape
+    if f or k:
+        x = pad2d(x.reshape(n, d, 1, h * w * c), (f, k), (0, 0), reflect=reflect).reshape(n, d + f + k, h, w, c)
+        d = d + f + k
+    if any(ph) or any(pw):
+        x = pad2d(x.reshape(n * d, h, w, c), ph, pw, reflect=reflect)
+        x = x.reshape(n, d, x.shape[1], x.shape[2], c)
+    return x
+
+
 def gdn_backward(x, grad, beta, gamma, inverse=False, rectify=False, alpha=1, epsilon=1):
     """Gradients of gdn_forward w.r.t. (x, beta, gamma) on the HIP kernel (alpha in {1, 2}, epsilon in {1, .5};
     the general exponents go through `gdn_general_composite`)."""

@@ -514,6 +514,35 @@ int tfc_conv2d_wgrad(const void* a, const void* b, float* dw, int dtype, int64_t
                      int stride, int transpose, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* SignalConv1D / SignalConv3D (same_zeros, explicit padding, NDHWC)        */
+/* ------------------------------------------------------------------------ */
+
+/* _correlate_down_explicit — python/layers/signal_conv.py:663-690 — for rank 3, one stride per axis:
+ * y[i] = sum_t x[i*s + t - k/2] * w[t] on each axis (zeros outside x), out = ceil(in / s).
+ * x DEV [N,D,H,W,Cin] (dtype: 0 f32, 1 bf16), w DEV float32 [kd,kh,kw,Cin,Cout] (DHWIO, the layer's `kernel`),
+ * bias DEV f32 [Cout] or NULL, y DEV [N,ceil(D/sd),ceil(H/sh),ceil(W/sw),Cout] (dtype of x).  activation: 0 none,
+ * 1 ReLU (fused).  Cin a multiple of 16, Cout >= 1.  Rank 1 is d = h = 1, kd = kh = 1, sd = sh = 1. */
+int tfc_conv3d_down(const void* x, const void* w, const float* bias, void* y, int dtype,
+                    int64_t n, int64_t d, int64_t h, int64_t wd, int64_t cin, int64_t cout,
+                    int kd, int kh, int kw, int sd, int sh, int sw, int activation, void* stream);
+
+/* _up_convolve_transpose_explicit — python/layers/signal_conv.py:778-847 with extra_pad_end=True — for rank 3:
+ * y[q*s + phi] = sum_d x[q - d] * w[d*s + phi + k/2] on each axis, out = in * s.  Run phase by phase: each of the
+ * sd*sh*sw output phases only takes the taps it has.  Arguments as tfc_conv3d_down. */
+int tfc_conv3d_up(const void* x, const void* w, const float* bias, void* y, int dtype,
+                  int64_t n, int64_t d, int64_t h, int64_t wd, int64_t cin, int64_t cout,
+                  int kd, int kh, int kw, int sd, int sh, int sw, int activation, void* stream);
+
+/* Weight gradient of either rank-3 direction (the reference relies on TF autodiff of signal_conv.py:663-690 /
+ * 778-847), the contract of tfc_conv2d_wgrad per axis: G[t][ca][cb] = sum_{n,q} A[n, q*s + t - k/2, ca] * B[n, q, cb]
+ * with zeros outside A; q runs over B's grid [db,hb,wb].  Down: A = x, B = dy; up: A = dy, B = x, transpose = 1 writes
+ * dw[t][cb][ca].  dw DEV f32 [kd,kh,kw,Cin,Cout] is WRITTEN (not added to).  a, b DEV dtype (0 f32, 1 bf16); channel
+ * counts multiples of 16.  Deterministic: partial sums are added in a fixed order. */
+int tfc_conv3d_wgrad(const void* a, const void* b, float* dw, int dtype, int64_t n,
+                     int64_t da, int64_t ha, int64_t wa, int64_t ca, int64_t db, int64_t hb, int64_t wb,
+                     int64_t cb, int kd, int kh, int kw, int sd, int sh, int sw, int transpose, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Training-time entropy bottleneck (deep factorized prior), fused          */
 /* ------------------------------------------------------------------------ */
 
