@@ -90,6 +90,8 @@ SIGNATURES = {
     "tfc_gdn_forward_general": (_int, [_vp, _vp, _int, _i64, _i64, _vp, _vp, _int, _int, C.c_float, C.c_float, _vp]),
     "tfc_gdn_backward": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _vp, _vp, _int, _int, _int,
                                 _int, _vp, _vp, _vp]),
+    "tfc_channel_norm_forward": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, C.c_float, _int, _vp]),
+    "tfc_channel_norm_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, C.c_float, _int, _vp]),
     "tfc_conv2d_down": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _int,
                                _int, _int, _int, _vp]),
     "tfc_conv2d_up": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _int,

@@ -73,6 +73,109 @@ def gdn_forward(x: torch.Tensor, beta: torch.Tensor, gamma: torch.Tensor, invers
     return y
 
 
+def channel_norm_reference(x, gamma, beta, epsilon=1e-3, relu=False, residual=None):
+    """The formula of `channel_norm` as differentiable tensor ops in float32 (archs.py:255-273, the variance through
+    `mean.detach()` as the reference's tf.stop_gradient; a float64 input stays float64): what ChannelNorm evaluates for
+    a CPU tensor."""
+    ft = torch.float64 if x.dtype == torch.float64 else torch.float32
+    xf = x.to(ft)
+    C = xf.shape[-1]
+    mean = xf.mean(dim=-1, keepdim=True)
+    var = ((xf - mean.detach()) ** 2).sum(dim=-1, keepdim=True) / (C - 1)
+    y = (xf - mean) * torch.rsqrt(var + epsilon)
+    if gamma is not None:
+        y = y * gamma.to(ft)
+    if beta is not None:
+        y = y + beta.to(ft)
+    if relu:
+        y = torch.relu(y)
+    if residual is not None:
+        y = y + residual.to(ft)
+    return y.to(x.dtype)
+
+
+def _channel_norm_args(x, gamma, beta, epsilon):
+    _lib.require_device()
+    if x.dtype not in _DTYPE_CODE:
+        raise TypeError(f"ChannelNorm kernel supports float32 and bfloat16, got {x.dtype}")
+    if x.dim() < 2:
+        raise ValueError(f"Input tensor must have at least rank 2, received shape {tuple(x.shape)}.")
+    C = x.shape[-1]
+    if C < 2:
+        raise ValueError(f"ChannelNorm divides by channels - 1: at least 2 channels, got {C}")
+    params = []
+    for name, t in (("gamma", gamma), ("beta", beta)):
+        if t is not None:
+            t = t.detach().to(x.device, torch.float32).contiguous()
+            if t.shape != (C,):
+                raise ValueError(f"{name} shape {tuple(t.shape)} does not match C={C}")
+        params.append(t)
+    return x.contiguous(), params[0], params[1], C, float(epsilon)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def channel_norm_forward(x, gamma, beta, epsilon=1e-3, relu=False, residual=None):
+    """tfc_channel_norm_forward (include/tfc_hip.h): one launch, no gradient."""
+    x, gamma, beta, C, epsilon = _channel_norm_args(x, gamma, beta, epsilon)
+    if residual is not None:
+        if residual.shape != x.shape:
+            raise ValueError(f"residual shape {tuple(residual.shape)} does not match the input's {tuple(x.shape)}")
+        residual = residual.detach().to(x.dtype).contiguous()
+    y = torch.empty_like(x)
+    _lib.check(_lib.lib().tfc_channel_norm_forward(
+        x.data_ptr(), _ptr(gamma), _ptr(beta), _ptr(residual), y.data_ptr(), _DTYPE_CODE[x.dtype], x.numel() // C, C,
+        epsilon, int(bool(relu)), _lib.stream_ptr()))
+    return y
+
+
+def channel_norm_backward(x, grad, gamma, beta, epsilon=1e-3, relu=False):
+    """tfc_channel_norm_backward: -> (dx, dgamma, dbeta), float32 [C] parameter gradients (None for a missing one)."""
+    x, gamma, beta, C, epsilon = _channel_norm_args(x, gamma, beta, epsilon)
+    grad = grad.to(x.dtype).contiguous()
+    dx = torch.empty_like(x)
+    dgamma = None if gamma is None else torch.empty(C, dtype=torch.float32, device=x.device)
+    dbeta = None if beta is None else torch.empty(C, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().tfc_channel_norm_backward(
+        x.data_ptr(), grad.data_ptr(), _ptr(gamma), _ptr(beta), dx.data_ptr(), _ptr(dgamma), _ptr(dbeta),
+        _DTYPE_CODE[x.dtype], x.numel() // C, C, epsilon, int(bool(relu)), _lib.stream_ptr()))
+    return dx, dgamma, dbeta
+
+
+class _ChannelNormFunction(torch.autograd.Function):
+    """Differentiable wrapper of the two ChannelNorm entries (the reference differentiates archs.py:255-273 with TF
+    autodiff).  The residual's gradient is the incoming one."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, epsilon, relu):
+        ctx.save_for_backward(x, gamma, beta)
+        ctx.cfg = (epsilon, relu, residual is not None)
+        return channel_norm_forward(x, gamma, beta, epsilon, relu, residual)
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, gamma, beta = ctx.saved_tensors
+        epsilon, relu, has_residual = ctx.cfg
+        dx, dgamma, dbeta = channel_norm_backward(x, grad, gamma, beta, epsilon, relu)
+        if gamma is not None:
+            dgamma = dgamma.to(gamma.dtype)
+        if beta is not None:
+            dbeta = dbeta.to(beta.dtype)
+        return dx, dgamma, dbeta, (grad if has_residual else None), None, None
+
+
+def channel_norm(x, gamma, beta, epsilon=1e-3, relu=False, residual=None):
+    """ChannelNorm of HiFiC (archs.py:214-297) over the last axis of x [..., C] on the fused kernel: unbiased variance,
+    gamma / beta [C] or None, then ReLU if `relu`, then `+ residual` if given.  Differentiable in x, gamma, beta and
+    residual."""
+    needs = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, gamma, beta, residual))
+    if needs:
+        return _ChannelNormFunction.apply(x, gamma, beta, residual, float(epsilon), bool(relu))
+    return channel_norm_forward(x, gamma, beta, epsilon, relu, residual)
+
+
 def _conv(fn_name, x, kernel, bias, stride, activation, up, weights_key=0):
     _lib.require_device()
     if x.dtype not in _DTYPE_CODE:

@@ -452,6 +452,31 @@ int tfc_gdn_backward(const void* x, const void* g, void* dx, int dtype, int64_t 
                      int rectify, int alpha_mode, int eps_mode, float* dbeta, float* dgamma,
                      void* stream);
 
+/* ChannelNorm of HiFiC — models/hific/archs.py:214-297 (`_get_moments` :262-273, tf.nn.batch_normalization :258) —
+ * with the ReLU / residual add the model puts behind it (archs.py:88-98, 129-154, 201-211), one pass over HBM:
+ *   mean_p = sum_c x[p,c] / C;   var_p = sum_c (x[p,c] - mean_p)^2 / (C - 1)      (the UNBIASED variance)
+ *   y[p,c] = (x[p,c] - mean_p) * rsqrt(var_p + epsilon) * gamma[c] + beta[c];  relu != 0: y = max(y, 0);
+ *   residual != NULL: y += residual[p,c] (after the ReLU).
+ * x, residual, y DEV [pixels, channels] dtype (0 f32, 1 bf16), channels innermost; gamma, beta DEV f32 [channels] or
+ * NULL (scale=False / center=False: 1 / 0).  Statistics in float32; bf16 is rounded once, on the store.  channels >= 2;
+ * epsilon finite and >= 0; pixels == 0 returns 0.  Row sizes that are multiples of 16 bytes up to 4 KB bf16 /
+ * 8 KB f32, and odd multiples of 8 bytes (rows go in pairs) up to half that, take 16-byte accesses, any other a
+ * wave-per-row kernel.  y leaves non-temporal when x + y exceed 128 MiB
+ * (TFC_CNORM_NT=0|1 in the environment: never / always). */
+int tfc_channel_norm_forward(const void* x, const float* gamma, const float* beta, const void* residual, void* y,
+                             int dtype, int64_t pixels, int64_t channels, float epsilon, int relu, void* stream);
+
+/* Backward of tfc_channel_norm_forward without a residual (the reference relies on TF autodiff of archs.py:255-273;
+ * the residual branch's gradient is g itself).  With xhat = (x - mean) rstd and g' = g * [y before the ReLU > 0]:
+ *   dx = rstd * (g' gamma - sum_c(g' gamma) / C - xhat * sum_c(g' gamma xhat) / (C - 1))
+ *   dgamma[c] = sum_p g' xhat;   dbeta[c] = sum_p g'.
+ * The tf.stop_gradient(mean) of archs.py:267 removes a term proportional to sum_c (x - mean) = 0: no difference.
+ * x, g, dx DEV [pixels, channels] dtype; dgamma, dbeta DEV f32 [channels], WRITTEN (not added to), either may be NULL.
+ * The statistics are recomputed from x.  Deterministic: per-wave partial sums are added in a fixed order. */
+int tfc_channel_norm_backward(const void* x, const void* g, const float* gamma, const float* beta, void* dx,
+                              float* dgamma, float* dbeta, int dtype, int64_t pixels, int64_t channels, float epsilon,
+                              int relu, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* SignalConv2D (same_zeros, explicit padding, NHWC, non-separable)         */
 /* ------------------------------------------------------------------------ */
