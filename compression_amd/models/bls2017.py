@@ -8,6 +8,7 @@ import torch
 
 from .. import distributions, entropy_models, layers
 from ..layers import functional
+from ..ops import image_ops
 from ..pipeline import inline_lane
 
 __all__ = ["AnalysisTransform", "SynthesisTransform", "BLS2017Model"]
@@ -55,9 +56,16 @@ class BLS2017Model(torch.nn.Module):
     # layout of the .tfci container: [string, x_shape, y_shape] (bls2017.py:164-176, 280-283)
     num_strings, num_packed = 1, 3
 
-    def __init__(self, lmbda=0.01, num_filters=128, compute_dtype=torch.float32):
+    def __init__(self, lmbda=0.01, num_filters=128, compute_dtype=torch.float32, distortion="mse"):
+        """`distortion`: "mse" (the reference's scripts) or "ms-ssim": the loss is then
+        bpp + lmbda * mean over the batch of (1 - ssim_multiscale(x, x_hat, 255)) and forward()'s third value is that
+        distortion.  The `-opt-msssim` models the reference publishes results for were trained this way; its model
+        scripts themselves do not carry the switch."""
         super().__init__()
+        if distortion not in ("mse", "ms-ssim"):
+            raise ValueError(f'distortion must be "mse" or "ms-ssim", got {distortion!r}')
         self.lmbda = lmbda
+        self.distortion = distortion
         self.compute_dtype = compute_dtype
         self.analysis_transform = AnalysisTransform(num_filters)
         self.synthesis_transform = SynthesisTransform(num_filters)
@@ -65,7 +73,7 @@ class BLS2017Model(torch.nn.Module):
         self.entropy_model = None
 
     def forward(self, x, training=True):
-        """(loss, bpp, mse) — bls2017.py:109-125."""
+        """(loss, bpp, mse) — bls2017.py:109-125; with distortion="ms-ssim" the third value is 1 - MS-SSIM."""
         em = entropy_models.ContinuousBatchedEntropyModel(self.prior, coding_rank=3, compression=False,
                                                           bottleneck_dtype=self.compute_dtype)
         x = x.to(self.compute_dtype)
@@ -74,6 +82,10 @@ class BLS2017Model(torch.nn.Module):
         x_hat = self.synthesis_transform(y_hat.to(self.compute_dtype))
         num_pixels = x.shape[0] * x.shape[1] * x.shape[2]
         bpp = bits.sum() / num_pixels
+        if self.distortion == "ms-ssim":
+            msssim = image_ops.ssim_multiscale(x, x_hat, 255.0)
+            distortion = torch.mean(1.0 - msssim).to(bpp.dtype)
+            return bpp + self.lmbda * distortion, bpp, distortion
         mse = torch.mean((x.float() - x_hat.float()) ** 2).to(bpp.dtype)
         return bpp + self.lmbda * mse, bpp, mse
 

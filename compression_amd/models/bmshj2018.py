@@ -8,6 +8,7 @@ import torch
 
 from .. import distributions, entropy_models, layers
 from ..layers import functional
+from ..ops import image_ops
 from ..pipeline import inline_lane
 
 __all__ = ["AnalysisTransform", "SynthesisTransform", "HyperAnalysisTransform",
@@ -84,8 +85,15 @@ class BMSHJ2018Model(torch.nn.Module):
     num_strings, num_packed = 2, 5
 
     def __init__(self, lmbda=0.01, num_filters=192, num_scales=64, scale_min=0.11, scale_max=256.0,
-                 compute_dtype=torch.float32):
+                 compute_dtype=torch.float32, distortion="mse"):
+        """`distortion`: "mse" (the reference's scripts) or "ms-ssim": the loss is then
+        bpp + lmbda * mean over the batch of (1 - ssim_multiscale(x, x_hat, 255)) and forward()'s third value is that
+        distortion.  The `-opt-msssim` models the reference publishes results for were trained this way; its model
+        scripts themselves do not carry the switch."""
         super().__init__()
+        if distortion not in ("mse", "ms-ssim"):
+            raise ValueError(f'distortion must be "mse" or "ms-ssim", got {distortion!r}')
+        self.distortion = distortion
         self.lmbda, self.num_scales = lmbda, num_scales
         self.compute_dtype = compute_dtype
         offset = math.log(scale_min)
@@ -117,6 +125,10 @@ class BMSHJ2018Model(torch.nn.Module):
         x_hat = self.synthesis_transform(y_hat.to(self.compute_dtype))
         num_pixels = x.shape[0] * x.shape[1] * x.shape[2]
         bpp = (bits.sum() + side_bits.sum()) / num_pixels
+        if self.distortion == "ms-ssim":
+            msssim = image_ops.ssim_multiscale(x, x_hat, 255.0)
+            distortion = torch.mean(1.0 - msssim).to(bpp.dtype)
+            return bpp + self.lmbda * distortion, bpp, distortion
         mse = torch.mean((x.float() - x_hat.float()) ** 2).to(bpp.dtype)
         return bpp + self.lmbda * mse, bpp, mse
 

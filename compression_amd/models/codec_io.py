@@ -11,6 +11,7 @@ import argparse
 import numpy as np
 import torch
 
+from ..ops import image_ops
 from ..util import PackedTensors
 
 __all__ = ["read_png", "write_png", "compress_file", "decompress_file", "container_dtypes", "load_checkpoint",
@@ -58,11 +59,21 @@ def compress_file(model, input_file, output_file, verbose=False):
     with open(output_file, "wb") as f:
         f.write(data)
     if verbose:
-        x_hat = model.decompress(*tensors)[0].float().cpu()
+        decoded = model.decompress(*tensors)[0]
+        x_hat = decoded.float().cpu()
         mse = torch.mean((x.float() - x_hat) ** 2).item()
         psnr = 10.0 * np.log10(255.0 ** 2 / mse) if mse > 0 else float("inf")
         print(f"Mean squared error: {mse:0.4f}")
         print(f"PSNR (dB): {psnr:0.2f}")
+        # bls2017.py:295-303 (the reference casts both images to float32 first: the same integers)
+        side = image_ops.min_side(len(image_ops.MSSSIM_POWER_FACTORS), 11)
+        if min(x.shape[0], x.shape[1]) < side:
+            print(f"Multiscale SSIM: n/a (image side below {side})")
+        else:
+            msssim = image_ops.ssim_multiscale(x.to(device), decoded.to(device, torch.uint8), 255).item()
+            msssim_db = -10.0 * np.log10(1.0 - msssim) if msssim < 1.0 else float("inf")
+            print(f"Multiscale SSIM: {msssim:0.4f}")
+            print(f"Multiscale SSIM (dB): {msssim_db:0.2f}")
         print(f"Bits per pixel: {len(data) * 8 / (x.shape[0] * x.shape[1]):0.4f}")
     return data
 

@@ -478,6 +478,42 @@ int tfc_channel_norm_backward(const void* x, const void* g, const float* gamma, 
                               int relu, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* SSIM / multiscale SSIM, one scale per call                               */
+/* ------------------------------------------------------------------------ */
+
+/* One scale of tf.image.ssim / tf.image.ssim_multiscale.  The definition is TensorFlow's (tensorflow/python/ops/
+ * image_ops_impl.py: _ssim_per_channel, ssim_multiscale), not the reference tree's, which only calls it
+ * (models/bls2017.py:295); parity with TensorFlow itself is unpinned, the checker is a float64 evaluation of the
+ * formulas below.  x, y DEV [batch, height, width, channels], channels innermost, dtype 0 float32, 1 bfloat16,
+ * 2 float16, 3 uint8; a plane is one image's one channel.  taps HOST float32 [filter_size], 1 <= filter_size <= 31: the
+ * 1-D window g (the 2-D one is g g^T), applied VALID.  With F that filter, c1 = (k1 max_val)^2, c2 = (k2 max_val)^2:
+ *   mu1 = F(x), mu2 = F(y), S = F(x^2 + y^2), P = F(x y)
+ *   l = (2 mu1 mu2 + c1) / (mu1^2 + mu2^2 + c1);   cs = (2 P - 2 mu1 mu2 + c2) / (S - mu1^2 - mu2^2 + c2)
+ *   means[plane] = (mean(l cs), mean(cs)) over the (height - n + 1)(width - n + 1) positions     DEV f32 [planes, 2]
+ * pooled_x, pooled_y: DEV f32 [planes, ceil(height / 2), ceil(width / 2)] or both NULL: the mean of each 2x2 block of
+ * x and y, the last row / column repeated where height / width is odd (the next scale's pair; as a call's x, y it is
+ * batch = planes, channels = 1).  Moments are accumulated in float32 on x - c, y - c (c: a pixel of the tile), which
+ * leaves the variances and the covariance unchanged.  Deterministic: per-workgroup sums are added in a fixed order, no
+ * float atomics.  Arguments are checked before anything is launched.  filter_size 11 runs kernels with the tap count as
+ * a compile-time constant (TFC_SSIM_RUNTIME_TAPS=1 in the environment: the general kernels, for comparison). */
+int tfc_ssim_scale_forward(const void* x, const void* y, int dtype, int64_t batch, int64_t height, int64_t width,
+                           int64_t channels, const float* taps, int filter_size, float c1, float c2, float* means,
+                           float* pooled_x, float* pooled_y, void* stream);
+
+/* Backward of tfc_ssim_scale_forward (TensorFlow differentiates the composed ops).  grad_means DEV f32 [planes, 2];
+ * grad_pooled_x / grad_pooled_y DEV f32 [planes, ceil(height / 2), ceil(width / 2)] or NULL (no gradient arrives
+ * through that pooled image).  grad_x, grad_y DEV f32 [batch, height, width, channels], WRITTEN, either may be NULL:
+ *   grad_x = F'(a1) + 2 x F'(b) + y F'(c) + pool'(grad_pooled_x)
+ * with a1, b, c the derivatives of sum(grad_means[plane] * (l cs, cs)) / positions with respect to mu1, S and P at
+ * every position, F' the window as a FULL correlation (the adjoint of F) and pool' a quarter of the coarser gradient
+ * per pixel, the repeated row / column folded onto the last one; likewise grad_y.  The moments are recomputed from
+ * x and y: nothing else is saved by the forward call. */
+int tfc_ssim_scale_backward(const void* x, const void* y, int dtype, int64_t batch, int64_t height, int64_t width,
+                            int64_t channels, const float* taps, int filter_size, float c1, float c2,
+                            const float* grad_means, const float* grad_pooled_x, const float* grad_pooled_y,
+                            float* grad_x, float* grad_y, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* SignalConv2D (same_zeros, explicit padding, NHWC, non-separable)         */
 /* ------------------------------------------------------------------------ */
 
