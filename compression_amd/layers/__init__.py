@@ -3,8 +3,7 @@ from .functional import (channel_norm, conv2d_down, conv2d_up, conv3d_down, conv
 from .channel_norm import ChannelNorm  # noqa: F401
 from .keras_conv import KerasConv2D, KerasConv2DTranspose  # noqa: F401
 from .gdn import GDN  # noqa: F401
-from .signal_conv import SignalConv2D  # noqa: F401
-from .signal_conv_nd import SignalConv1D, SignalConv3D  # noqa: F401
+from .signal_conv import SignalConv1D, SignalConv2D, SignalConv3D  # noqa: F401
 from .initializers import IdentityInitializer  # noqa: F401
 from .parameters import GDNParameter, Parameter, RDFTParameter  # noqa: F401
 from .soft_round import SoftRound, SoftRoundConditionalMean  # noqa: F401

@@ -176,29 +176,51 @@ def channel_norm(x, gamma, beta, epsilon=1e-3, relu=False, residual=None):
     return channel_norm_forward(x, gamma, beta, epsilon, relu, residual)
 
 
-def _conv(fn_name, x, kernel, bias, stride, activation, up, weights_key=0):
+def _ntuple(v, n):
+    return (int(v),) * n if isinstance(v, int) else tuple(int(s) for s in v)
+
+
+def pad_channels(t, multiple=16, dim=-1):
+    """Zero channels up to a multiple of 16 along `dim` (what the convolution kernels take; zero channels change nothing)."""
+    extra = -t.shape[dim] % multiple
+    if not extra:
+        return t
+    pad = [0, 0] * (t.dim() - 1 - (dim % t.dim())) + [0, extra]
+    return torch.nn.functional.pad(t, pad)
+
+
+def _conv_args(x, kernel, bias, rank):
+    """The convolution launchers' checks -> (kernel, bias) as float32 on x's device."""
     _lib.require_device()
     if x.dtype not in _DTYPE_CODE:
         raise TypeError(f"conv kernel supports float32 and bfloat16, got {x.dtype}")
-    if x.dim() != 4:
-        raise ValueError(f"Input tensor must have rank 4, received shape {tuple(x.shape)}.")
-    x = x.contiguous()
-    n, h, w, cin = x.shape
-    kh, kw, kcin, cout = kernel.shape
-    if kcin != cin:
-        raise ValueError(f"kernel expects {kcin} input channels, input has {cin}")
-    kernel = kernel.detach().to(x.device, torch.float32).contiguous()
+    if x.dim() != rank + 2:
+        raise ValueError(f"Input tensor must have rank {rank + 2}, received shape {tuple(x.shape)}.")
+    if kernel.shape[-2] != x.shape[-1]:
+        raise ValueError(f"kernel expects {kernel.shape[-2]} input channels, input has {x.shape[-1]}")
+    kernel = kernel.detach().to(x.device, torch.float32)
     if bias is not None:
         bias = bias.detach().to(x.device, torch.float32).contiguous()
-    if up:
-        oh, ow = h * stride, w * stride
-    else:
-        oh, ow = -(-h // stride), -(-w // stride)
-    y = torch.empty((n, oh, ow, cout), dtype=x.dtype, device=x.device)
+    return kernel, bias
+
+
+def _conv_output(x, strides, up, cout):
+    """The output tensor: in * s per axis (up) or ceil(in / s) (down)."""
+    spatial = tuple(n * s if up else -(-n // s) for n, s in zip(x.shape[1:-1], strides))
+    return torch.empty((x.shape[0],) + spatial + (cout,), dtype=x.dtype, device=x.device)
+
+
+def _conv(x, kernel, bias, stride, activation, up, weights_key=0):
+    kernel, bias = _conv_args(x, kernel, bias, 2)
+    x, kernel = x.contiguous(), kernel.contiguous()
+    n, h, w, cin = x.shape
+    kh, kw, _, cout = kernel.shape
+    y = _conv_output(x, (stride, stride), up, cout)
     act = {None: 0, "relu": 1}[activation]
     if weights_key:
         _lib.lib().tfc_conv2d_weights_key(weights_key)      # this thread's next conv call: fragments packed once per value
-    _lib.check(getattr(_lib.lib(), fn_name)(
+    fn = _lib.lib().tfc_conv2d_up if up else _lib.lib().tfc_conv2d_down
+    _lib.check(fn(
         x.data_ptr(), kernel.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(),
         _DTYPE_CODE[x.dtype], n, h, w, cin, cout, kh, kw, int(stride), act, _lib.stream_ptr()))
     return y
@@ -209,17 +231,11 @@ def conv2d_gdn(x, kernel, bias, stride, up, prepared: GDNPrepared, inverse: bool
     kernel applied the activation itself (include/tfc_hip.h, tfc_conv2d_gdn); else y is the convolution's output and
     the caller applies the GDN kernel."""
     import ctypes
-    _lib.require_device()
-    x = x.contiguous()
+    kernel, bias = _conv_args(x, kernel, bias, 2)
+    x, kernel = x.contiguous(), kernel.contiguous()
     n, h, w, cin = x.shape
-    kh, kw, kcin, cout = kernel.shape
-    if kcin != cin:
-        raise ValueError(f"kernel expects {kcin} input channels, input has {cin}")
-    kernel = kernel.detach().to(x.device, torch.float32).contiguous()
-    if bias is not None:
-        bias = bias.detach().to(x.device, torch.float32).contiguous()
-    oh, ow = (h * stride, w * stride) if up else (-(-h // stride), -(-w // stride))
-    y = torch.empty((n, oh, ow, cout), dtype=x.dtype, device=x.device)
+    kh, kw, _, cout = kernel.shape
+    y = _conv_output(x, (stride, stride), up, cout)
     fused = ctypes.c_int(0)
     if weights_key:
         _lib.lib().tfc_conv2d_weights_key(weights_key)
@@ -266,97 +282,16 @@ def conv2d_wgrad(a, b, kernel_support, stride, transpose):
     return dw
 
 
-class _ConvFunction(torch.autograd.Function):
-    """Differentiable wrapper of the two conv entry points (the reference differentiates
-    signal_conv.py:663-690 / 778-847 with TF autodiff):
-      dx  = the OTHER direction's forward kernel on dy with the kernel's channel axes swapped,
-      dw  = tfc_conv2d_wgrad,   dbias = sum of dy over pixels."""
-
-    @staticmethod
-    def forward(ctx, x, kernel, bias, stride, activation, up):
-        y = _conv("tfc_conv2d_up" if up else "tfc_conv2d_down", x, kernel, bias, stride, activation, up)
-        ctx.save_for_backward(x, kernel, y if activation == "relu" else None)
-        ctx.meta = (stride, activation, up, bias is not None)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, kernel, y = ctx.saved_tensors
-        stride, activation, up, has_bias = ctx.meta
-        gy = gy.to(x.dtype).contiguous()
-        if activation == "relu":
-            gy = gy * (y > 0)
-        kh, kw = kernel.shape[:2]
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            kt = kernel.permute(0, 1, 3, 2)
-            if up:
-                dx = _conv("tfc_conv2d_down", gy, kt, None, stride, None, False)
-            else:
-                dx = _conv("tfc_conv2d_up", gy, kt, None, stride, None, True)[:, :x.shape[1], :x.shape[2]]
-        if ctx.needs_input_grad[1]:
-            dw = conv2d_wgrad(gy, x, (kh, kw), stride, True) if up else conv2d_wgrad(x, gy, (kh, kw), stride, False)
-            dw = dw.to(kernel.dtype)
-        if has_bias and ctx.needs_input_grad[2]:
-            db = gy.float().sum(dim=(0, 1, 2))
-        return dx, dw, db, None, None, None
-
-
-def _conv_dispatch(x, kernel, bias, stride, activation, up, weights_key=0):
-    needs = torch.is_grad_enabled() and (x.requires_grad or kernel.requires_grad
-                                         or (bias is not None and bias.requires_grad))
-    if needs:
-        return _ConvFunction.apply(x, kernel, bias, stride, activation, up)
-    return _conv("tfc_conv2d_up" if up else "tfc_conv2d_down", x, kernel, bias, stride, activation, up, weights_key)
-
-
-def conv2d_down(x, kernel, bias=None, stride=1, activation=None, weights_key=0):
-    """Analysis correlation (signal_conv.py:663-690): NHWC x, HWIO kernel, `same_zeros`.  weights_key: a number that
-    names this VALUE of `kernel` (include/tfc_hip.h, tfc_conv2d_weights_key): its packed fragments are kept between
-    calls; 0: packed per call."""
-    return _conv_dispatch(x, kernel, bias, stride, activation, False, weights_key)
-
-
-def conv2d_up(x, kernel, bias=None, stride=1, activation=None, weights_key=0):
-    """Synthesis transposed convolution (signal_conv.py:778-847, extra_pad_end=True)."""
-    return _conv_dispatch(x, kernel, bias, stride, activation, True, weights_key)
-
-
-def _triple(v):
-    return (int(v),) * 3 if isinstance(v, int) else tuple(int(s) for s in v)
-
-
-def _pad_channels(t, multiple=16, dim=-1):
-    """Zero channels up to a multiple of 16 along `dim` (the rank-3 kernels take such counts only)."""
-    extra = -t.shape[dim] % multiple
-    if not extra:
-        return t
-    pad = [0, 0] * (t.dim() - 1 - (dim % t.dim())) + [0, extra]
-    return torch.nn.functional.pad(t, pad)
-
-
-def _conv3d(fn_name, x, kernel, bias, strides, activation, up):
-    _lib.require_device()
-    if x.dtype not in _DTYPE_CODE:
-        raise TypeError(f"conv kernel supports float32 and bfloat16, got {x.dtype}")
-    if x.dim() != 5:
-        raise ValueError(f"Input tensor must have rank 5, received shape {tuple(x.shape)}.")
-    kd, kh, kw, kcin, cout = kernel.shape
-    if kcin != x.shape[-1]:
-        raise ValueError(f"kernel expects {kcin} input channels, input has {x.shape[-1]}")
-    kernel = kernel.detach().to(x.device, torch.float32)
-    x, kernel = _pad_channels(x).contiguous(), _pad_channels(kernel, dim=-2).contiguous()
-    if bias is not None:
-        bias = bias.detach().to(x.device, torch.float32).contiguous()
+def _conv3d(x, kernel, bias, strides, activation, up):
+    kernel, bias = _conv_args(x, kernel, bias, 3)
+    x, kernel = pad_channels(x).contiguous(), pad_channels(kernel, dim=-2).contiguous()
     n, d, h, w, cin = x.shape
+    kd, kh, kw, _, cout = kernel.shape
     sd, sh, sw = strides
-    if up:
-        out = (d * sd, h * sh, w * sw)
-    else:
-        out = (-(-d // sd), -(-h // sh), -(-w // sw))
-    y = torch.empty((n,) + out + (cout,), dtype=x.dtype, device=x.device)
+    y = _conv_output(x, strides, up, cout)
     act = {None: 0, "relu": 1}[activation]
-    _lib.check(getattr(_lib.lib(), fn_name)(
+    fn = _lib.lib().tfc_conv3d_up if up else _lib.lib().tfc_conv3d_down
+    _lib.check(fn(
         x.data_ptr(), kernel.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(),
         _DTYPE_CODE[x.dtype], n, d, h, w, cin, cout, kd, kh, kw, sd, sh, sw, act, _lib.stream_ptr()))
     return y
@@ -370,7 +305,7 @@ def conv3d_wgrad(a, b, kernel_support, strides, transpose):
     kd, kh, kw = kernel_support
     sd, sh, sw = strides
     ca, cb = a.shape[-1], b.shape[-1]
-    a, b = _pad_channels(a).contiguous(), _pad_channels(b.to(a.dtype)).contiguous()
+    a, b = pad_channels(a).contiguous(), pad_channels(b.to(a.dtype)).contiguous()
     n, da, ha, wa, cap = a.shape
     _, db, hb, wb, cbp = b.shape
     shape = (kd, kh, kw, cbp, cap) if transpose else (kd, kh, kw, cap, cbp)
@@ -381,60 +316,76 @@ def conv3d_wgrad(a, b, kernel_support, strides, transpose):
     return dw[..., :cb, :ca] if transpose else dw[..., :ca, :cb]
 
 
-class _Conv3dFunction(torch.autograd.Function):
-    """Differentiable wrapper of tfc_conv3d_down / tfc_conv3d_up, as _ConvFunction for rank 2:
+# per number of spatial axes: (forward launcher, weight gradient); rank 2 takes one stride, rank 3 one per axis
+_CONV_KERNELS = {2: (_conv, conv2d_wgrad), 3: (_conv3d, conv3d_wgrad)}
+
+
+class _ConvFunction(torch.autograd.Function):
+    """Differentiable wrapper of a rank's conv entry points (the reference differentiates
+    signal_conv.py:663-690 / 778-847 with TF autodiff):
       dx  = the OTHER direction's forward kernel on dy with the kernel's channel axes swapped (cropped after up),
-      dw  = tfc_conv3d_wgrad,   dbias = sum of dy over pixels."""
+      dw  = the rank's weight gradient kernel,   dbias = sum of dy over pixels."""
 
     @staticmethod
-    def forward(ctx, x, kernel, bias, strides, activation, up):
-        y = _conv3d("tfc_conv3d_up" if up else "tfc_conv3d_down", x, kernel, bias, strides, activation, up)
+    def forward(ctx, x, kernel, bias, strides, activation, up, rank):
+        y = _CONV_KERNELS[rank][0](x, kernel, bias, strides, activation, up)
         ctx.save_for_backward(x, kernel, y if activation == "relu" else None)
-        ctx.meta = (strides, activation, up, bias is not None)
+        ctx.meta = (strides, activation, up, bias is not None, rank)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, kernel, y = ctx.saved_tensors
-        strides, activation, up, has_bias = ctx.meta
+        strides, activation, up, has_bias, rank = ctx.meta
+        launch, wgrad = _CONV_KERNELS[rank]
         gy = gy.to(x.dtype).contiguous()
         if activation == "relu":
             gy = gy * (y > 0)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            kt = kernel.transpose(3, 4)
+            kt = kernel.transpose(-1, -2)
             if up:
-                dx = _conv3d("tfc_conv3d_down", gy, kt, None, strides, None, False)
+                dx = launch(gy, kt, None, strides, None, False)
             else:
-                dx = _conv3d("tfc_conv3d_up", gy, kt, None, strides, None, True)
-                dx = dx[:, :x.shape[1], :x.shape[2], :x.shape[3]]
+                dx = launch(gy, kt, None, strides, None, True)[(slice(None),) + tuple(slice(n) for n in x.shape[1:-1])]
         if ctx.needs_input_grad[1]:
-            support = tuple(kernel.shape[:3])
-            dw = conv3d_wgrad(gy, x, support, strides, True) if up else conv3d_wgrad(x, gy, support, strides, False)
+            support = tuple(kernel.shape[:rank])
+            dw = wgrad(gy, x, support, strides, True) if up else wgrad(x, gy, support, strides, False)
             dw = dw.to(kernel.dtype)
         if has_bias and ctx.needs_input_grad[2]:
-            db = gy.float().sum(dim=(0, 1, 2, 3))
-        return dx, dw, db, None, None, None
+            db = gy.float().sum(dim=tuple(range(rank + 1)))
+        return dx, dw, db, None, None, None, None
 
 
-def _conv3d_dispatch(x, kernel, bias, strides, activation, up):
-    strides = _triple(strides)
+def _conv_dispatch(rank, x, kernel, bias, strides, activation, up, **launch_args):
     needs = torch.is_grad_enabled() and (x.requires_grad or kernel.requires_grad
                                          or (bias is not None and bias.requires_grad))
     if needs:
-        return _Conv3dFunction.apply(x, kernel, bias, strides, activation, up)
-    return _conv3d("tfc_conv3d_up" if up else "tfc_conv3d_down", x, kernel, bias, strides, activation, up)
+        return _ConvFunction.apply(x, kernel, bias, strides, activation, up, rank)
+    return _CONV_KERNELS[rank][0](x, kernel, bias, strides, activation, up, **launch_args)
+
+
+def conv2d_down(x, kernel, bias=None, stride=1, activation=None, weights_key=0):
+    """Analysis correlation (signal_conv.py:663-690): NHWC x, HWIO kernel, `same_zeros`.  weights_key: a number that
+    names this VALUE of `kernel` (include/tfc_hip.h, tfc_conv2d_weights_key): its packed fragments are kept between
+    calls; 0: packed per call."""
+    return _conv_dispatch(2, x, kernel, bias, stride, activation, False, weights_key=weights_key)
+
+
+def conv2d_up(x, kernel, bias=None, stride=1, activation=None, weights_key=0):
+    """Synthesis transposed convolution (signal_conv.py:778-847, extra_pad_end=True)."""
+    return _conv_dispatch(2, x, kernel, bias, stride, activation, True, weights_key=weights_key)
 
 
 def conv3d_down(x, kernel, bias=None, strides=1, activation=None):
     """Analysis correlation of rank 3 (signal_conv.py:663-690): NDHWC x, DHWIO kernel, `same_zeros`, one stride per
     axis; out = ceil(in / s).  Rank 1 is d = h = 1."""
-    return _conv3d_dispatch(x, kernel, bias, strides, activation, False)
+    return _conv_dispatch(3, x, kernel, bias, _ntuple(strides, 3), activation, False)
 
 
 def conv3d_up(x, kernel, bias=None, strides=1, activation=None):
     """Synthesis transposed convolution of rank 3 (signal_conv.py:778-847, extra_pad_end=True); out = in * s."""
-    return _conv3d_dispatch(x, kernel, bias, strides, activation, True)
+    return _conv_dispatch(3, x, kernel, bias, _ntuple(strides, 3), activation, True)
 
 
 def pad3d(x, pads, reflect=False):

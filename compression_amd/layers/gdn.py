@@ -4,8 +4,17 @@ from __future__ import annotations
 import torch
 
 from . import functional, parameters
+from .cached import CachedValues
 
 __all__ = ["GDN"]
+
+
+def _one():
+    return torch.ones(())
+
+
+def _identity_tenth(c):
+    return 0.1 * torch.eye(c)
 
 
 class _GDNFunction(torch.autograd.Function):
@@ -24,7 +33,7 @@ class _GDNFunction(torch.autograd.Function):
         return dx, dbeta, dgamma, None, None, None, None
 
 
-class GDN(torch.nn.Module):
+class GDN(CachedValues, torch.nn.Module):
     """y_i = x_i / (beta_i + sum_j gamma[j, i] |x_j|^alpha)^epsilon  (inverse: multiply).
 
     Same constructor arguments as the reference layer (gdn.py:127-139).  `alpha_parameter` /
@@ -47,10 +56,11 @@ class GDN(torch.nn.Module):
         self.data_format = data_format
         self._alpha_fixed, self._epsilon_fixed = alpha_parameter, epsilon_parameter
         self._beta_fixed, self._gamma_fixed = beta_parameter, gamma_parameter
-        self._alpha_init = alpha_initializer or (lambda: torch.ones(()))
-        self._epsilon_init = epsilon_initializer or (lambda: torch.ones(()))
-        self._beta_init = beta_initializer or (lambda c: torch.ones(c))
-        self._gamma_init = gamma_initializer or (lambda c: 0.1 * torch.eye(c))
+        # (module-level defaults: a layer with a lambda in it does not pickle)
+        self._alpha_init = alpha_initializer or _one
+        self._epsilon_init = epsilon_initializer or _one
+        self._beta_init = beta_initializer or torch.ones
+        self._gamma_init = gamma_initializer or _identity_tenth
         self.reparam_beta = self.reparam_gamma = None
         self.reparam_alpha = self.reparam_epsilon = None
         if alpha_parameter is None:
@@ -114,37 +124,10 @@ class GDN(torch.nn.Module):
             cache["prepared"] = hit = (key, prepared, beta, gamma)
         return hit[1]
 
-    # The cache holds native handles (functional.GDNPrepared): it is not copied or pickled with the module, the
-    # copy rebuilds its own on first use (copy.deepcopy for an EMA model, torch.save of the module object).
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state.pop("_value_cache", None)
-        return state
-
-    def __deepcopy__(self, memo):
-        import copy
-        cls = self.__class__
-        new = cls.__new__(cls)
-        memo[id(self)] = new
-        for k, v in self.__dict__.items():
-            if k != "_value_cache":
-                new.__dict__[k] = copy.deepcopy(v, memo)
-        return new
+    _cache_attrs = ("_value_cache",)        # (holds native handles, functional.GDNPrepared)
 
     def invalidate_kernel_cache(self):
         self.__dict__["_value_cache"] = {}
-
-    def _load_from_state_dict(self, *args, **kwargs):
-        self.invalidate_kernel_cache()
-        return super()._load_from_state_dict(*args, **kwargs)
-
-    def _apply(self, fn, *args, **kwargs):
-        self.invalidate_kernel_cache()
-        return super()._apply(fn, *args, **kwargs)
-
-    def train(self, mode=True):
-        self.invalidate_kernel_cache()
-        return super().train(mode)
 
     @property
     def beta(self):

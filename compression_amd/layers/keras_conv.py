@@ -10,7 +10,7 @@ The kernels compute (include/tfc_hip.h, tfc_conv2d_down / tfc_conv2d_up)
   down_s(x)[i] = sum_t x[i s + t - k // 2] w[t]    and    up_s(x)[n] = f[n + k // 2],
 which is the same window for s = 1 and for odd L at k = 3, s = 2, and one sample later where `before` < k // 2 (k = 3,
 s = 2, even L: before = 0).  `a` zero rows / columns in front of the input move the window back, and the first output
-samples are dropped (the device of SignalConv2D._forward_general):
+samples are dropped (as SignalConv._forward_general does):
   down:  a = m s - (k // 2 - before), m = ceil((k // 2 - before) / s):  y[i] = down_s(x')[i + m]
   up:    a = ceil((k // 2 - before) / s), o = a s - (k // 2 - before):  y[m] = up_s(x')[m + o]
 
@@ -29,8 +29,8 @@ import math
 
 import torch
 
-from . import functional
-from .signal_conv import SignalConv2D, _version_of
+from . import cached, functional
+from .functional import _ntuple
 
 __all__ = ["KerasConv2D", "KerasConv2DTranspose", "same_before"]
 
@@ -45,17 +45,14 @@ def _padded_channels(c, multiple):
     return c if c <= 4 else -(-c // multiple) * multiple
 
 
-def _pair(v):
-    return (int(v), int(v)) if isinstance(v, int) else tuple(int(s) for s in v)
-
-
-class _KerasConvBase(torch.nn.Module):
+class _KerasConvBase(cached.CachedValues, torch.nn.Module):
     transpose = False
+    _cache_attrs = ("_padded_cache",)
 
     def __init__(self, filters, kernel_size, strides=1, in_channels=None):
         super().__init__()
         self.filters = int(filters)
-        self.kernel_size = _pair(kernel_size)
+        self.kernel_size = _ntuple(kernel_size, 2)
         if isinstance(strides, (tuple, list)):
             if len(set(strides)) != 1:
                 raise NotImplementedError("one stride for both axes")
@@ -92,17 +89,17 @@ class _KerasConvBase(torch.nn.Module):
             return k, torch.nn.functional.pad(self.bias, (0, cout_p - self.filters))
         if torch.is_grad_enabled() or not self.kernel.is_cuda:
             return make() + (0,)
-        versions = (_version_of(self.kernel), _version_of(self.bias))
+        versions = (cached.version_of(self.kernel), cached.version_of(self.bias))
         if None in versions:
             return make() + (0,)
-        ident = (self.kernel.data_ptr(), self.bias.data_ptr(), versions, str(self.kernel.device), cin_p, id(self))
+        ident = (self.kernel.data_ptr(), self.bias.data_ptr(), versions, str(self.kernel.device), cin_p)
         hit = self.__dict__.get("_padded_cache")
         if hit is None or hit[0] != ident:
             self.invalidate_kernel_cache()
             k, b = make()
             k, b = k.contiguous(), b.contiguous()
             torch.cuda.current_stream().synchronize()          # complete before another stream reads them
-            hit = (ident, k, b, next(SignalConv2D._WEIGHT_KEYS) if SignalConv2D.keyed_weights else 0)
+            hit = (ident, k, b, cached.new_weights_key() if cached.KEYED_WEIGHTS else 0)
             self.__dict__["_padded_cache"] = hit
         return hit[1], hit[2], hit[3]
 
@@ -110,40 +107,8 @@ class _KerasConvBase(torch.nn.Module):
         """Drops the padded weights and the library's packed fragments of them: after a write through `.data`, which
         advances neither address nor version counter (load_state_dict, .to(), train() / eval() do it themselves)."""
         hit = self.__dict__.pop("_padded_cache", None)
-        if hit is not None and hit[3] and hit[0][-1] == id(self):
-            SignalConv2D._drop_weights_key(hit[3])
-
-    def __del__(self):
-        try:
-            self.invalidate_kernel_cache()
-        except Exception:
-            pass
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state.pop("_padded_cache", None)
-        return state
-
-    def __deepcopy__(self, memo):
-        import copy
-        new = self.__class__.__new__(self.__class__)
-        memo[id(self)] = new
-        for k, v in self.__dict__.items():
-            if k != "_padded_cache":
-                new.__dict__[k] = copy.deepcopy(v, memo)
-        return new
-
-    def _load_from_state_dict(self, *args, **kwargs):
-        self.invalidate_kernel_cache()
-        return super()._load_from_state_dict(*args, **kwargs)
-
-    def _apply(self, fn, *args, **kwargs):
-        self.invalidate_kernel_cache()
-        return super()._apply(fn, *args, **kwargs)
-
-    def train(self, mode=True):
-        self.invalidate_kernel_cache()
-        return super().train(mode)
+        if hit is not None and hit[3]:
+            cached.drop_weights_key(hit[3])
 
     def output_size(self, h, w):
         s = self.strides

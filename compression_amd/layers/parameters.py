@@ -13,19 +13,18 @@ __all__ = ["rdft_from_kernel", "kernel_from_rdft", "gdn_reparam_init", "gdn_repa
 
 
 def rdft_from_kernel(kernel: torch.Tensor):
-    """HWIO kernel -> (real, imag) of its normalised 2-D RDFT, shape [I, O, kh, kw//2+1]
+    """[*support, I, O] kernel -> (real, imag) of its normalised RDFT over the support axes, [I, O, ..., k // 2 + 1]
     (RDFTParameter.__init__, parameters.py:85-127)."""
-    kh, kw = kernel.shape[:2]
-    spec = torch.fft.rfft2(kernel.permute(2, 3, 0, 1)) / math.sqrt(kh * kw)
+    support = kernel.shape[:-2]
+    spec = torch.fft.rfftn(kernel.movedim((-2, -1), (0, 1)).float(), dim=tuple(range(2, 2 + len(support))))
+    spec = spec / math.sqrt(math.prod(support))
     return spec.real.contiguous(), spec.imag.contiguous()
 
 
-def kernel_from_rdft(real: torch.Tensor, imag: torch.Tensor, support):
-    """Inverse of the above (RDFTParameter.__call__, parameters.py:140-170)."""
-    kh, kw = support
-    real, imag = real.float(), imag.float()       # no half-precision complex math
-    spec = torch.complex(real, imag) * math.sqrt(kh * kw)
-    return torch.fft.irfft2(spec, s=(kh, kw)).permute(2, 3, 0, 1)
+def kernel_from_rdft(real: torch.Tensor, imag: torch.Tensor, support, dtype=torch.float32):
+    """Inverse of the above (RDFTParameter.__call__, parameters.py:140-170), computed in `dtype`."""
+    spec = torch.complex(real.to(dtype), imag.to(dtype)) * math.sqrt(math.prod(support))      # no half-precision complex math
+    return torch.fft.irfftn(spec, s=tuple(support), dim=tuple(range(2, 2 + len(support)))).movedim((0, 1), (-2, -1))
 
 
 def gdn_reparam_init(initial_value: torch.Tensor, offset: float = 2 ** -18):
@@ -82,25 +81,15 @@ class RDFTParameter(Parameter):
         rank = len(self._shape)
         if rank not in (3, 4, 5):
             raise ValueError(f"Expected kernel tensor of rank 3, 4, or 5; received shape {self._shape}.")
-        n = rank - 2
-        spec = torch.fft.rfftn(initial_value.movedim((-2, -1), (0, 1)).float(), dim=tuple(range(2, 2 + n)))
-        spec = spec / math.sqrt(math.prod(self._shape[:-2]))
-        self.real = torch.nn.Parameter(spec.real.contiguous())
-        self.imag = torch.nn.Parameter(spec.imag.contiguous())
+        real, imag = rdft_from_kernel(initial_value)
+        self.real, self.imag = torch.nn.Parameter(real), torch.nn.Parameter(imag)
 
     dtype = property(lambda self: self._dtype)
     shape = property(lambda self: self._shape)
 
     def forward(self, compute_dtype=None):
-        real, imag = self.real, self.imag
-        if compute_dtype in (torch.bfloat16, torch.float16) or compute_dtype is None:
-            real, imag = real.float(), imag.float()          # no half-precision complex math
-        else:
-            real, imag = real.to(compute_dtype), imag.to(compute_dtype)
-        support = self._shape[:-2]
-        n = len(support)
-        spec = torch.complex(real, imag) * math.sqrt(math.prod(support))
-        kernel = torch.fft.irfftn(spec, s=support, dim=tuple(range(2, 2 + n))).movedim((0, 1), (-2, -1))
+        half = compute_dtype in (torch.bfloat16, torch.float16, None)
+        kernel = kernel_from_rdft(self.real, self.imag, self._shape[:-2], torch.float32 if half else compute_dtype)
         return kernel if compute_dtype is None else kernel.to(compute_dtype)
 
     def get_config(self):

@@ -25,6 +25,25 @@ def test_initial_value_is_reproduced_and_weights_round_trip(cls, shape):
         getattr(tfc, cls)(None)
 
 
+@pytest.mark.parametrize("shape", [(5, 5, 3, 4), (4, 3, 2, 2)])
+def test_rank2_rdft_is_bit_equal_to_the_rfft2_form(shape):
+    """The rank-generic pair (rfftn / irfftn over the support axes) gives, for an HWIO kernel, the bits of the rank-2
+    spelling it replaced."""
+    import math
+    from compression_amd.layers import parameters
+    torch.manual_seed(3)
+    kernel = torch.randn(shape)
+    kh, kw = shape[:2]
+    spec = torch.fft.rfft2(kernel.permute(2, 3, 0, 1)) / math.sqrt(kh * kw)
+    real, imag = parameters.rdft_from_kernel(kernel)
+    assert torch.equal(real, spec.real.contiguous()) and torch.equal(imag, spec.imag.contiguous())
+    assert real.is_contiguous() and imag.is_contiguous() and real.shape == (shape[2], shape[3], kh, kw // 2 + 1)
+    back = torch.fft.irfft2(torch.complex(real, imag) * math.sqrt(kh * kw), s=(kh, kw)).permute(2, 3, 0, 1)
+    got = parameters.kernel_from_rdft(real, imag, (kh, kw))
+    assert torch.equal(got, back) and got.stride() == back.stride()
+    assert torch.allclose(got, kernel, atol=1e-6)
+
+
 @pytest.mark.parametrize("shape", [(7, 3, 2), (5, 3, 1, 2)])
 def test_rdft_gradients_propagate(shape):
     torch.manual_seed(1)

@@ -691,3 +691,27 @@ def test_float32_layers_on_the_bfloat16_matrix_cores(case, monkeypatch):
     for mode in got:
         assert (got[mode] - want).abs().max().item() <= 4e-6 * scale, mode
     assert (got["split"] - got["native"]).abs().max().item() <= 8e-6 * scale
+
+
+@pytest.mark.parametrize("shape", [(5, 5, 3, 4), (4, 3, 2, 2), (9, 9, 16, 8)])
+def test_rank2_inverse_rdft_on_the_device_is_bit_equal_to_the_irfft2_form(shape):
+    """Under no_grad SignalConv2D.kernel runs the inverse RDFT on the device: the rank-generic spelling (irfftn over
+    the support axes) gives the bits of the rank-2 spelling it replaced, and so does the layer's kept kernel."""
+    import math
+    from compression_amd import layers
+    from compression_amd.layers import parameters
+    torch.manual_seed(3)
+    kh, kw = shape[:2]
+    real, imag = (t.cuda() for t in parameters.rdft_from_kernel(torch.randn(shape)))
+    want = torch.fft.irfft2(torch.complex(real, imag) * math.sqrt(kh * kw), s=(kh, kw)).permute(2, 3, 0, 1)
+    assert torch.equal(parameters.kernel_from_rdft(real, imag, (kh, kw)), want)
+    layer = layers.SignalConv2D(shape[3], (kh, kw), in_channels=shape[2]).cuda()
+    with torch.no_grad():
+        layer.kernel_real.copy_(real)
+        layer.kernel_imag.copy_(imag)
+        assert torch.equal(layer.kernel, want)
+    # and forward, on the device, for the parameters a layer is built with
+    kernel = torch.randn(shape, device="cuda")
+    spec = torch.fft.rfft2(kernel.permute(2, 3, 0, 1)) / math.sqrt(kh * kw)
+    got = parameters.rdft_from_kernel(kernel)
+    assert torch.equal(got[0], spec.real) and torch.equal(got[1], spec.imag)
