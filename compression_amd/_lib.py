@@ -126,6 +126,14 @@ SIGNATURES = {
                                                  _vp, _vp, _vp]),
     "tfc_noisy_normal_bits_forward_tail": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, C.c_float, _vp, _vp]),
     "tfc_noisy_normal_bits_backward_tail": (_int, [_vp, _vp, _vp, _int, _i64, _i64, C.c_float, _vp, _vp, _vp, _vp]),
+    "tfc_spectral_norm_forward": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "tfc_spectral_norm_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "tfc_disc_front_forward": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _vp]),
+    "tfc_disc_front_backward": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _vp]),
+    "tfc_lrelu_forward": (_int, [_vp, _int, _i64, _vp]),
+    "tfc_lrelu_bias_backward": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _int, _vp]),
+    "tfc_gan_loss_forward": (_int, [_vp, _int, _i64, _vp, _vp]),
+    "tfc_gan_loss_backward": (_int, [_vp, _vp, _int, _i64, _int, _vp, _vp]),
 }
 
 ABI_VERSION = 2          # include/tfc_hip.h TFC_ABI_VERSION this binding was written against

@@ -253,7 +253,7 @@ def conv2d_wgrad(a, b, kernel_support, stride, transpose):
     kh, kw = kernel_support
     ca, cb = a.shape[-1], b.shape[-1]
     built = (256, 192, 128, 64, 32)
-    if any(c > 4 and c not in built for c in (ca, cb)) and ca % 32 == 0 and cb % 32 == 0:
+    if any(c > 4 and c not in built for c in (ca, cb)) and all(c <= 4 or c % 32 == 0 for c in (ca, cb)):
         # the kernel is built for 32, 64, 128, 192 or 256 channels on either side; the gradient of a channel
         # block pair only needs those channels, so other widths (ms2020: 224, 320 .. 512) go in blocks
         def blocks(c):

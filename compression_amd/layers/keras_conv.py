@@ -131,7 +131,9 @@ class _KerasConvBase(cached.CachedValues, torch.nn.Module):
 class KerasConv2D(_KerasConvBase):
     """tf.keras.layers.Conv2D(filters, kernel_size, strides, padding="same") — kernel [kh, kw, in, out], bias [out]."""
 
-    def _run(self, x, kernel, bias, key):
+    def _run(self, x, kernel, bias, key, conv=None):
+        """`conv`: the launcher behind the window arithmetic (SpectralNormConv2D puts its own there)."""
+        conv = conv or functional.conv2d_down
         s = self.strides
         front, skip, back, outs = [], [], [], []
         for d in range(2):
@@ -146,7 +148,7 @@ class KerasConv2D(_KerasConvBase):
             back.append(max(0, (m + out - 1) * s + 1 - (length + a)))
         if any(front) or any(back):
             x = functional.pad2d(x, (front[0], back[0]), (front[1], back[1]))
-        y = functional.conv2d_down(x, kernel, bias, s, None, weights_key=key)
+        y = conv(x, kernel, bias, s, None, weights_key=key)
         if any(skip) or y.shape[1] != outs[0] or y.shape[2] != outs[1]:
             y = y[:, skip[0]:skip[0] + outs[0], skip[1]:skip[1] + outs[1]]
         return y

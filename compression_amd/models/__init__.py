@@ -1,8 +1,10 @@
 """Callers of the hot path: the model definitions (architecture and shapes of models/bls2017.py,
-models/bmshj2018.py, models/ms2020.py and models/hific; no training loop / dataset plumbing)."""
-from . import bls2017, bmshj2018, hific, ms2020
+models/bmshj2018.py, models/ms2020.py and models/hific; no dataset plumbing; HiFiC's GAN training step is
+hific_train)."""
+from . import bls2017, bmshj2018, hific, hific_train, ms2020
 from .bls2017 import BLS2017Model
 from .bmshj2018 import BMSHJ2018Model
 from .ms2020 import MS2020Model
-from .hific import HiFiCModel
+from .hific import Discriminator, HiFiCModel
+from .hific_train import HiFiCTrainer
 from .codec_io import compress_file, decompress_file, read_png, write_png  # noqa: F401

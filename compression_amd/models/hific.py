@@ -1,22 +1,29 @@
 """Mentzer, Toderici, Tschannen, Agustsson 2020, "High-Fidelity Generative Image Compression": the HiFiC codec
-(models/hific/archs.py:31-33, 67-211, 425-581; model.py:117-126, 511-590) — encoder, generator, hyperprior and the
-coding path.  Not here: the discriminator, the GAN and LPIPS losses, the training loop and the published checkpoints
-(DESIGN.md §12)."""
+(models/hific/archs.py:31-33, 67-211, 300-372, 425-581; model.py:117-126, 511-590) — encoder, generator, hyperprior,
+the coding path, and the conditional patch discriminator.  The losses and the alternating training step are in
+hific_train.py.  Not here: LPIPS weights, datasets and the published checkpoints."""
 from __future__ import annotations
 
+import collections
 import math
 
 import torch
 
 from .. import distributions, entropy_models, layers
-from ..layers import functional
+from ..layers import functional, gan_functional
 from ..layers.channel_norm import ChannelNorm
 from ..layers.keras_conv import KerasConv2D, KerasConv2DTranspose
+from ..layers.spectral_norm import SpectralNormConv2D
 from ..ops import round_ops
 from ..pipeline import inline_lane
 
-__all__ = ["Encoder", "Decoder", "ResidualBlock", "Hyperprior", "HiFiCModel", "padded_size", "latent_size",
-           "hyper_latent_size"]
+__all__ = ["Encoder", "Decoder", "ResidualBlock", "Hyperprior", "HiFiCModel", "Discriminator", "Nodes", "BppPair",
+           "padded_size", "latent_size", "hyper_latent_size"]
+
+# model.py:40-52: what the training step hands from the codec to the losses and the discriminator
+Nodes = collections.namedtuple("Nodes", ["input_image", "input_image_scaled", "reconstruction",
+                                         "reconstruction_scaled", "latent_quantized"])
+BppPair = collections.namedtuple("BppPair", ["total_nbpp", "total_qbpp"])
 
 SCALES_MIN, SCALES_MAX, SCALES_LEVELS = 0.11, 256.0, 64          # archs.py:31-33
 
@@ -157,6 +164,56 @@ class Hyperprior(torch.nn.Module):
         return scales.contiguous(), means.contiguous()
 
 
+class Discriminator(torch.nn.Module):
+    """archs.py:300-372, the conditional patch discriminator; every convolution is spectrally normalised
+    (SpectralNormConv2D), every leaky ReLU has slope 0.2:
+
+      latent [N, h, w, Cy] -> conv 12, 3x3 -> lrelu -> nearest resize to H x W -> concat behind x [N, H, W, 3] (15)
+      -> `num_layers` x (conv 4x4 / 2, lrelu) with base, 2 base, ... filters (at most 512)
+      -> conv 4x4 (the next width), lrelu -> conv 4x4 to 1 channel
+      -> logits reshaped to [-1, 1] and their sigmoid: (probabilities, logits).
+
+    `fused = True`: the front end (lrelu, resize, concat and the zero channels the next convolution wants) is one
+    launch, and each leaky ReLU runs in place behind its convolution with its backward fused with the bias gradient.
+    `fused = False`: the same normalised kernels with lrelu, resize, concat and padding as tensor ops (what the tests
+    compare the fused launches against)."""
+
+    def __init__(self, num_filters_base=64, num_layers=3, in_channels_latent=220):
+        super().__init__()
+        self.fused = True
+        self.latent_conv = SpectralNormConv2D(12, 3, in_channels=in_channels_latent)
+        widths, cin = [], 3 + 12
+        for i in range(num_layers + 1):
+            widths.append(min(num_filters_base * 2 ** i, 512))
+        convs = []
+        for i, c in enumerate(widths):
+            convs.append(SpectralNormConv2D(c, 4, strides=2 if i < num_layers else 1, in_channels=cin))
+            cin = c
+        self.convs = torch.nn.ModuleList(convs)
+        self.conv_out = SpectralNormConv2D(1, 4, in_channels=cin)
+
+    def output_size(self, h, w):
+        """Spatial extent of the logits for an H x W image (before they are flattened)."""
+        for conv in self.convs:
+            h, w = conv.output_size(h, w)
+        return self.conv_out.output_size(h, w)
+
+    def forward(self, x, latent):
+        if x.dim() != 4 or latent.dim() != 4 or x.shape[0] != latent.shape[0]:
+            raise ValueError(f"x [N, H, W, 3] and latent [N, h, w, C] expected, got {tuple(x.shape)}, "
+                             f"{tuple(latent.shape)}")
+        t = self.latent_conv(latent.to(x.dtype)).contiguous()
+        front = gan_functional.disc_front if self.fused else gan_functional.disc_front_composite
+        t = front(x, t, self.convs[0].padded_in_channels())
+        for conv in self.convs:
+            if self.fused:
+                t = conv(t, lrelu=True)
+            else:
+                t = torch.nn.functional.leaky_relu(conv(t), gan_functional.LRELU_SLOPE)
+        logits = self.conv_out(t).reshape(-1, 1)
+        return torch.sigmoid(logits), logits
+
+
 class HiFiCModel(torch.nn.Module):
     """The codec.  The reference's tfc.GaussianConditional(scales, scale_table, mean) (archs.py:518-532) is this
     project's LocationScaleIndexedEntropyModel over the same 64 log-spaced scales: the scale synthesis gives the table
@@ -220,6 +277,29 @@ class HiFiCModel(torch.nn.Module):
         y_hat = round_ops.round_st(y, means) if latents is None else latents
         x_hat = self.reconstruct(y_hat, x_shape) * 255.0
         return x_hat, bits.float() + side_bits.float()
+
+    def training_nodes(self, x):
+        """What the training step needs of one pass (model.py:365-455, archs.py:496-581, 653-687): x [B, H, W, 3] in
+        [0, 255] -> (Nodes(input, input / 255, reconstruction * 255, reconstruction, latent_quantized), BppPair(
+        total_nbpp, total_qbpp)).  The reconstruction comes from the straight-through quantised latents, total_nbpp
+        from the noisy likelihoods and total_qbpp from the quantised ones, each of latents plus hyper-latents as
+        batch-mean bits per pixel of the input."""
+        em, side = self._models(False)
+        x_shape = tuple(x.shape[1:3])
+        scaled = x.to(self.compute_dtype) / 255.0
+        y = self.encoder(self.pad_image(scaled))
+        z = self.hyperprior.analyse(y)
+        _, side_nbits = side(z, training=True)
+        z_hat, side_qbits = side(z, training=False)
+        scales, means = self.hyperprior.synthesise(z_hat.to(self.compute_dtype), tuple(y.shape[1:3]))
+        _, nbits = em(y, scales, loc=means, training=True)
+        _, qbits = em(y, scales, loc=means, training=False)
+        y_hat = round_ops.round_st(y, means)
+        rec = self.reconstruct(y_hat, x_shape)
+        pixels = float(x_shape[0] * x_shape[1])
+        nbpp = (nbits.float() + side_nbits.float()).mean() / pixels
+        qbpp = (qbits.float() + side_qbits.float()).mean() / pixels
+        return Nodes(x, scaled, rec * 255.0, rec, y_hat), BppPair(nbpp, qbpp)
 
     @torch.no_grad()
     def latents(self, x):

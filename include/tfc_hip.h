@@ -680,6 +680,56 @@ int tfc_noisy_normal_bits_backward_tail(const void* y_in, const void* y_hat, con
                                         int64_t units, int64_t elems, float laplace_tail_mass, const float* gbits,
                                         void* dy, float* dscale, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* HiFiC discriminator and GAN loss                                         */
+/* ------------------------------------------------------------------------ */
+
+/* Spectral normalisation of a convolution kernel — models/hific/archs.py:340-367 (`arch_ops.conv2d(..., use_sn=True)`
+ * of compare_gan, which the reference imports at archs.py:24), one power iteration, epsilon 1e-12:
+ *   W = kernel [kh, kw, cin, cout] read as [rows = kh kw cin, cols = cout];  l2n(a) = a rsqrt(max(sum a^2, 1e-12))
+ *   v = l2n(W^T u);   u' = l2n(W v);   sigma = u'^T W v;   w_sn = W / sigma  (the same layout as W).
+ * w, u [rows], w_sn, u_out [rows], v_out [cols], sigma [1]: DEV float32.  No float atomics: two calls, equal bits. */
+int tfc_spectral_norm_forward(const float* w, const float* u, int64_t rows, int64_t cols, float* w_sn, float* u_out,
+                              float* v_out, float* sigma, void* stream);
+/* Its backward (the reference relies on TF autodiff with u' and v held constant): g = dL/dw_sn,
+ *   dw = g / sigma - (<g, W> / sigma^2) u' v^T.      u = u' and v, sigma as the forward wrote them. */
+int tfc_spectral_norm_backward(const float* g, const float* w, const float* u, const float* v, const float* sigma,
+                               int64_t rows, int64_t cols, float* dw, void* stream);
+
+/* The discriminator's front end — models/hific/archs.py:342-347 (lrelu, tf.image.resize NEAREST, tf.concat) plus the
+ * zero channels the next convolution wants, one pass:
+ *   out[n, y, x, :] = x[n, y, x, :image_channels] | lrelu(latent[n, sy, sx, :latent_channels]) | zeros
+ *   sy = min(floor((2 y + 1) latent_height / (2 height)), latent_height - 1), sx likewise; lrelu(a) = max(a, 0.2 a).
+ * x DEV [n, height, width, image_channels], latent DEV [n, latent_height, latent_width, latent_channels] (the latent
+ * branch's convolution output), out DEV [n, height, width, padded_channels]; dtype 0 f32, 1 bf16.
+ * image_channels + latent_channels <= 16 and <= padded_channels, a multiple of 4 up to 1024; axes up to 32768. */
+int tfc_disc_front_forward(const void* x, const void* latent, void* out, int dtype, int64_t n, int64_t height,
+                           int64_t width, int64_t latent_height, int64_t latent_width, int image_channels,
+                           int latent_channels, int padded_channels, void* stream);
+/* Its backward: g = dL/dout;  dx = g[..., :image_channels];  dlatent[n, sy, sx, c] = (latent > 0 ? 1 : 0.2) times the
+ * sum of g[n, y, x, image_channels + c] over the pixels whose source is (sy, sx), in a fixed order. */
+int tfc_disc_front_backward(const void* g, const void* latent, void* dx, void* dlatent, int dtype, int64_t n,
+                            int64_t height, int64_t width, int64_t latent_height, int64_t latent_width,
+                            int image_channels, int latent_channels, int padded_channels, void* stream);
+
+/* arch_ops.lrelu(net, leak=0.2) — models/hific/archs.py:351, 358, 363 — in place: y = max(y, 0.2 y), `count` values. */
+int tfc_lrelu_forward(void* y, int dtype, int64_t count, void* stream);
+/* Its backward fused with the bias gradient of the convolution in front of it, one pass over gy and y [pixels,
+ * channels]: gm = gy (y > 0 ? 1 : 0.2) (dtype), dbias[c] = sum over pixels of gm (float32, before gm is rounded; fixed
+ * order).  masked = 0: no activation, only dbias = the sum of gy (y and gm unused).  dbias may be NULL. */
+int tfc_lrelu_bias_backward(const void* gy, const void* y, void* gm, float* dbias, int dtype, int64_t pixels,
+                            int64_t channels, int masked, void* stream);
+
+/* compare_gan's non_saturating loss as models/hific/model.py:616-638 calls it.  logits DEV [2 half], real half first;
+ * sce(x, z) = max(x, 0) - x z + log1p(exp(-|x|));
+ *   out[0] = d_loss = mean sce(real, 1) + mean sce(fake, 0);   out[1] = g_loss = mean sce(fake, 1);
+ *   out[2] = mean sigmoid(real);   out[3] = mean sigmoid(fake)   (model.py:761-762).   out DEV float32 [4]. */
+int tfc_gan_loss_forward(const void* logits, int dtype, int64_t half, float* out, void* stream);
+/* grad = *scale (sigmoid(x) - z) / half for mode 0 (d_loss) or, mode 1 (g_loss), the fake half with z = 1 and zeros for
+ * the real half.  scale DEV float32 [1]: the incoming gradient of the loss.  grad DEV [2 half] dtype. */
+int tfc_gan_loss_backward(const void* logits, const float* scale, int dtype, int64_t half, int mode, void* grad,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
