@@ -246,14 +246,23 @@ def conv2d_gdn(x, kernel, bias, stride, up, prepared: GDNPrepared, inverse: bool
     return y, bool(fused.value)
 
 
+def _wgrad_width(c):
+    """The channel count the weight gradient kernel runs a side of `c` channels at: 1 ... 4, or a multiple of 32."""
+    return c if c <= 4 else c + -c % 32
+
+
 def conv2d_wgrad(a, b, kernel_support, stride, transpose):
     """Weight gradient kernel: G[t][ca][cb] = sum A[n, q*s + t - k/2, ca] B[n, q, cb] as a float32
-    [kh, kw, Cin, Cout] tensor (transpose=True: A carries Cout, B carries Cin)."""
+    [kh, kw, Cin, Cout] tensor (transpose=True: A carries Cout, B carries Cin).  A side of more than 4 channels that is
+    no multiple of 32 gets zero channels up to the next one, sliced off the result."""
     _lib.require_device()
-    kh, kw = kernel_support
     ca, cb = a.shape[-1], b.shape[-1]
+    if (_wgrad_width(ca), _wgrad_width(cb)) != (ca, cb):
+        dw = conv2d_wgrad(pad_channels(a, _wgrad_width(ca)), pad_channels(b.to(a.dtype), _wgrad_width(cb)),
+                          kernel_support, stride, transpose)
+        return dw[..., :cb, :ca] if transpose else dw[..., :ca, :cb]
     built = (256, 192, 128, 64, 32)
-    if any(c > 4 and c not in built for c in (ca, cb)) and all(c <= 4 or c % 32 == 0 for c in (ca, cb)):
+    if any(c > 4 and c not in built for c in (ca, cb)):
         # the kernel is built for 32, 64, 128, 192 or 256 channels on either side; the gradient of a channel
         # block pair only needs those channels, so other widths (ms2020: 224, 320 .. 512) go in blocks
         def blocks(c):
@@ -271,6 +280,12 @@ def conv2d_wgrad(a, b, kernel_support, stride, transpose):
                     for b0, b1 in blocks(cb)]
             rows.append(torch.cat(cols, dim=2 if transpose else 3))
         return torch.cat(rows, dim=3 if transpose else 2)
+    return _conv2d_wgrad_launch(a, b, kernel_support, stride, transpose)
+
+
+def _conv2d_wgrad_launch(a, b, kernel_support, stride, transpose):
+    """tfc_conv2d_wgrad (include/tfc_hip.h) on channel counts it is built for."""
+    kh, kw = kernel_support
     a, b = a.contiguous(), b.contiguous()
     n, ha, wa, ca = a.shape
     _, hb, wb, cb = b.shape
@@ -343,11 +358,14 @@ class _ConvFunction(torch.autograd.Function):
             gy = gy * (y > 0)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            kt = kernel.transpose(-1, -2)
+            g, kt = gy, kernel.transpose(-1, -2)
+            if rank == 2 and g.shape[-1] > 4:
+                # the rank-2 kernels take 1 ... 4 or a multiple of 16 input channels: here the layer's `filters`
+                g, kt = pad_channels(g), pad_channels(kt, dim=-2)
             if up:
-                dx = launch(gy, kt, None, strides, None, False)
+                dx = launch(g, kt, None, strides, None, False)
             else:
-                dx = launch(gy, kt, None, strides, None, True)[(slice(None),) + tuple(slice(n) for n in x.shape[1:-1])]
+                dx = launch(g, kt, None, strides, None, True)[(slice(None),) + tuple(slice(n) for n in x.shape[1:-1])]
         if ctx.needs_input_grad[1]:
             support = tuple(kernel.shape[:rank])
             dw = wgrad(gy, x, support, strides, True) if up else wgrad(x, gy, support, strides, False)

@@ -76,7 +76,7 @@ class SignalConv(torch.nn.Module):
     # signal_conv.py:416-419: None means padding.startswith("same_")
     _extra_pad_end_default = None
     # the kernels take 1 ... _narrow_channels or a multiple of 16 input channels; zero channels are added in forward()
-    # for every configuration, or in the general path only (the models then have to come with counts that fit)
+    # for every configuration, or by the two paths themselves (rank 2, whose separable kernel is padded once dense)
     _narrow_channels = 0
     _pads_channels_in_forward = True
 
@@ -331,7 +331,8 @@ class SignalConv1D(SignalConv3D):
 
 class SignalConv2D(cached.CachedValues, SignalConv):
     """2-D signal convolution layer (signal_conv.py:1037-1041) on tfc_conv2d_*: one stride for both axes (unequal
-    strides run at stride 1), 1 ... 4 or a multiple of 16 input channels.  Under no_grad it keeps the kernel of its
+    strides run at stride 1), 1 ... 4 or a multiple of 16 input channels (other counts get zero channels up to the next
+    multiple, in the forward pass and in both gradients).  Under no_grad it keeps the kernel of its
     RDFT parameters and names the value of its weights to the library (`keyed_weights`), and it takes a GDN layer as
     its activation into the convolution kernel."""
     _rank = 2
@@ -419,6 +420,7 @@ class SignalConv2D(cached.CachedValues, SignalConv):
         act = self.activation
         fused = _fused_relu(act)
         corr, up, down = self.corr, self.strides_up[0], self.strides_down[0]
+        x, kernel = self._pad_channels(x, kernel)              # (the models' counts fit and pass through as they are)
         wkey = self._inference_weights_key() if x.is_cuda else 0
         if corr and up != 1:
             corr, kernel = False, self._flipped(kernel)        # signal_conv.py:875-880

@@ -20,7 +20,7 @@ def emu_down(x, kernel, bias=None, stride=1, activation=None, weights_key=0):
     assert c <= 4 or c % 16 == 0, "the kernels take 1..4 or a multiple of 16 input channels"
     oh, ow = -(-h // stride), -(-w // stride)
     xp = torch.nn.functional.pad(x.permute(0, 3, 1, 2).double(), (kw // 2, kw + stride, kh // 2, kh + stride))
-    y = torch.nn.functional.conv2d(xp, kernel.permute(3, 2, 0, 1).double(), stride=stride)[:, :, :oh, :ow]
+    y = torch.nn.functional.conv2d(xp, kernel.permute(3, 2, 0, 1).double().contiguous(), stride=stride)[:, :, :oh, :ow]
     return y.permute(0, 2, 3, 1).to(x.dtype).contiguous()
 
 
@@ -29,7 +29,8 @@ def emu_up(x, kernel, bias=None, stride=1, activation=None, weights_key=0):
     n, h, w, c = x.shape
     assert c <= 4 or c % 16 == 0
     # conv_transpose2d = the full convolution f of the zero-upsampled input: f[m] = sum_q x[q] w[m - q s]
-    f = torch.nn.functional.conv_transpose2d(x.permute(0, 3, 1, 2).double(), kernel.permute(2, 3, 0, 1).double(), stride=stride)
+    f = torch.nn.functional.conv_transpose2d(x.permute(0, 3, 1, 2).double(), kernel.permute(2, 3, 0, 1).double().contiguous(),
+                                           stride=stride)
     f = torch.nn.functional.pad(f, (0, stride + kw, 0, stride + kh))
     y = f[:, :, kh // 2:kh // 2 + h * stride, kw // 2:kw // 2 + w * stride]
     return y.permute(0, 2, 3, 1).to(x.dtype).contiguous()

@@ -293,6 +293,9 @@ def test_conv_gradients_bf16_and_module():
     out.square().sum().backward()
     grads = [p.grad for p in layer.parameters()]
     assert grads and all(g is not None and torch.isfinite(g).all() and g.abs().sum() > 0 for g in grads)
+    # and their values, against the float64 definition on integer inputs and cotangents (tests/signal_conv_oracle.py)
+    from test_signal_conv_grad_gpu import check_module, integers
+    check_module(layer, integers((1, 6, 6, 64), 0, 7, 1))
 
 
 @pytest.mark.parametrize("ca,cb,k,s,transpose", [
@@ -654,6 +657,8 @@ def test_default_argument_layer_on_the_device():
     assert np.max(np.abs(np.moveaxis(y.cpu().numpy(), -1, 1) - want)) <= 1e-5
     layer(x).square().sum().backward()
     assert all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in layer.parameters())
+    from test_signal_conv_grad_gpu import check_module, integers
+    check_module(layer, integers((2, 8, 9, 3), 0, 7, 1))        # the values, against the float64 definition
 
 
 F32_SPLIT_CASES = [  # up, n, h, w, cin, cout, k, s — layer shapes of the models, float32

@@ -26,7 +26,7 @@ def emu_down(x, kernel, bias=None, strides=1, activation=None):
     for a in (2, 1, 0):
         pad += [k[a] // 2, k[a] + s[a]]
     xp = torch.nn.functional.pad(x.permute(0, 4, 1, 2, 3).double(), pad)
-    y = torch.nn.functional.conv3d(xp, kernel.permute(4, 3, 0, 1, 2).double(), stride=s)[:, :, :out[0], :out[1], :out[2]]
+    y = torch.nn.functional.conv3d(xp, kernel.permute(4, 3, 0, 1, 2).double().contiguous(), stride=s)[:, :, :out[0], :out[1], :out[2]]
     return _epilogue(y.permute(0, 2, 3, 4, 1), bias, activation).to(x.dtype).contiguous()
 
 
@@ -34,7 +34,7 @@ def emu_up(x, kernel, bias=None, strides=1, activation=None):
     s = (strides,) * 3 if isinstance(strides, int) else tuple(strides)
     k = kernel.shape[:3]
     # conv_transpose3d = the full convolution of the zero-upsampled input: f[m] = sum_q x[q] w[m - q s]
-    f = torch.nn.functional.conv_transpose3d(x.permute(0, 4, 1, 2, 3).double(), kernel.permute(3, 4, 0, 1, 2).double(),
+    f = torch.nn.functional.conv_transpose3d(x.permute(0, 4, 1, 2, 3).double(), kernel.permute(3, 4, 0, 1, 2).double().contiguous(),
                                              stride=s)
     f = torch.nn.functional.pad(f, (0, s[2] + k[2], 0, s[1] + k[1], 0, s[0] + k[0]))
     sl = [slice(k[a] // 2, k[a] // 2 + x.shape[1 + a] * s[a]) for a in range(3)]

@@ -65,6 +65,14 @@ def test_gradients_reach_every_parameter():
     (y1.square().sum() + y3.square().sum()).backward()
     for p in (l1.kernel_real, l1.kernel_imag, l1.bias, l3.kernel_variable, l3.bias):
         assert p.grad is not None and torch.isfinite(p.grad).all() and p.grad.abs().sum() > 0
+    # and their values, against the float64 definition (tests/signal_conv_oracle.py) on integer inputs and cotangents:
+    # the rdft layer at its random kernel, the ReLU layer at integer weights (everything exact)
+    from test_signal_conv_grad_gpu import check_module, integers
+    check_module(l1, integers((2, 20, 8), 0, 7, 1))
+    with torch.no_grad():
+        l3.kernel_variable.copy_(integers(l3.kernel_variable.shape, -3, 3, 2))
+        l3.bias.copy_(integers(l3.bias.shape, -20, 20, 3))
+    check_module(l3, integers((2, 3, 4, 5, 16), 0, 7, 4))
 
 
 def test_small_3d_autoencoder_trains():
