@@ -92,6 +92,10 @@ SIGNATURES = {
                                 _int, _vp, _vp, _vp]),
     "tfc_channel_norm_forward": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, C.c_float, _int, _vp]),
     "tfc_channel_norm_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, C.c_float, _int, _vp]),
+    "tfc_lpips_distance_forward": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, C.c_float, _vp]),
+    "tfc_lpips_distance_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, C.c_float, _int, _vp]),
+    "tfc_maxpool2d_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _int, _int, _vp]),
+    "tfc_maxpool2d_backward": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _int, _int, _vp]),
     "tfc_ssim_scale_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, C.POINTER(C.c_float), _int, C.c_float,
                                       C.c_float, _vp, _vp, _vp, _vp]),
     "tfc_ssim_scale_backward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, C.POINTER(C.c_float), _int, C.c_float,

@@ -512,3 +512,155 @@ def pad2d(x, pad_h, pad_w, reflect=False):
         i = torch.arange(-before, length + after, device=x.device).abs()
         return torch.where(i >= length, 2 * (length - 1) - i, i)
     return x.index_select(1, mirror(h, t, b)).index_select(2, mirror(w, l, r))
+
+
+def _pool_windows(x, k, s):
+    """The k * k shifted views of an NHWC tensor whose element [n, i, j] is that of window (i, j), in the window's
+    row-major order -> [N, OH, OW, k * k, C]."""
+    n, h, w, c = x.shape
+    oh, ow = (h - k) // s + 1, (w - k) // s + 1
+    return torch.stack([x[:, i:i + s * (oh - 1) + 1:s, j:j + s * (ow - 1) + 1:s]
+                        for i in range(k) for j in range(k)], dim=3)
+
+
+def _pool_args(x, kernel_size, stride):
+    k, s = int(kernel_size), int(stride)
+    if x.dim() != 4:
+        raise ValueError(f"Input tensor must have rank 4, received shape {tuple(x.shape)}.")
+    if k < 1 or s < 1 or x.shape[1] < k or x.shape[2] < k:
+        raise ValueError(f"a {x.shape[1]} x {x.shape[2]} image holds no {k} x {k} window (stride {s})")
+    return k, s
+
+
+def max_pool2d_reference(x, kernel_size=3, stride=2):
+    """The definition of `max_pool2d` as differentiable tensor ops: NHWC, no padding, out = (in - k) // s + 1.  The
+    gradient of a window goes to its FIRST maximum in row-major order (torch.argmax returns the first): what
+    `max_pool2d` evaluates for a CPU tensor."""
+    k, s = _pool_args(x, kernel_size, stride)
+    win = _pool_windows(x, k, s)
+    first = win.detach().float().argmax(dim=3, keepdim=True) if win.dtype == torch.bfloat16 else \
+        win.detach().argmax(dim=3, keepdim=True)
+    return win.gather(3, first).squeeze(3)
+
+
+class _MaxPoolFunction(torch.autograd.Function):
+    """tfc_maxpool2d_forward / _backward (include/tfc_hip.h): the forward keeps x, the backward finds the winners again."""
+
+    @staticmethod
+    def forward(ctx, x, k, s):
+        x = x.contiguous()
+        n, h, w, c = x.shape
+        y = torch.empty((n, (h - k) // s + 1, (w - k) // s + 1, c), dtype=x.dtype, device=x.device)
+        _lib.check(_lib.lib().tfc_maxpool2d_forward(x.data_ptr(), y.data_ptr(), _DTYPE_CODE[x.dtype], n, h, w, c, k, s,
+                                                    _lib.stream_ptr()))
+        ctx.save_for_backward(x)
+        ctx.cfg = (k, s)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, = ctx.saved_tensors
+        k, s = ctx.cfg
+        n, h, w, c = x.shape
+        gy = gy.to(x.dtype).contiguous()
+        dx = torch.empty_like(x)
+        _lib.check(_lib.lib().tfc_maxpool2d_backward(x.data_ptr(), gy.data_ptr(), dx.data_ptr(), _DTYPE_CODE[x.dtype],
+                                                     n, h, w, c, k, s, _lib.stream_ptr()))
+        return dx, None, None
+
+
+def max_pool2d(x, kernel_size=3, stride=2):
+    """Max-pool of an NHWC tensor, window `kernel_size`, no padding, out = (in - k) // s + 1, on the HIP kernels
+    (float32 / bfloat16); differentiable in x, ties to the first element of a window.  CPU tensors take
+    `max_pool2d_reference`."""
+    k, s = _pool_args(x, kernel_size, stride)
+    if not x.is_cuda:
+        return max_pool2d_reference(x, k, s)
+    if x.dtype not in _DTYPE_CODE:
+        raise TypeError(f"max-pool kernel supports float32 and bfloat16, got {x.dtype}")
+    return _MaxPoolFunction.apply(x, k, s)
+
+
+class _UnitNormalize(torch.autograd.Function):
+    """f / (|f| + eps) over the last axis with its derivative written out, g / (n + eps) - f (f . g) / (n (n + eps)^2)
+    and the second term 0 where n = 0: autograd's own sqrt gives inf * 0 at an all-zero pixel."""
+
+    @staticmethod
+    def forward(ctx, f, eps):
+        n = f.pow(2).sum(dim=-1, keepdim=True).sqrt()
+        ctx.save_for_backward(f, n)
+        ctx.eps = eps
+        return f / (n + eps)
+
+    @staticmethod
+    def backward(ctx, g):
+        f, n = ctx.saved_tensors
+        dot = (f * g).sum(dim=-1, keepdim=True)
+        second = torch.where(n > 0, dot / (n * (n + ctx.eps) ** 2), torch.zeros_like(n))
+        return g / (n + ctx.eps) - f * second, None
+
+
+def _distance_args(f0, f1, w):
+    if f0.shape != f1.shape or f0.dim() < 3:
+        raise ValueError(f"feature shapes {tuple(f0.shape)} / {tuple(f1.shape)} must match and be [N, ..., C]")
+    c = f0.shape[-1]
+    if w.shape != (c,):
+        raise ValueError(f"weight shape {tuple(w.shape)} does not match C={c}")
+    n = f0.shape[0]
+    p = f0.numel() // (n * c) if n else 1
+    if p < 1:
+        raise ValueError(f"features {tuple(f0.shape)} hold no pixel")
+    return n, p, c
+
+
+def lpips_distance_reference(f0, f1, w, epsilon=1e-10):
+    """The definition of `lpips_distance` as differentiable tensor ops in float32 (a float64 input stays float64), the
+    normalisation's gradient in the explicit form: what `lpips_distance` evaluates for CPU tensors."""
+    n, p, c = _distance_args(f0, f1, w)
+    ft = torch.float64 if f0.dtype == torch.float64 else torch.float32
+    u = _UnitNormalize.apply(f0.to(ft).reshape(n, p, c), float(epsilon))
+    v = _UnitNormalize.apply(f1.to(ft).reshape(n, p, c), float(epsilon))
+    return ((u - v) ** 2 * w.to(ft)).sum(dim=-1).mean(dim=-1)
+
+
+class _LpipsDistanceFunction(torch.autograd.Function):
+    """tfc_lpips_distance_forward / _backward (include/tfc_hip.h).  A gradient nobody needs is not written."""
+
+    @staticmethod
+    def forward(ctx, f0, f1, w, epsilon):
+        n, p, c = _distance_args(f0, f1, w)
+        f0, f1 = f0.contiguous(), f1.to(f0.dtype).contiguous()
+        d = torch.empty(n, dtype=torch.float32, device=f0.device)
+        _lib.check(_lib.lib().tfc_lpips_distance_forward(
+            f0.data_ptr(), f1.data_ptr(), w.data_ptr(), d.data_ptr(), _DTYPE_CODE[f0.dtype], n, p, c, epsilon,
+            _lib.stream_ptr()))
+        ctx.save_for_backward(f0, f1, w)
+        ctx.cfg = (n, p, c, epsilon)
+        return d
+
+    @staticmethod
+    def backward(ctx, g):
+        f0, f1, w = ctx.saved_tensors
+        n, p, c, epsilon = ctx.cfg
+        g = g.to(torch.float32).contiguous()
+        df0 = torch.empty_like(f0) if ctx.needs_input_grad[0] else None
+        df1 = torch.empty_like(f1) if ctx.needs_input_grad[1] else None
+        mask = (1 if df0 is not None else 0) | (2 if df1 is not None else 0)
+        _lib.check(_lib.lib().tfc_lpips_distance_backward(
+            g.data_ptr(), f0.data_ptr(), f1.data_ptr(), w.data_ptr(), _ptr(df0), _ptr(df1), _DTYPE_CODE[f0.dtype],
+            n, p, c, epsilon, mask, _lib.stream_ptr()))
+        return df0, df1, None, None
+
+
+def lpips_distance(f0, f1, w, epsilon=1e-10):
+    """One tap of LPIPS: features f0, f1 [N, ..., C] (float32 / bfloat16), w [C] -> float32 [N],
+    mean over pixels of sum_c w[c] (f0 / (|f0| + eps) - f1 / (|f1| + eps))^2, in one pass on the HIP kernel;
+    differentiable in f0 and f1 (w is frozen).  CPU tensors take `lpips_distance_reference`."""
+    if not f0.is_cuda:
+        return lpips_distance_reference(f0, f1, w, epsilon)
+    if f0.dtype not in _DTYPE_CODE:
+        raise TypeError(f"LPIPS distance kernel supports float32 and bfloat16, got {f0.dtype}")
+    if w.requires_grad:
+        raise ValueError("the LPIPS layer weights are frozen: lpips_distance gives no gradient for w")
+    w = w.detach().to(f0.device, torch.float32).contiguous()
+    return _LpipsDistanceFunction.apply(f0, f1, w, float(epsilon))

@@ -1,8 +1,9 @@
 """HiFiC's losses and its alternating discriminator / generator training step (models/hific/configs.py:20-77;
 model.py:61-115, 365-455, 588-764, 800-837, 875-897) on this library's kernels.
 
-Not here: datasets and the input pipeline, summaries, checkpoints and hooks.  LPIPS needs downloaded weights: a user
-passes it as `perceptual_loss(fake_scaled, real_scaled) -> scalar`.  The reference's third ("aux") optimiser minimises
+Not here: datasets and the input pipeline, summaries, checkpoints and hooks.  The perceptual term is
+`perceptual_loss(fake_scaled, real_scaled) -> scalar`: `layers.LPIPSLoss(layers.LPIPS.from_lpips_package(...))` is LPIPS
+on this library's kernels (the network is here, its trained weights are the user's), or any other callable.  The reference's third ("aux") optimiser minimises
 the entropy model's auxiliary loss (model.py:807-811); the entropy models of this library have no auxiliary loss (their
 tails are solved on the device, not learned), so there are three optimisers: transform, entropy, disc."""
 from __future__ import annotations

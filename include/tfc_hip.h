@@ -478,6 +478,44 @@ int tfc_channel_norm_backward(const void* x, const void* g, const float* gamma, 
                               int relu, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* LPIPS: the distance head and the max-pool                                */
+/* ------------------------------------------------------------------------ */
+
+/* The per-layer distance of LPIPS (Zhang et al. 2018; HiFiC's perceptual loss, models/hific/model.py:840-872, which
+ * loads it as a frozen graph: the definition here is the paper's, checked against a float64 evaluation of it).
+ * f0, f1 DEV [images, pixels, channels] dtype (0 f32, 1 bf16), channels innermost; w DEV f32 [channels]:
+ *   n0 = sqrt(sum_c f0^2), n1 = sqrt(sum_c f1^2) per pixel
+ *   d[image] = 1 / pixels * sum_p sum_c w[c] (f0[p,c] / (n0 + epsilon) - f1[p,c] / (n1 + epsilon))^2     DEV f32 [images]
+ * One pass: a pixel's two rows stay in registers, and the difference is taken before it is squared (the expanded
+ * form cancels where f0 ~ f1).  Rows that are multiples of 16 bytes up to 2 KB take 16-byte accesses, any other a
+ * wave-per-pixel kernel.  Deterministic: per-workgroup sums are added in a fixed order, no float atomics.
+ * epsilon finite and >= 0; pixels >= 1; images == 0 returns 0. */
+int tfc_lpips_distance_forward(const void* f0, const void* f1, const float* w, float* d, int dtype, int64_t images,
+                               int64_t pixels, int64_t channels, float epsilon, void* stream);
+
+/* Backward of tfc_lpips_distance_forward.  g DEV f32 [images]; mask bit 0: df0 is wanted, bit 1: df1; a gradient that
+ * is not wanted is not written and may be NULL.  df0, df1 DEV [images, pixels, channels] dtype.  With
+ * a = 1 / (n0 + epsilon), b = 1 / (n1 + epsilon) and e = 2 g[image] / pixels * w (a f0 - b f1):
+ *   df0 =  e a - f0 (f0 . e) a^2 / n0,   df1 = -e b + f1 (f1 . e) b^2 / n1,
+ * the second term 0 where the norm is 0: the derivative of f / (|f| + epsilon) written out, which is finite at an
+ * all-zero pixel (sqrt's own derivative there is inf * 0).  The norms are recomputed from f0 and f1. */
+int tfc_lpips_distance_backward(const float* g, const void* f0, const void* f1, const float* w, void* df0, void* df1,
+                                int dtype, int64_t images, int64_t pixels, int64_t channels, float epsilon, int mask,
+                                void* stream);
+
+/* Max-pool, window k x k, stride s, no padding: x DEV [n, h, w, c] dtype (0 f32, 1 bf16), y DEV
+ * [n, (h - k) / s + 1, (w - k) / s + 1, c] (floor).  A NaN in a window is its maximum, as in torch.  h, w >= k. */
+int tfc_maxpool2d_forward(const void* x, void* y, int dtype, int64_t n, int64_t h, int64_t w, int64_t c, int k, int s,
+                          void* stream);
+
+/* Backward of tfc_maxpool2d_forward as a gather, no atomics: dx[i] = sum of g over the windows whose maximum element i
+ * is, the windows in row-major order, summed in float32.  A window's maximum is found from x again (the forward
+ * stores nothing but y); among equal values it is the FIRST in the window's row-major order.  g DEV dtype, the shape
+ * of y; dx DEV dtype, the shape of x, WRITTEN. */
+int tfc_maxpool2d_backward(const void* x, const void* g, void* dx, int dtype, int64_t n, int64_t h, int64_t w,
+                           int64_t c, int k, int s, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* SSIM / multiscale SSIM, one scale per call                               */
 /* ------------------------------------------------------------------------ */
 
