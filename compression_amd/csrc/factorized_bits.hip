@@ -47,7 +47,6 @@ __device__ inline float fast_log1p(float x) { return __logf(1.f + x); }
 __device__ inline float log_sigmoid(float x) {     // log(1 / (1 + exp(-x))), stable both ways
   return fminf(x, 0.f) - fast_log1p(__expf(-fabsf(x)));
 }
-__device__ inline float sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 
 // logits of the cumulative at z; optionally keeps the activations the backward pass needs:
 // h[l][i] = output of layer l (after the gate), th[l][i] = tanh of its pre-gate value.
@@ -173,15 +172,24 @@ __global__ void factorized_bits_reduce_kernel(const float* partial, int blocks_p
   bits[u] = s * -1.4426950408889634f;          // / -ln 2
 }
 
-// c(upper) - c(lower), on the side of the median where it does not cancel
-__device__ inline float interval_prob(float upper, float lower) {
-  return upper > 0.f ? sigmoid(-lower) - sigmoid(-upper) : sigmoid(upper) - sigmoid(lower);
+// log sigmoid(x) and log sigmoid(-x) from one exp and one log: they differ by x exactly
+struct LogSigmoidPair { float pos, neg; };
+__device__ inline LogSigmoidPair log_sigmoid_pair(float x) {
+  const float a = fast_log1p(__expf(-fabsf(x)));
+  return {fminf(x, 0.f) - a, fminf(-x, 0.f) - a};
 }
-// d log_interval / d(upper, lower) = sigma'(u) * inv, -sigma'(l) * inv with inv = 1 / prob
-// (with a Laplace tail: inv = (1 - m) / mixture, laplace_tail.h)
-__device__ inline void log_interval_grad(float upper, float lower, float inv, float* gu, float* gl) {
-  *gu = sigmoid(upper) * sigmoid(-upper) * inv;
-  *gl = -sigmoid(lower) * sigmoid(-lower) * inv;
+// d log P / d(upper, lower) = sigma'(u) / P, -sigma'(l) / P with sigma'(u) = sigmoid(u) sigmoid(-u): the ratios
+// are formed in LOG space, as noisy_normal_bits.hip forms phi / P.  In probability space every sigmoid is 0
+// once |logit| passes ~90 and sigma' * (1 / P) is 0 * inf there; the ratio itself is bounded
+// (1 / (exp(|u - l|) - 1) in the tails).  ds_up, ds_lo: log sigma' at both ends.
+// P = exp(big) (1 - ratio), ratio = exp(small - big)
+struct IntervalLogs { float big, ratio, ds_up, ds_lo; };
+__device__ inline IntervalLogs interval_logs(float upper, float lower) {
+  const LogSigmoidPair u = log_sigmoid_pair(upper), l = log_sigmoid_pair(lower);
+  const bool right = upper > 0.f;
+  const float big = right ? l.neg : u.pos;
+  const float small = right ? u.neg : l.pos;
+  return {big, __expf(small - big), u.pos + u.neg, l.pos + l.neg};
 }
 
 template <int K, int W>
@@ -257,15 +265,23 @@ __global__ void __launch_bounds__(MAXT) factorized_backward_kernel(BitsParams p)
     const float v = load_as_float(yh, e);
     const float up = mlp_forward<K, W, false>(prm, v + 0.5f, nullptr, nullptr);
     const float lo = mlp_forward<K, W, false>(prm, v - 0.5f, nullptr, nullptr);
-    const float prob = interval_prob(up, lo);
-    float inv = 1.f / prob, direct = 0.f;
+    const IntervalLogs il = interval_logs(up, lo);
+    float gu, gl, direct = 0.f;
     if (p.tail_mass > 0.f) {
-      const TailGrad tg = tail_mix_grad(prob, v, p.tail_mass);
-      inv = tg.prior;
+      // d log(mixture) = (1 - m) dP / mixture + m dQ / mixture (laplace_tail.h).  Where P has underflowed and
+      // the tail keeps the mixture alive, sigma' has underflowed with it: the prior's share is 0, not NaN.
+      const TailGrad tg = tail_mix_grad(__expf(il.big) * (1.f - il.ratio), v, p.tail_mass);
+      gu = __expf(il.ds_up) * tg.prior;
+      gl = -__expf(il.ds_lo) * tg.prior;
       direct = tg.direct;
+    } else {
+      // sigma' / P = exp(log sigma' - big) / (1 - ratio): one log less than exp(log sigma' - log P)
+      // 1 - ratio is 0 only where the logit is flat at float32 resolution (upper == lower); 2^-24 is the
+      // smallest difference it can otherwise take, so the guard changes nothing else and keeps dy finite
+      const float r = __builtin_amdgcn_rcpf(fmaxf(1.f - il.ratio, 5.9604645e-8f));
+      gu = __expf(il.ds_up - il.big) * r;
+      gl = -__expf(il.ds_lo - il.big) * r;
     }
-    float gu, gl;
-    log_interval_grad(up, lo, inv, &gu, &gl);
     float dz = mlp_backward<K, W>(prm, v + 0.5f, g * gu, dprm) + mlp_backward<K, W>(prm, v - 0.5f, g * gl, dprm);
     dz = fmaf(g, direct, dz);
     if (yin) {
@@ -382,7 +398,11 @@ int fb_forward(const char* who, const void* y, const void* noise, void* y_hat, i
                float* bits, void* stream) {
   using namespace tfc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (units == 0 || elems == 0) return 0;
+  if (units == 0) return 0;
+  if (elems == 0) {                                 // an empty coding unit sums to 0 bits
+    TFC_HIP(hipMemsetAsync(bits, 0, sizeof(float) * units, st));
+    return 0;
+  }
   BitsParams p{};
   p.y = y; p.noise = noise; p.y_hat = y_hat; p.units = units; p.elems = elems;
   p.channels = static_cast<int>(channels); p.params = params; p.log_prob = log_prob; p.tail_mass = tail_mass;
