@@ -33,15 +33,9 @@
 
 #include "../../include/tfc_hip.h"
 #include "common.h"
+#include "mfma_types.h"
 
 namespace tfc {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
 struct GdnParams {
   const void* x;
@@ -137,8 +131,6 @@ __device__ inline float gdn_dx(float xv, float r, float a, float relu_floor, flo
   return xv > relu_floor ? d : 0.f;
 }
 
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
 // v_cvt_pk_bf16_f32: two floats -> packed bf16 pair, round-to-nearest-even.
 __device__ inline unsigned int pack_bf16(float lo, float hi) {
   return __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{lo, hi}, bf16x2));

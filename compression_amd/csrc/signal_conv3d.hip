@@ -18,34 +18,10 @@
 #include <type_traits>
 #include <vector>
 
-#include "../../include/tfc_hip.h"
-#include "common.h"
+#include "conv_shared.h"
 
 namespace tfc {
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-// float32 on the bfloat16 matrix cores, as the 2-D layers run it (signal_conv.hip, conv_split_x_kernel): a = a1 + a2 + a3
-// with a_i bfloat16, and a b = a1 b1 + a1 b2 + a2 b1 + a1 b3 + a2 b2 + a3 b1 to float32 rounding noise: one bfloat16
-// convolution over six times the input channels, x planes [x1 | x1 | x1 | x2 | x2 | x3] against w planes
-// [w1 | w2 | w3 | w1 | w2 | w1], float32 out.
-__device__ inline void split3(float a, __bf16* p1, __bf16* p2, __bf16* p3) {
-  const __bf16 a1 = static_cast<__bf16>(a);
-  const float r1 = a - static_cast<float>(a1);
-  const __bf16 a2 = static_cast<__bf16>(r1);
-  const float r2 = r1 - static_cast<float>(a2);
-  *p1 = a1; *p2 = a2; *p3 = static_cast<__bf16>(r2);
-}
-__device__ inline int x_plane(int q) { return q < 3 ? 0 : q < 5 ? 1 : 2; }
-__device__ inline int w_plane(int q) { return q == 0 || q == 3 || q == 5 ? 0 : q == 1 || q == 4 ? 1 : 2; }
-__device__ inline float split_plane(float a, int plane) {
-  __bf16 p[3];
-  split3(a, &p[0], &p[1], &p[2]);
-  return static_cast<float>(plane == 0 ? p[0] : plane == 1 ? p[1] : p[2]);
-}
 
 constexpr int kThreads = 256;
 constexpr int kTile = 128;                     // output samples per workgroup (4 waves x 32)

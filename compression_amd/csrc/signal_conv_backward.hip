@@ -16,19 +16,11 @@
 // one zero-padded 32-row tile, element-wise staging).  bf16: v_mfma_f32_32x32x16_bf16; f32:
 // v_mfma_f32_32x32x2_f32 (exact products, fp32 accumulation either way).
 // Roofline: MFMA-bound, 2 * taps * M * a * b FLOP — the forward pass's count.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 
-#include "../../include/tfc_hip.h"
-#include "common.h"
+#include "conv_shared.h"
 
 namespace tfc {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
 constexpr int WG_PIX = 64;       // pixels per LDS stage
 constexpr int WG_STRIDE = 72;    // bf16 elements per transposed LDS row (144 B: conflict-free b128 reads)
@@ -42,26 +34,14 @@ struct WgradGeom {
   int kh, kw, stride;
   int chunks;            // workgroups per tap
   float* partial;        // [kh*kw][chunks][CA][CB]
-  unsigned int wb_mul, wb_sh, hb_mul, hb_sh;      // n / WB, n / HB as multiplications (wg_fast_div)
+  unsigned int wb_mul, wb_sh, hb_mul, hb_sh;      // n / WB, n / HB as multiplications (fast_div)
   int tr;                // bf16, both tensors wide, < 2^31 pixels: row-major stages + ds_read_b64_tr_b16 (below)
 };
 
-// n / d for 0 <= n < 2^31 as a multiplication (signal_conv.hip fast_div): mul = ceil(2^(31 + s) / d), s = ceil(log2 d)
-inline void wg_fast_div_setup(unsigned int d, unsigned int* mul, unsigned int* sh) {
-  if (d <= 1) { *mul = 0; *sh = 0; return; }
-  unsigned int s = 0;
-  while ((1ull << s) < d) ++s;
-  *mul = static_cast<unsigned int>(((1ull << (31 + s)) + d - 1) / d);
-  *sh = s - 1;
-}
-__device__ inline unsigned int wg_fast_div(unsigned int n, unsigned int mul, unsigned int sh) {
-  return mul ? __umulhi(n, mul) >> sh : n;
-}
 // Row stride (elements) of a row-major bf16 stage in LDS whose rows ds_read_b64_tr_b16 reads without bank conflicts:
 // stride in dwords = 16 mod 32 (gdn_backward.hip pg_row_elems).
 template <int C>
 constexpr int wg_row_elems() { return C + 2 * (((16 - (C / 2) % 32) + 32) % 32); }
-typedef __attribute__((ext_vector_type(2))) unsigned int wg_u32x2;
 
 // KTA / KTB = 32-channel tiles of A / B (1 with CA <= 4 = narrow tensor)
 template <typename T, int KTA, int KTB, bool TRB = false>
@@ -113,9 +93,9 @@ __global__ void __launch_bounds__(256) conv_wgrad_kernel(WgradGeom g) {
       long long n;
       if (small) {          // (< 2^31 pixels: the divisions as multiplications — a 64-bit division is ~150 instructions)
         const unsigned int m32 = static_cast<unsigned int>(m);
-        const unsigned int r1 = wg_fast_div(m32, g.wb_mul, g.wb_sh);
+        const unsigned int r1 = fast_div(m32, g.wb_mul, g.wb_sh);
         qx = static_cast<int>(m32 - r1 * static_cast<unsigned int>(g.WB));
-        const unsigned int n1 = wg_fast_div(r1, g.hb_mul, g.hb_sh);
+        const unsigned int n1 = fast_div(r1, g.hb_mul, g.hb_sh);
         qy = static_cast<int>(r1 - n1 * static_cast<unsigned int>(g.HB));
         n = n1;
       } else {
@@ -148,9 +128,9 @@ __global__ void __launch_bounds__(256) conv_wgrad_kernel(WgradGeom g) {
         const int cg = c % (RA / 8);
         long long ra = -1;
         if (m < M32) {
-          const unsigned int r1 = wg_fast_div(m, g.wb_mul, g.wb_sh);              // n * HB + qy
+          const unsigned int r1 = fast_div(m, g.wb_mul, g.wb_sh);              // n * HB + qy
           const int qx = static_cast<int>(m - r1 * static_cast<unsigned int>(g.WB));
-          const unsigned int n1 = wg_fast_div(r1, g.hb_mul, g.hb_sh);
+          const unsigned int n1 = fast_div(r1, g.hb_mul, g.hb_sh);
           const int qy = static_cast<int>(r1 - n1 * static_cast<unsigned int>(g.HB));
           const int iy = qy * g.stride + ty - g.kh / 2, ix = qx * g.stride + tx - g.kw / 2;
           if (iy >= 0 && iy < g.HA && ix >= 0 && ix < g.WA) ra = (static_cast<long long>(n1) * g.HA + iy) * g.WA + ix;
@@ -271,20 +251,20 @@ __global__ void __launch_bounds__(256) conv_wgrad_kernel(WgradGeom g) {
                                  static_cast<unsigned int>(((8 * (grp >> 1) + (j >> 2)) * RSA + 16 * (grp & 1) + 4 * (j & 3)) * 2);
       const unsigned int bbase = static_cast<unsigned int>(reinterpret_cast<size_t>(bsr)) +
                                  static_cast<unsigned int>(((8 * (grp >> 1) + (j >> 2)) * RSB + 16 * (grp & 1) + 4 * (j & 3)) * 2);
-      wg_u32x2 ra2[2][NHA][2], rb2[2][NHB][2];
+      u32x2 ra2[2][NHA][2], rb2[2][NHB][2];
       // (the reads of K step ks + 1 are issued in front of the MFMAs of K step ks; the compiler does not count these reads:
       // a wait per K step, tied to the registers they fill.  Plain unrolled code: a generic lambda does not capture
       // variables that only inline-asm operands name)
 #define TFC_WG_REQUEST(S, KS)                                                                                             \
       _Pragma("unroll") for (int hf = 0; hf < 2; ++hf) {                                                                  \
         _Pragma("unroll") for (int a = 0; a < NHA; ++a) {                                                                 \
-          ra2[S][a][hf] = wg_u32x2{0u, 0u};                                                                               \
+          ra2[S][a][hf] = u32x2{0u, 0u};                                                                                  \
           if (wa + 2 * a < KTA)                                                                                           \
             asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(ra2[S][a][hf])                                               \
                          : "v"(abase + static_cast<unsigned int>(((16 * (KS) + 4 * hf) * RSA) * 2) + 64u * (wa + 2 * a))); \
         }                                                                                                                 \
         _Pragma("unroll") for (int b = 0; b < NHB; ++b) {                                                                 \
-          rb2[S][b][hf] = wg_u32x2{0u, 0u};                                                                               \
+          rb2[S][b][hf] = u32x2{0u, 0u};                                                                                  \
           if (wb + 2 * b < KTB)                                                                                           \
             asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(rb2[S][b][hf])                                               \
                          : "v"(bbase + static_cast<unsigned int>(((16 * (KS) + 4 * hf) * RSB) * 2) + 64u * (wb + 2 * b))); \
@@ -402,8 +382,8 @@ int launch_wgrad(WgradGeom g, int transpose, float* dw, hipStream_t st) {
     // TFC_WGRAD_TR = 0: the transpose by hand (the round-5 staging)
     static const bool tr_on = [] { const char* e = std::getenv("TFC_WGRAD_TR"); return !(e && e[0] == '0'); }();
     g.tr = tr_on && sizeof(T) == 2 && g.CA >= 32 && g.CB >= 32 && g.N * g.HB * g.WB < (1ll << 31) ? 1 : 0;
-    wg_fast_div_setup(static_cast<unsigned int>(g.WB), &g.wb_mul, &g.wb_sh);
-    wg_fast_div_setup(static_cast<unsigned int>(g.HB), &g.hb_mul, &g.hb_sh);
+    fast_div_setup(static_cast<unsigned int>(g.WB), &g.wb_mul, &g.wb_sh);
+    fast_div_setup(static_cast<unsigned int>(g.HB), &g.hb_mul, &g.hb_sh);
     if (g.tr)
       lds = std::max(lds, sizeof(unsigned short) * WG_PIX * (wg_row_elems<KTA * 32>() + wg_row_elems<KTB * 32>()));
   }

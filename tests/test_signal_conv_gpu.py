@@ -140,11 +140,14 @@ def test_bf16_paths():
     assert (y - want).abs().max() <= 2 ** -7 * max(1.0, want.abs().max())
 
 
-@pytest.mark.parametrize("k,s,cin,cout,hw", [(5, 2, 192, 3, (13, 9)), (9, 4, 64, 3, (7, 10)), (5, 2, 32, 1, (6, 6)),
-                                             (4, 2, 48, 4, (5, 8)), (5, 3, 32, 2, (4, 7))])
+FEW_CHANNEL_CASES = [(5, 2, 192, 3, (13, 9)), (9, 4, 64, 3, (7, 10)), (5, 2, 32, 1, (6, 6)),      # k, s, cin, cout, hw
+                     (4, 2, 48, 4, (5, 8)), (5, 3, 32, 2, (4, 7))]
+
+
+@pytest.mark.parametrize("k,s,cin,cout,hw", FEW_CHANNEL_CASES)
 def test_up_into_few_channels_bf16(k, s, cin, cout, hw):
     """The last synthesis layer (C -> 3 and the like, bf16; kernels up to 5x5) runs as one 1x1 product per input
-    pixel plus a gather over the taps that land on an output pixel (signal_conv.hip, conv_up_small_cout), larger
+    pixel plus a gather over the taps that land on an output pixel (signal_conv.hip, route_up_gather), larger
     kernels as the implicit GEMM over output pixels: same result as the definition (signal_conv.py:778-847),
     with bias and with ReLU."""
     from compression_amd.layers import conv2d_up
@@ -159,10 +162,13 @@ def test_up_into_few_channels_bf16(k, s, cin, cout, hw):
         assert (y - want).abs().max() <= 2 ** -7 * max(1.0, want.abs().max())
 
 
-@pytest.mark.parametrize("case", [(5, 2, 192, 3, (40, 70)), (5, 2, 64, 3, (9, 33)), (3, 2, 32, 4, (17, 50)),
-                                  (5, 2, 192, 2, (8, 32)), (4, 2, 64, 3, (11, 37)),
-                                  # more product columns than an LDS row: a pass per kernel-row residue
-                                  (9, 4, 128, 3, (20, 40)), (9, 4, 192, 3, (9, 33)), (7, 3, 64, 4, (9, 34))])
+FUSED_UP_CASES = [(5, 2, 192, 3, (40, 70)), (5, 2, 64, 3, (9, 33)), (3, 2, 32, 4, (17, 50)),
+                  (5, 2, 192, 2, (8, 32)), (4, 2, 64, 3, (11, 37)),
+                  # more product columns than an LDS row: a pass per kernel-row residue
+                  (9, 4, 128, 3, (20, 40)), (9, 4, 192, 3, (9, 33)), (7, 3, 64, 4, (9, 34))]
+
+
+@pytest.mark.parametrize("case", FUSED_UP_CASES)
 def test_up_into_few_channels_fused_equals_unfused(case, monkeypatch):
     """conv_up_fused_kernel (tap products of a block kept in LDS; kernels with more product columns than an LDS row
     take the implicit GEMM) against the float32 definition, at the tolerance of one bf16 rounding — blocks hanging
@@ -181,8 +187,11 @@ def test_up_into_few_channels_fused_equals_unfused(case, monkeypatch):
     assert torch.equal(one, y[1:])
 
 
-@pytest.mark.parametrize("case", [(5, 2, 3, 192, (64, 96)), (5, 2, 3, 192, (37, 71)), (9, 4, 3, 128, (128, 128)),
-                                  (9, 4, 3, 128, (101, 190)), (5, 2, 1, 128, (48, 64)), (5, 2, 4, 192, (33, 50))])
+IMAGE_SIDE_CASES = [(5, 2, 3, 192, (64, 96)), (5, 2, 3, 192, (37, 71)), (9, 4, 3, 128, (128, 128)),      # k, s, cin, cout, hw
+                    (9, 4, 3, 128, (101, 190)), (5, 2, 1, 128, (48, 64)), (5, 2, 4, 192, (33, 50))]
+
+
+@pytest.mark.parametrize("case", IMAGE_SIDE_CASES)
 def test_image_side_analysis_layer_bf16(case):
     """conv_image_kernel (image patch in LDS as interleaved (x, c) rows, a kernel row = ceil(kw * Cin / 16) K steps)
     against the float32 definition — blocks over every edge, 1 / 3 / 4 input channels, both strides — and image by
@@ -387,7 +396,13 @@ def test_bf16_model_layer_shapes_against_scipy(label, shape, kshape, stride, up)
     assert np.max(np.abs(y - want) - tol * np.abs(want)) <= 0.51 * tol, label   # exact small sums, 1/2 ulp elsewhere
 
 
-@pytest.mark.parametrize("up,hw,cout", [(True, (24, 64), 192), (True, (32, 64), 128), (False, (64, 64), 192)])
+GDN_ACTIVATION_CASES = [(True, (24, 64), 192), (True, (32, 64), 128), (False, (64, 64), 192)]      # up, hw, cout
+IMAGE_GDN_CASES = [((64, 64), 3), ((96, 192), 2), ((66, 128), 1), ((64, 72), 2)]                     # hw, batch
+KEYED_CASES = [(False, (2, 32, 64, 192), (5, 5, 192, 192), 2), (True, (2, 16, 32, 192), (5, 5, 192, 3), 2),
+               (False, (1, 64, 128, 3), (5, 5, 3, 192), 2)]                                          # up, x, kernel, stride
+
+
+@pytest.mark.parametrize("up,hw,cout", GDN_ACTIVATION_CASES)
 @pytest.mark.parametrize("inverse", [False, True])
 def test_gdn_as_the_activation_is_one_kernel(up, hw, cout, inverse):
     """SignalConv2D(activation=GDN) (signal_conv.py:948-950 applying gdn.py:371-421, the way bls2017.py:61-91 builds its
@@ -425,7 +440,7 @@ def test_gdn_as_the_activation_is_one_kernel(up, hw, cout, inverse):
     assert bool((err <= tol).all()), float((err - tol).max())
 
 
-@pytest.mark.parametrize("hw,batch", [((64, 64), 3), ((96, 192), 2), ((66, 128), 1), ((64, 72), 2)])
+@pytest.mark.parametrize("hw,batch", IMAGE_GDN_CASES)
 def test_image_side_layer_applies_its_gdn_itself(hw, batch):
     """bmshj2018's / bls2017's first analysis layer, SignalConv2D(192, (5, 5), corr=True, strides_down=2, activation=GDN)
     on a three-channel image (bls2017.py:66-69): conv_image_gdn_kernel writes the normalised activations — same values
@@ -477,9 +492,8 @@ def test_keyed_weights_are_packed_once_per_value():
     torch.manual_seed(11)
     lib = _lib.lib()
     key = (1 << 40) + 12345
-    for fn, shape, kshape, stride in ((conv2d_down, (2, 32, 64, 192), (5, 5, 192, 192), 2),
-                                      (conv2d_up, (2, 16, 32, 192), (5, 5, 192, 3), 2),
-                                      (conv2d_down, (1, 64, 128, 3), (5, 5, 3, 192), 2)):
+    for up, shape, kshape, stride in KEYED_CASES:
+        fn = conv2d_up if up else conv2d_down
         x = torch.randn(shape, device="cuda").to(torch.bfloat16)
         w1 = torch.randn(kshape, device="cuda") / 30
         w2 = torch.randn(kshape, device="cuda") / 30
@@ -696,6 +710,31 @@ def test_float32_layers_on_the_bfloat16_matrix_cores(case, monkeypatch):
     for mode in got:
         assert (got[mode] - want).abs().max().item() <= 4e-6 * scale, mode
     assert (got["split"] - got["native"]).abs().max().item() <= 8e-6 * scale
+
+
+def test_float32_split_path_in_several_chunks_of_images(monkeypatch):
+    """The six-plane path takes a batch in chunks of images whose planes fit a byte budget (2 GiB; no test shape comes
+    near it).  TFC_CONV_F32_CHUNK_BYTES, read per call, sets the budget: with exactly one image's planes (h w 6 cin
+    bfloat16) the three images go through as three chunks — the loop's input and output offsets for n0 > 0, the six-plane
+    weights packed once under the call's own key.  Held to the float64 definition at the 4e-6 of the test above, and an
+    image's values must not depend on the chunk it went in: bit-equal to the same call under the default budget."""
+    from compression_amd.layers import conv2d_down
+    n, h, w, cin, cout, k, s = 3, 20, 20, 16, 40, 4, 2
+    torch.manual_seed(11)
+    x = torch.randn(n, h, w, cin)
+    ker = torch.randn(k, k, cin, cout) / np.sqrt(k * k * cin)
+    bias = torch.randn(cout)
+    want = ref_down(x.double(), ker.double(), bias.double(), s, False)
+    monkeypatch.setenv("TFC_CONV_F32", "split")
+    monkeypatch.delenv("TFC_CONV_F32_CHUNK_BYTES", raising=False)
+    whole = conv2d_down(x.cuda(), ker, bias, s).cpu()
+    monkeypatch.setenv("TFC_CONV_F32_CHUNK_BYTES", str(h * w * 6 * cin * 2))
+    chunked = conv2d_down(x.cuda(), ker, bias, s).cpu()
+    assert chunked.shape == want.shape
+    scale = max(1.0, want.abs().max().item())
+    err = (chunked.double() - want).abs().max().item()
+    assert err <= 4e-6 * scale
+    assert torch.equal(chunked, whole)
 
 
 @pytest.mark.parametrize("shape", [(5, 5, 3, 4), (4, 3, 2, 2), (9, 9, 16, 8)])

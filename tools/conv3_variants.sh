@@ -7,9 +7,9 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 D=$R/tools/probe_libs
 if [ "$1" = build ]; then
   shift; mkdir -p $D
-  OBJS=$(ls $R/build/*.o | grep -v signal_conv.hip.o)
+  OBJS=$(ls $R/build/*.o | grep -v conv_gemm3.hip.o)
   for m in "$@"; do
-    ( /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -DTFC_CONV3_EXP=$m -c $R/compression_amd/csrc/signal_conv.hip -o /tmp/sc_exp$m.o &&
+    ( /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -DTFC_CONV3_EXP=$m -c $R/compression_amd/csrc/conv_gemm3.hip -o /tmp/sc_exp$m.o &&
       /opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o $D/libtfc_conv3_exp$m.so $OBJS /tmp/sc_exp$m.o && echo built $m ) &
   done
   wait
