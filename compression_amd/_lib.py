@@ -138,6 +138,8 @@ SIGNATURES = {
     "tfc_lrelu_bias_backward": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _int, _vp]),
     "tfc_gan_loss_forward": (_int, [_vp, _int, _i64, _vp, _vp]),
     "tfc_gan_loss_backward": (_int, [_vp, _vp, _int, _i64, _int, _vp, _vp]),
+    "tfc_vecvq_assign": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, _int, _vp, _vp, _vp, _vp, _vp]),
+    "tfc_vecvq_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
 }
 
 ABI_VERSION = 2          # include/tfc_hip.h TFC_ABI_VERSION this binding was written against

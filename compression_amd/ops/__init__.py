@@ -1,4 +1,5 @@
 """Operator-level API (the reference's `python/ops`)."""
-from . import gen_ops, image_ops, math_ops, padding_ops, round_ops
+from . import gen_ops, image_ops, math_ops, padding_ops, round_ops, vq_ops
 from .gen_ops import *  # noqa: F401,F403
 from .image_ops import ssim, ssim_multiscale, ssim_multiscale_reference, ssim_reference  # noqa: F401
+from .vq_ops import ecvq_assign, ecvq_assign_reference, ecvq_counts  # noqa: F401

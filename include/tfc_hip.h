@@ -768,6 +768,34 @@ int tfc_gan_loss_forward(const void* logits, int dtype, int64_t half, float* out
 int tfc_gan_loss_backward(const void* logits, const float* scale, int dtype, int64_t half, int mode, void* grad,
                           void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Entropy-constrained vector quantisation (the toy-source VECVQ model)     */
+/* ------------------------------------------------------------------------ */
+
+/* models/toy_sources/vecvq.py:53-71 with the distortion of compression_model.py:88-95, without the [N, K] cost matrix:
+ *   dist[n, k] = s sum_d (x[n, d] - c[k, d])^2,  s = 1 (distortion 0, sse) or 1 / D (distortion 1, mse);
+ *   index[n] = argmin_k (rates[k] + lmbda dist[n, k]), ties to the LOWEST k (as tf.argmin);
+ *   rate[n] = rates[index[n]];  distortion[n] = dist[n, index[n]];  counts[k] = the number of rows with index k.
+ * x DEV f32 [N, D], codebook DEV f32 [K, D], rates DEV f32 [K]; index DEV i32 [N], rate, distortion DEV f32 [N],
+ * counts DEV i32 [K] or NULL.  The distance is always evaluated as the difference (x - c)^2.  index is in [0, K)
+ * whatever the inputs (a NaN cost never wins).  D in [1, 2^20], K in [1, 2^24], N >= 0 (N == 0 launches nothing),
+ * lmbda finite: checked on the host before anything is launched. */
+int tfc_vecvq_assign(const float* x, const float* codebook, const float* rates, int64_t n, int64_t k, int64_t d,
+                     float lmbda, int distortion, int* index, float* rate, float* dist, int* counts, void* stream);
+
+/* Gradients of tfc_vecvq_assign (models/toy_sources/vecvq.py:65-71 differentiated; compression_model.py:88-95) for
+ * g_rate = dL/drate, g_dist = dL/ddistortion, DEV f32 [N], either NULL meaning zero.  Each output is written only if
+ * its pointer is not NULL:
+ *   d_rates[k]       = sum_{n: index[n] = k} g_rate[n]
+ *   d_codebook[k, :] = 2 s sum_{n: index[n] = k} g_dist[n] (c_k - x_n)      (the difference itself is accumulated)
+ *   d_x[n, :]        = 2 s g_dist[n] (x_n - c_index[n])
+ * Codewords nobody chose get exact zeros.  Deterministic: a gather with no float atomics; every sum runs in ascending n
+ * within ranges fixed by (N, K, D), and the ranges are combined in ascending order.  A row whose index is outside
+ * [0, K) contributes nothing. */
+int tfc_vecvq_backward(const float* x, const float* codebook, const int* index, const float* g_rate,
+                       const float* g_dist, int64_t n, int64_t k, int64_t d, int distortion, float* d_rates,
+                       float* d_codebook, float* d_x, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
