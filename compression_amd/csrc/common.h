@@ -268,6 +268,9 @@ struct KernelTimer {
 };
 bool profiling_enabled();
 
+// tfc_set_chip_shared(1): the caller keeps other kernels in flight beside the coder's
+bool chip_shared();
+
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 }  // namespace tfc

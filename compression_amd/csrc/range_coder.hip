@@ -17,6 +17,12 @@
 // Behaviour follows (bit-exact, checked by tests/ against oracle/):
 //   cc/lib/range_coder.cc:37-307, cc/lib/range_coder.h:79-282,
 //   cc/kernels/range_coder_kernels.cc:101-471.
+//
+// This unit: the encoder and decoder handles and every kernel they launch (the kernel headers included below
+// stay here with them: kernels of both sides write the __device__ counters that one host function reads, and the
+// library has no relocatable device code).  The wave-per-stream device primitives are in range_wave.h, the
+// tables and their image builders in range_tables.h / range_tables.hip, the deprecated single-stream ops in
+// range_coder_legacy.hip, the library's error and timing plumbing in runtime.hip.
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
@@ -24,9 +30,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
-#include <chrono>
 #include <cstring>
-#include <functional>
 #include <type_traits>
 #include <memory>
 #include <mutex>
@@ -36,599 +40,16 @@
 #include "../../include/tfc_hip.h"
 #include "common.h"
 #include "range_coder_device.h"
-
-namespace tfc {
-
-std::string& last_error() {
-  static thread_local std::string e;
-  return e;
-}
-
-double slow_call_threshold_ms() {
-  static const double ms = [] {
-    const char* e = std::getenv("TFC_SLOW_CALL_MS");
-    return e ? std::atof(e) : 0.0;
-  }();
-  return ms;
-}
-
-namespace {
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-}  // namespace
-
-SlowCall::SlowCall(const char* w, const char* f, int l)
-    : what(w), file(f), line(l), t0(slow_call_threshold_ms() > 0.0 ? now_ms() : 0.0) {}
-
-SlowCall::~SlowCall() {
-  if (t0 == 0.0) return;
-  const double dt = now_ms() - t0;
-  if (dt >= slow_call_threshold_ms())
-    std::fprintf(stderr, "[tfc slow call] %8.2f ms  %s:%d  %s  (%llu)\n", dt, file, line, what, detail);
-}
-
-int fail(const char* fmt, ...) {
-  char buf[1024];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  last_error() = buf;
-  return 1;
-}
-
-// ---- optional kernel timing --------------------------------------------------
-namespace {
-struct ProfileEntry {
-  std::string name;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-  double total_ms = 0;
-  int64_t launches = 0;
-};
-bool g_profile_on = false;
-std::mutex g_profile_mutex;      // encoders / decoders may run on several host threads
-std::vector<ProfileEntry>& profile_table() {
-  static std::vector<ProfileEntry> t;
-  return t;
-}
-ProfileEntry& profile_entry(const char* name) {
-  for (auto& e : profile_table())
-    if (e.name == name) return e;
-  profile_table().push_back(ProfileEntry{name, {}, 0, 0});
-  return profile_table().back();
-}
-}  // namespace
-
-bool profiling_enabled() { return g_profile_on; }
-
-KernelTimer::KernelTimer(const char* n, hipStream_t s) : name(n), st(s), on(g_profile_on), slow(n, "launch scope", 0) {
-  if (!on) return;
-  (void)hipEventCreate(&a);
-  (void)hipEventCreate(&b);
-  (void)hipEventRecord(a, st);
-}
-
-KernelTimer::~KernelTimer() {
-  if (!on) return;
-  (void)hipEventRecord(b, st);
-  std::lock_guard<std::mutex> lock(g_profile_mutex);
-  profile_entry(name).pending.emplace_back(a, b);
-}
-
-}  // namespace tfc
+#include "range_tables.h"
+#include "range_wave.h"
 
 using namespace tfc;
-
-namespace {
-std::atomic<int> g_chip_shared{0};      // tfc_set_chip_shared
-}
-
-// -> the previous value, so that nested users can restore it
-extern "C" int tfc_set_chip_shared(int shared) {
-  return g_chip_shared.exchange(shared ? 1 : 0, std::memory_order_relaxed);
-}
-
-namespace {
-std::atomic<int>& default_mode() {
-  static std::atomic<int> mode{[] {
-    const char* e = std::getenv("TFC_DEFAULT_MODE");
-    if (e && !std::strcmp(e, "latency")) return TFC_MODE_LATENCY;
-    if (e && !std::strcmp(e, "throughput")) return TFC_MODE_THROUGHPUT;
-    return TFC_MODE_AUTO;
-  }()};
-  return mode;
-}
-}  // namespace
-extern "C" int tfc_set_default_mode(int mode) {
-  if (mode != TFC_MODE_AUTO && mode != TFC_MODE_LATENCY && mode != TFC_MODE_THROUGHPUT)
-    return fail("unknown mode %d", mode);
-  default_mode().store(mode);
-  return 0;
-}
-extern "C" int tfc_get_default_mode(void) { return default_mode().load(); }
-
-extern "C" int tfc_pipe_counters(int64_t* launches, int64_t* fallback_blocks);
-
-extern "C" void tfc_profile_enable(int on) {
-  std::lock_guard<std::mutex> lock(g_profile_mutex);
-  g_profile_on = on != 0;
-  if (on) {
-    for (auto& e : profile_table()) {
-      for (auto& p : e.pending) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-      e.pending.clear();
-      e.total_ms = 0;
-      e.launches = 0;
-    }
-  }
-}
-
-extern "C" int tfc_profile_query(const char* kernel, double* total_ms, int64_t* launches) {
-  std::lock_guard<std::mutex> lock(g_profile_mutex);
-  ProfileEntry& e = profile_entry(kernel);
-  for (auto& p : e.pending) {
-    float ms = 0;
-    if (hipEventSynchronize(p.second) == hipSuccess && hipEventElapsedTime(&ms, p.first, p.second) == hipSuccess) {
-      e.total_ms += ms;
-      e.launches += 1;
-    }
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
-  e.pending.clear();
-  *total_ms = e.total_ms;
-  *launches = e.launches;
-  return 0;
-}
-
-// ===========================================================================
-// Tables
-// ===========================================================================
-
-struct tfc_tables {
-  std::vector<int32_t> host;       // raw lookup
-  std::vector<int2> rows;          // (start of header, ints incl. header)
-  DevBuf d_data, d_rows;
-  DevBuf d_fast, d_rows_fast;      // encoder LDS image (uint16, entries scaled to 16-bit precision) + its rows
-  DevBuf d_dec_image, d_dec_dir;   // decoder LDS image: d_fast + pad + pivot arrays; row directory
-  int dec_words = 0;
-  bool dec_fast_ok = false;
-  // lane-per-stream kernels (range_lanes.h): one LDS image; the encoder uses its first lane_enc_bytes
-  DevBuf d_lane_image;
-  int lane_enc_bytes = 0, lane_dec_bytes = 0, lane_precision = 0;
-  bool lanes_ok = false;
-  // the pipelined decoder's COMPACT image (range_pipe.h, dec_chain_kernel<..., true>): bitmaps of every second bound at
-  // PAIR resolution (one bit per two quotient values: half the bitmaps' bytes), and per row what dec_parse_kernel adds
-  // to a raw entry to have the symbol
-  DevBuf d_pair_image, d_pair_adjust;
-  int pair_dec_bytes = 0;
-  bool pairs_ok = false;
-  int max_abs_prec = 0;
-  bool any_escape = false;
-  int64_t max_row = 0;
-};
-
-namespace {
-
-int scan_row(const std::vector<int32_t>& v, int64_t end, int64_t* cur, std::vector<int2>* rows) {
-  int64_t p = *cur;
-  if (end < p + 3) return fail("CDF ended prematurely.");
-  const int64_t head = p;
-  const int64_t ap = std::llabs(static_cast<long long>(v[head]));
-  if (ap < 1 || ap >= 17)
-    return fail("precision=%lld not in range [1, 17)", static_cast<long long>(ap));
-  const int32_t last = 1 << ap;
-  ++p;
-  if (v[p] != 0) return fail("CDF must start with 0.");
-  do {
-    ++p;
-    if (p == end) return fail("CDF must end with 1 << precision.");
-    if (v[p] < v[p - 1]) return fail("CDF must be monotonically increasing.");
-  } while (v[p] != last);
-  ++p;
-  rows->push_back(make_int2(static_cast<int>(head), static_cast<int>(p - head)));
-  while (p != end && v[p] == last) ++p;
-  *cur = p;
-  return 0;
-}
-
-}  // namespace
-
-extern "C" int tfc_abi_version(void) { return TFC_ABI_VERSION; }
-extern "C" const char* tfc_last_error(void) { return last_error().c_str(); }
-extern "C" void tfc_free(void* p) { std::free(p); }
-
-extern "C" int tfc_tables_create(const int32_t* lookup, int rank, int64_t rows, int64_t cols,
-                                 void* stream, tfc_tables** out) {
-  *out = nullptr;
-  if (rank != 1 && rank != 2) return fail("`lookup` must be rank 1 or 2: rank=%d", rank);
-  const int64_t total = rank == 1 ? cols : rows * cols;
-  if (total >= (int64_t{1} << 31)) return fail("`lookup` too large");
-  std::unique_ptr<tfc_tables> t(new tfc_tables);
-  t->host.assign(lookup, lookup + total);
-  if (rank == 1) {
-    for (int64_t cur = 0; cur != total;)
-      if (scan_row(t->host, total, &cur, &t->rows)) return 1;
-  } else {
-    for (int64_t cur = 0; cur != total;) {
-      const int64_t row_end = cur + cols;
-      if (scan_row(t->host, row_end, &cur, &t->rows)) return 1;
-      if (cur != row_end) return fail("CDF must end with 1 << precision.");
-    }
-  }
-  for (const int2& r : t->rows) {
-    const int32_t sp = t->host[r.x];
-    t->max_abs_prec = std::max(t->max_abs_prec, std::abs(sp));
-    t->any_escape |= sp < 0;
-    t->max_row = std::max<int64_t>(t->max_row, r.y);
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TFC_HIP(t->d_data.alloc(sizeof(int32_t) * std::max<int64_t>(total, 1), st));
-  TFC_HIP(t->d_rows.alloc(sizeof(int2) * std::max<size_t>(t->rows.size(), 1), st));
-  if (total)
-    TFC_HIP(hipMemcpyAsync(t->d_data.p, t->host.data(), sizeof(int32_t) * total,
-                           hipMemcpyHostToDevice, st));
-  if (!t->rows.empty())
-    TFC_HIP(hipMemcpyAsync(t->d_rows.p, t->rows.data(), sizeof(int2) * t->rows.size(),
-                           hipMemcpyHostToDevice, st));
-  {
-    std::vector<int32_t> fast(t->host);
-    for (const int2& r : t->rows) {
-      const int sh = 16 - std::abs(t->host[r.x]);
-      for (int i = 1; i < r.y; ++i) fast[r.x + i] = t->host[r.x + i] << sh;
-    }
-    // Encoder image: 16 bits per entry.  A scaled entry is at most 65536 and only ever used as
-    // "lower" (< 65536) or as "upper - 1" (the coder call word holds upper - 1), so it is stored modulo
-    // 2^16; whether a row has the escape symbol moves from the header's sign into the row directory.
-    // Half the LDS of the int32 image = twice the encoder workgroups per CU.
-    std::vector<uint16_t> fast16(std::max<int64_t>(total, 1));
-    for (int64_t i = 0; i < total; ++i) fast16[i] = static_cast<uint16_t>(fast[i]);
-    std::vector<int2> rows_fast(t->rows);
-    for (int2& r : rows_fast)
-      if (t->host[r.x] < 0) r.y |= static_cast<int>(0x80000000u);
-    TFC_HIP(t->d_fast.alloc(sizeof(uint16_t) * fast16.size(), st));
-    TFC_HIP(hipMemcpyAsync(t->d_fast.p, fast16.data(), sizeof(uint16_t) * fast16.size(), hipMemcpyHostToDevice, st));
-    TFC_HIP(t->d_rows_fast.alloc(sizeof(int2) * std::max<size_t>(rows_fast.size(), 1), st));
-    if (!rows_fast.empty())
-      TFC_HIP(hipMemcpyAsync(t->d_rows_fast.p, rows_fast.data(), sizeof(int2) * rows_fast.size(),
-                             hipMemcpyHostToDevice, st));
-    // Decoder image: the scaled table, 64 words of padding (lanes past a row's end
-    // read harmless data), then 64 pivots per wide row (> 64 symbols).
-    std::vector<int32_t> image(fast);
-    image.resize(image.size() + 64, 65536);
-    std::vector<int4> dir;
-    bool ok = true;
-    for (const int2& r : t->rows) {
-      const int nsym = r.y - 2;
-      const int cdf0 = r.x + 1;
-      const int chunk = (nsym + 63) / 64;
-      if (chunk > 64) ok = false;
-      // a zero-width FIRST symbol has the upper bound 0, whose "bound - 1" form wraps and matches every
-      // offset: such tables keep the generic decoder (64-bit comparison, range_coder.h:204-222)
-      if (nsym > 1 && fast[cdf0 + 1] == 0) ok = false;
-      int4 d;
-      d.y = cdf0;
-      d.z = nsym | (std::max(chunk, 1) << 16);
-      d.w = t->host[r.x] < 0 ? nsym - 1 : -1;
-      if (chunk <= 1) {
-        d.x = cdf0 + 1;
-      } else {
-        d.x = static_cast<int>(image.size());
-        for (int j = 0; j < 64; ++j)
-          image.push_back(fast[cdf0 + std::min((j + 1) * chunk, nsym)]);
-      }
-      dir.push_back(d);
-    }
-    image.resize(image.size() + 64, 65536);
-    t->dec_words = static_cast<int>(image.size());
-    t->dec_fast_ok = ok && !t->rows.empty();
-    TFC_HIP(t->d_dec_image.alloc(sizeof(int32_t) * image.size(), st));
-    TFC_HIP(t->d_dec_dir.alloc(sizeof(int4) * std::max<size_t>(dir.size(), 1), st));
-    TFC_HIP(hipMemcpyAsync(t->d_dec_image.p, image.data(), sizeof(int32_t) * image.size(),
-                           hipMemcpyHostToDevice, st));
-    if (!dir.empty())
-      TFC_HIP(hipMemcpyAsync(t->d_dec_dir.p, dir.data(), sizeof(int4) * dir.size(),
-                             hipMemcpyHostToDevice, st));
-    TFC_HIP(hipStreamSynchronize(st));
-  }
-  {
-    // Image of the lane-per-stream kernels: directory (one entry per table), 16-bit scaled cdf entries
-    // (modulo 2^16: only a row's last entry is 2^16), then per row the bitmap of its boundaries over
-    // [0, 2^precision) and the running count of boundaries before each 64-bit word.  The counts of a row have one
-    // more entry, for the word BEHIND the row (the next row's first, or one empty word behind the last row): the
-    // quotient estimate of an offset at the very top of the span is 2^precision, and the pipelined decoder
-    // (range_pipe.h) reads that word — of which its shift keeps bit 0 only, which it has cleared in its own copy —
-    // instead of clamping.  Rows must be strictly increasing (rank = popcount) and share one precision (the
-    // quotient scale is a kernel constant) — other tables keep the wave-per-stream kernels.
-    const size_t ntab = t->rows.size();
-    bool ok = ntab > 0;
-    const int prec = ok ? std::abs(t->host[t->rows[0].x]) : 0;
-    const size_t nw = std::max<size_t>(1, (size_t{1} << prec) / 64);
-    size_t cdf_entries = 0;
-    for (const int2& r : t->rows) {
-      const int nsym = r.y - 2;
-      if (std::abs(t->host[r.x]) != prec) ok = false;
-      if (nsym > 32767) ok = false;
-      for (int k = 1; ok && k <= nsym; ++k)
-        if (t->host[r.x + 1 + k] <= t->host[r.x + k]) ok = false;
-      cdf_entries += static_cast<size_t>(nsym + 1);
-    }
-    // behind the tables' rows: the uniform binary row {0, 1/2, 1} the pipelined decoder (range_pipe.h) decodes the
-    // bits of an escape code from (range_coder_kernels.cc:449-471: DecodeLinearly on {0, 1, 2} at precision 1)
-    cdf_entries += 3;
-    const size_t words = (ntab + 1) * nw + 1, counts = (ntab + 1) * (nw + 1);
-    // the directory repeats its first entries behind its end: a block of kEncCadence / kDecCadence steps
-    // reads that many consecutive entries without a wrap test per step
-    constexpr size_t kDirRepeat = 16;
-    // (>= kEncCadence and kDecCadence of range_lanes.h, which asserts it)
-    const size_t dir_bytes = sizeof(tfc::LaneRow) * (ntab + kDirRepeat + 1);
-    const size_t cdf_bytes = (2 * cdf_entries + 15) & ~size_t{15};
-    const size_t enc_bytes = dir_bytes + cdf_bytes;
-    const size_t dec_bytes = enc_bytes + 8 * words + ((2 * counts + 15) & ~size_t{15});
-    // (the encoder needs directory + cdf entries only; a decoder image over the CU's LDS keeps the decoder on the
-    // wave-per-stream kernels — decodes_on_lanes checks — and the encoder may still run lane-per-stream)
-    if (enc_bytes > 128 * 1024) ok = false;
-    if (ok) {
-      std::vector<uint8_t> image(dec_bytes, 0);
-      tfc::LaneRow* dir = reinterpret_cast<tfc::LaneRow*>(image.data());
-      uint16_t* cdf16 = reinterpret_cast<uint16_t*>(image.data() + dir_bytes);
-      uint64_t* bits = reinterpret_cast<uint64_t*>(image.data() + enc_bytes);
-      uint16_t* cum = reinterpret_cast<uint16_t*>(image.data() + enc_bytes + 8 * words);
-      size_t ce = 0;
-      // per word: the boundaries before it MINUS ONE, as int16 (rank - 1 = symbol: the decoder adds the
-      // popcount inside the word and has the symbol; -1 for the first word), and once more behind the row
-      auto count_row = [&](size_t i) {
-        unsigned int run = 0;
-        for (size_t w = 0; w <= nw; ++w) {
-          cum[i * (nw + 1) + w] = static_cast<uint16_t>(static_cast<int16_t>(static_cast<int>(run) - 1));
-          if (w < nw) run += static_cast<unsigned int>(__builtin_popcountll(bits[i * nw + w]));
-        }
-      };
-      auto place_row = [&](tfc::LaneRow& d, size_t i) {
-        d.cdf = static_cast<unsigned int>(dir_bytes + 2 * ce) - 2u;     // of cdf[0], minus 2: lo / hi of symbol s at + 2 s + 2 / + 4
-        d.bits = static_cast<unsigned int>(enc_bytes + 8 * i * nw);
-        d.cum = static_cast<unsigned int>(enc_bytes + 8 * words + 2 * i * (nw + 1));
-      };
-      for (size_t i = 0; i < ntab; ++i) {
-        const int2 r = t->rows[i];
-        const int32_t* cdf = &t->host[r.x + 1];
-        const int nsym = r.y - 2;
-        const bool esc = t->host[r.x] < 0;
-        tfc::LaneRow& d = dir[i];
-        place_row(d, i);
-        d.info = static_cast<unsigned int>(esc ? nsym - 1 : nsym) | (esc ? 0x80000000u : 0u);
-        for (int k = 0; k <= nsym; ++k) cdf16[ce + k] = static_cast<uint16_t>(cdf[k] << (16 - prec));
-        for (int k = 0; k < nsym; ++k) bits[i * nw + (cdf[k] >> 6)] |= uint64_t{1} << (cdf[k] & 63);
-        count_row(i);
-        ce += static_cast<size_t>(nsym + 1);
-      }
-      for (size_t i = 0; i < kDirRepeat; ++i) dir[ntab + i] = dir[i % ntab];
-      {
-        // the binary row, at the table set's precision (the quotient scale is a kernel constant); at precision 0
-        // (no such tables: precision >= 1) its two boundaries would coincide
-        tfc::LaneRow& d = dir[ntab + kDirRepeat];
-        place_row(d, ntab);
-        d.info = 2u;
-        cdf16[ce] = 0; cdf16[ce + 1] = 0x8000; cdf16[ce + 2] = 0;
-        const unsigned int mid = 1u << (prec - 1);
-        bits[ntab * nw] |= 1ull;
-        bits[ntab * nw + (mid >> 6)] |= uint64_t{1} << (mid & 63);
-        count_row(ntab);
-      }
-      TFC_HIP(t->d_lane_image.alloc(image.size(), st));
-      TFC_HIP(hipMemcpyAsync(t->d_lane_image.p, image.data(), image.size(), hipMemcpyHostToDevice, st));
-      TFC_HIP(hipStreamSynchronize(st));
-      t->lane_enc_bytes = static_cast<int>(enc_bytes);
-      t->lane_dec_bytes = static_cast<int>(dec_bytes);
-      t->lane_precision = prec;
-      t->lanes_ok = true;
-    }
-  }
-  if (t->lanes_ok && t->lane_precision <= 15) {
-    // Compact image of the pipelined decoder (round 6).  The boundary bitmaps are 2/3 of the lane image (98 of 154 KB for
-    // BASELINE config 2's tables; bls2017's 192 x 128-symbol tables need 176 KB and do not fit a CU at all): one bit per
-    // quotient value, because two bounds may be neighbours.  EVERY SECOND bound of a strictly increasing row is at least
-    // two apart from the next one marked, so a bitmap of those needs one bit per PAIR of quotient values {2 j, 2 j + 1}
-    // only — half the bytes — and its rank i says: bound k = 2 i + o is the last marked one whose pair is not behind
-    // q's, hence  cdf[k] - 1 <= q < cdf[k + 2]  and the symbol is k - 1, k or k + 1.  The step (TFC_PDEC_STEP_H) reads
-    // the four entries cdf[k - 1 .. k + 2] with one ds_read2_b32 and settles it with two comparisons of the quotient
-    // (t0 = [q >= cdf[k]], t1 = [q >= cdf[k + 1]]: lower / upper bound by four selects, symbol = k - 1 + t0 + t1) —
-    // verified by the exact interval test like every estimate.
-    //   * which bounds are marked: those with k = o (mod 2), o = symbols of the row (mod 2) — then the last marked one is
-    //     k = n - 2 and the row's END (2^16, stored as 0: the only entry a comparison must not meet) is only ever an
-    //     upper bound;
-    //   * in front of cdf[0] a row has two zero entries (an even row's first window starts at cdf[-1]; a row of one symbol
-    //     takes k = -1: both comparisons true, the window slides to (cdf[0], cdf[1])), and rows are placed so that the
-    //     window of rank i starts at a multiple of four bytes: the directory's cdf pointer is that address for i = 0;
-    //   * the step's raw entry is 2 i + t0 + t1 = symbol - (o - 1): dec_parse_kernel adds the row's o - 1 (pair_adjust).
-    // Layout: directory (final form: what dec_chain_kernel<..., false> makes of its copy of the lane image), entries,
-    // bitmaps (row i at word i * nw2, one spare word behind the last row), counts (nw2 + 1 per row).
-    const size_t ntab = t->rows.size();
-    const int prec = t->lane_precision, sh = 16 - prec;
-    const size_t npairs = size_t{1} << (prec - 1);
-    const size_t nw2 = std::max<size_t>(1, npairs / 64);
-    constexpr size_t kDirRepeat = 16;
-    const size_t dir_bytes = sizeof(tfc::LaneRow) * (ntab + kDirRepeat + 1);
-    std::vector<uint16_t> entries;            // all rows: [pad ... 0, 0, cdf[0] ... cdf[n]]
-    std::vector<int> adjust(ntab);
-    std::vector<uint64_t> bits((ntab + 1) * nw2 + 1, 0);
-    std::vector<uint16_t> cum((ntab + 1) * (nw2 + 1), 0);
-    std::vector<size_t> window0(ntab + 1);    // entry index of the window of rank 0: cdf[o - 1]
-    auto add_row = [&](size_t i, const int32_t* cdf, int nsym, unsigned int carry) {
-      // (a row of ONE symbol has no bound a comparison may meet — cdf[1] is its end: its window starts two entries in
-      // front of cdf[0], in the pad: o = -1, both comparisons true)
-      const int o = nsym == 1 ? -1 : (nsym & 1);
-      // entry index of cdf[0] such that the byte address of cdf[o - 1] (dir_bytes is a multiple of 16) is a multiple of 4
-      size_t at0 = entries.size() + 2;
-      if (((at0 + o - 1) & 1) != 0) ++at0;
-      entries.resize(at0, 0);
-      for (int k = 0; k <= nsym; ++k) entries.push_back(static_cast<uint16_t>(static_cast<unsigned int>(cdf[k]) << sh));
-      window0[i] = at0 + o - 1;
-      // (the first marked bound, k = o, is left out: the rank is then the index i of the last marked bound, and the
-      // quotients below it share its window)
-      for (int k = o + 2; k < nsym; k += 2) {
-        const unsigned int pair = static_cast<unsigned int>(cdf[k]) >> 1;
-        bits[i * nw2 + (pair >> 6)] |= uint64_t{1} << (pair & 63);
-      }
-      unsigned int run = carry;
-      for (size_t w = 0; w <= nw2; ++w) {
-        cum[i * (nw2 + 1) + w] = static_cast<uint16_t>(run);
-        if (w < nw2) run += static_cast<unsigned int>(__builtin_popcountll(bits[i * nw2 + w]));
-      }
-    };
-    for (size_t i = 0; i < ntab; ++i) {
-      const int2 r = t->rows[i];
-      const int nsym = r.y - 2;
-      adjust[i] = (nsym == 1 ? -1 : (nsym & 1)) - 1;
-      add_row(i, &t->host[r.x + 1], nsym, 0u);
-    }
-    {
-      // the binary row of an escape code's bits {0, 1/2, 1}: two symbols, bound 0 marked, window (pad, 0, 1/2, end):
-      // t0 = 1, t1 = the bit; its ranks carry 0x4000, so that 2 i + t0 + t1 = 0x8001 + bit — the raw entry of a bit row
-      // as it is stored (the bit is entry >> 1 & 1; 0xFFFF stays the mark of a row a lane sat out)
-      const int32_t bin[3] = {0, 1 << (prec - 1), 1 << prec};
-      add_row(ntab, bin, 2, 0x4000u);
-    }
-    entries.resize(entries.size() + 2, 0);    // (the last window's fourth entry)
-    const size_t cdf_bytes = (2 * entries.size() + 15) & ~size_t{15};
-    const size_t bits_off = dir_bytes + cdf_bytes;
-    const size_t cum_off = bits_off + 8 * bits.size();
-    const size_t total = cum_off + ((2 * cum.size() + 15) & ~size_t{15});
-    if (total <= 160 * 1024) {
-      std::vector<uint8_t> image(total, 0);
-      tfc::LaneRow* dir = reinterpret_cast<tfc::LaneRow*>(image.data());
-      auto entry_of = [&](size_t i, unsigned int limit, bool esc, unsigned int esclo, bool binary) {
-        tfc::LaneRow d;
-        // (the step addresses the window as cdf + 4 i; the binary row's ranks carry 0x4000)
-        d.cdf = static_cast<unsigned int>(dir_bytes + 2 * window0[i]) - (binary ? 0x10000u : 0u);
-        d.info = (limit & 0x7FFFu) | (esc ? 0x8000u : 0u) | ((0xFFFFu - esclo) << 16);
-        d.bits = static_cast<unsigned int>(bits_off + 8 * i * nw2) - 8u;
-        d.cum = static_cast<unsigned int>(cum_off + 2 * i * (nw2 + 1)) - 2u;
-        return d;
-      };
-      for (size_t i = 0; i < ntab; ++i) {
-        const int2 r = t->rows[i];
-        const bool esc = t->host[r.x] < 0;
-        const int nsym = r.y - 2;
-        // limit: plain symbols (= the escape symbol's index), as in the lane image; ESCLO: the escape symbol's lower bound
-        // on the tables' own scale (0xFFFF, which no quotient reaches at precision <= 15, for a row without one)
-        dir[i] = entry_of(i, static_cast<unsigned int>(esc ? nsym - 1 : nsym), esc,
-                          esc ? static_cast<unsigned int>(t->host[r.x + 1 + nsym - 1]) : 0xFFFFu, false);
-      }
-      for (size_t i = 0; i < kDirRepeat; ++i) dir[ntab + i] = dir[i % ntab];
-      dir[ntab + kDirRepeat] = entry_of(ntab, 2u, false, 1u << (prec - 1), true);
-      std::memcpy(image.data() + dir_bytes, entries.data(), 2 * entries.size());
-      std::memcpy(image.data() + bits_off, bits.data(), 8 * bits.size());
-      std::memcpy(image.data() + cum_off, cum.data(), 2 * cum.size());
-      TFC_HIP(t->d_pair_image.alloc(image.size(), st));
-      TFC_HIP(hipMemcpyAsync(t->d_pair_image.p, image.data(), image.size(), hipMemcpyHostToDevice, st));
-      TFC_HIP(t->d_pair_adjust.alloc(sizeof(int) * ntab, st));
-      TFC_HIP(hipMemcpyAsync(t->d_pair_adjust.p, adjust.data(), sizeof(int) * ntab, hipMemcpyHostToDevice, st));
-      TFC_HIP(hipStreamSynchronize(st));
-      t->pair_dec_bytes = static_cast<int>(total);
-      t->pairs_ok = true;
-    }
-  }
-  TFC_HIP(hipStreamSynchronize(st));
-  *out = t.release();
-  return 0;
-}
-
-extern "C" int64_t tfc_tables_count(const tfc_tables* t) { return static_cast<int64_t>(t->rows.size()); }
-extern "C" void tfc_tables_destroy(tfc_tables* t) { delete t; }
 
 // ===========================================================================
 // Kernels
 // ===========================================================================
 
 namespace tfc {
-
-constexpr int kWavesPerBlock = 4;
-constexpr int kBlock = kWavesPerBlock * 64;
-// Tables up to this many bytes are staged in LDS (160 KiB per CU on gfx950).
-constexpr size_t kLdsTableBytes = 144 * 1024;
-
-struct DecRow;
-struct TableView {
-  const int32_t* data;
-  const uint16_t* fast16;     // encoder LDS image: entries scaled to 16-bit precision, modulo 2^16
-  const int2* rows_fast;      // (offset, length | escape row << 31) per table, for that image
-  const int32_t* dec_image;   // decoder LDS image (see tfc_tables_create)
-  const struct DecRow* dec_dir;
-  int dec_words;
-  const int2* rows;
-  int ntab;
-  int total;
-};
-
-// Where symbols come from (encode) / go to (decode).
-// Loads and stores of the kernels' tensor arguments go through global-address-space pointers: the functors below travel
-// inside job arrays indexed at run time, where hipcc cannot tell that their pointers are global and emits FLAT
-// instructions — which count on lgkmcnt as well as vmcnt, so that every wait for an LDS read in the same loop becomes a
-// wait for the loop's stores too (seen in dec_parse_kernel and enc_expand_kernel, round 6).
-#ifndef TFC_AS1
-#define TFC_AS1 __attribute__((address_space(1)))
-#endif
-template <typename T>
-__device__ inline T tfc_gload(const T* p) {
-  static_assert(sizeof(T) == 2 || sizeof(T) == 4, "16- and 32-bit elements");
-  if constexpr (sizeof(T) == 2) {
-    return __builtin_bit_cast(T, *reinterpret_cast<const TFC_AS1 unsigned short*>((const TFC_AS1 void*)p));
-  } else {
-    return __builtin_bit_cast(T, *reinterpret_cast<const TFC_AS1 unsigned int*>((const TFC_AS1 void*)p));
-  }
-}
-template <typename T>
-__device__ inline void tfc_gstore(T* p, T v) {
-  static_assert(sizeof(T) == 2 || sizeof(T) == 4, "16- and 32-bit elements");
-  if constexpr (sizeof(T) == 2) {
-    *reinterpret_cast<TFC_AS1 unsigned short*>((TFC_AS1 void*)p) = __builtin_bit_cast(unsigned short, v);
-  } else {
-    *reinterpret_cast<TFC_AS1 unsigned int*>((TFC_AS1 void*)p) = __builtin_bit_cast(unsigned int, v);
-  }
-}
-
-struct SymInt32 {          // plain int32 symbols
-  const int32_t* value;
-  __device__ int32_t load(int64_t pos, int /*table*/) const { return tfc_gload(value + pos); }
-  // split form for kernels that request an element before they know its table
-  __device__ int32_t raw(int64_t pos) const { return tfc_gload(value + pos); }
-  __device__ int32_t quant(int32_t r, int /*table*/) const { return r; }
-  __device__ const int32_t* base() const { return value; }
-  using raw_type = int32_t;
-};
-
-
-template <typename T>
-__device__ inline float to_float(T v);
-template <> __device__ inline float to_float<float>(float v) { return v; }
-template <> __device__ inline float to_float<__hip_bfloat16>(__hip_bfloat16 v) { return __bfloat162float(v); }
-template <> __device__ inline float to_float<__half>(__half v) { return __half2float(v); }
-template <typename T>
-__device__ inline T from_float(float v);
-template <> __device__ inline float from_float<float>(float v) { return v; }
-template <> __device__ inline __hip_bfloat16 from_float<__hip_bfloat16>(float v) { return __float2bfloat16(v); }
-template <> __device__ inline __half from_float<__half>(float v) { return __float2half(v); }
-
-// Fused quantisation: sym = int32(rint(y - qoff[t])) - cdf_offset[t].  The
-// subtraction happens in the bottleneck dtype like the reference's
-// `bottleneck -= offset` (continuous_batched.py:375-378); rintf is
-// round-half-to-even like tf.round.
-template <typename T>
-struct SymQuant {
-  const T* y;
-  const float* qoffset;        // may be null
-  const int32_t* cdf_offset;
-  __device__ int32_t load(int64_t pos, int table) const { return quant(tfc_gload(y + pos), table); }
-  __device__ T raw(int64_t pos) const { return tfc_gload(y + pos); }
-  __device__ const T* base() const { return y; }
-  using raw_type = T;
-  __device__ int32_t quant(T r, int table) const {
-    float f = to_float<T>(r);
-    if (qoffset) f = to_float<T>(from_float<T>(f - to_float<T>(from_float<T>(tfc_gload(qoffset + table)))));
-    return static_cast<int32_t>(rintf(f)) - tfc_gload(cdf_offset + table);
-  }
-};
 
 struct EncParams {
   TableView tab;
@@ -662,91 +83,6 @@ __device__ inline bool enc_guard_skips(const EncParams& p, int64_t s, int lane) 
     if (need > p.cap_total) atomicOr(p.overflow_flag, 1u);
   }
   return true;
-}
-
-// Per-element classification shared by the counting and the coding pass.
-struct Call {
-  int32_t lo16, hi16;   // interval scaled to 16-bit precision
-  int32_t gamma;        // > 0 => escape follows
-  int32_t neg;
-  int32_t bad;          // 1: index out of range, 2: value out of range
-};
-
-template <bool NORMALISED, typename TabFn>
-__device__ inline Call classify_impl(const TabFn& T, const int2 row, int32_t v) {
-  Call c;
-  c.gamma = 0;
-  c.neg = 0;
-  c.bad = 0;
-  const int32_t sp = T(row.x);
-  const int32_t prec = sp < 0 ? -sp : sp;
-  int32_t sym = v;
-  if (sp > 0) {
-    if (v < 0 || v >= row.y - 2) {
-      c.bad = 2;
-      sym = 0;
-    }
-  } else {
-    const int32_t vmax = row.y - 3;
-    if (v < 0) {
-      c.neg = 1;
-      c.gamma = -v;
-      sym = vmax;
-    } else if (v >= vmax) {
-      c.gamma = v - vmax + 1;
-      sym = vmax;
-    }
-  }
-  const int sh = NORMALISED ? 0 : 16 - prec;
-  c.lo16 = T(row.x + 1 + sym) << sh;
-  c.hi16 = T(row.x + 2 + sym) << sh;
-  return c;
-}
-
-template <typename TabFn>
-__device__ inline Call classify(const TabFn& T, const int2 row, int32_t v) {
-  return classify_impl<false>(T, row, v);
-}
-template <typename TabFn>
-__device__ inline Call classify_normalised(const TabFn& T, const int2 row, int32_t v) {
-  return classify_impl<true>(T, row, v);
-}
-
-// The same classification on the encoder's 16-bit LDS image (tfc_tables_create): hi16 is the upper
-// bound modulo 2^16 — its only use is "upper - 1" in the call word, which is right either way.
-__device__ inline Call classify_fast(const uint16_t* tab, const int2 row, int32_t v) {
-  Call c;
-  c.gamma = 0;
-  c.neg = 0;
-  c.bad = 0;
-  const int len = row.y & 0x7FFFFFFF;
-  int32_t sym = v;
-  if (row.y >= 0) {
-    if (v < 0 || v >= len - 2) {
-      c.bad = 2;
-      sym = 0;
-    }
-  } else {
-    const int32_t vmax = len - 3;
-    if (v < 0) {
-      c.neg = 1;
-      c.gamma = -v;
-      sym = vmax;
-    } else if (v >= vmax) {
-      c.gamma = v - vmax + 1;
-      sym = vmax;
-    }
-  }
-  c.lo16 = tab[row.x + 1 + sym];
-  c.hi16 = tab[row.x + 2 + sym];
-  return c;
-}
-
-__device__ inline int escape_calls(int32_t gamma) {
-  // 1 + 2*floor(log2 gamma) bits for the Elias-gamma code, plus one sign bit
-  // (range_coder_kernels.cc:304-321).
-  const int nb = 31 - __clz(gamma);
-  return 2 * nb + 2;
 }
 
 // Counting + validation pass: fully parallel and HBM-bound (one coalesced read of the
@@ -853,75 +189,6 @@ __global__ void enc_offsets_kernel(const unsigned long long* calls, const uint4*
   if (threadIdx.x == 0) {
     off[streams] = carry;
     *total = static_cast<unsigned long long>(carry);
-  }
-}
-
-// 16-bit digit collector: 64 digits per VGPR, one coalesced store per flush.
-struct DigitSink {
-  uint8_t* dst;        // 2-byte aligned
-  unsigned int nbytes; // bytes already stored
-  unsigned int cap;
-  int n;               // digits waiting in reg
-  int reg;
-  unsigned int overflow;
-};
-
-__device__ inline void sink_flush(DigitSink& o, int lane) {
-  if (o.nbytes + 2u * o.n > o.cap) {
-    o.overflow = 1;
-  } else if (lane < o.n) {
-    const unsigned int d = static_cast<unsigned int>(o.reg);
-    const unsigned short be = static_cast<unsigned short>(((d & 0xFF) << 8) | ((d >> 8) & 0xFF));
-    reinterpret_cast<unsigned short*>(o.dst + o.nbytes)[lane] = be;
-  }
-  o.nbytes += 2u * o.n;
-  o.n = 0;
-}
-
-__device__ inline void sink_put(DigitSink& o, unsigned int digit, int lane) {
-  o.reg = tfc_writelane(static_cast<int>(digit), o.n, o.reg);
-  ++o.n;
-  if (o.n == 64) sink_flush(o, lane);
-}
-
-// One interval update on wave-uniform state; [lo16, hi16) / 2^16.
-__device__ inline void enc_update(EncoderState& st, unsigned int lo16, unsigned int hi16,
-                                  DigitSink& o, int lane) {
-  const unsigned long long span = static_cast<unsigned long long>(st.span_m1) + 1;
-  const unsigned int a = static_cast<unsigned int>((span * lo16) >> 16);
-  const unsigned int b = static_cast<unsigned int>(((span * hi16) >> 16) - 1);
-  st.base += a;
-  st.span_m1 = b - a;
-  const bool wrapped = st.base < a;
-  if (static_cast<unsigned int>(st.base + st.span_m1) < st.base) {
-    if ((st.span_m1 >> 16) == 0) {
-      st.base <<= 16;
-      st.span_m1 = (st.span_m1 << 16) | 0xFFFFu;
-      st.pend_bytes += 2;
-    }
-    return;
-  }
-  if (st.pend_digit != 0) {
-    unsigned int d = st.pend_digit;
-    unsigned int fill = 0;
-    if (!wrapped) {
-      d -= 1;
-      fill = 0xFFFFu;
-    }
-    sink_put(o, d, lane);
-    for (unsigned int k = 0; k < st.pend_bytes; k += 2) sink_put(o, fill, lane);
-    st.pend_digit = 0;
-    st.pend_bytes = 0;
-  }
-  if ((st.span_m1 >> 16) == 0) {
-    const unsigned int top = st.base >> 16;
-    st.base <<= 16;
-    st.span_m1 = (st.span_m1 << 16) | 0xFFFFu;
-    if (st.base <= static_cast<unsigned int>(st.base + st.span_m1)) {
-      sink_put(o, top, lane);
-    } else {
-      st.pend_digit = top + 1;
-    }
   }
 }
 
@@ -1206,126 +473,6 @@ struct DecParams {
   int blocks_after_escape;         // dec_fast_kernel: batches decoded as checked 8-symbol blocks after an escape
 };
 
-// 64 upcoming big-endian digits of the stream, one per lane.
-struct DigitWindow {
-  const uint8_t* src;
-  long long len;        // stream length in bytes
-  unsigned int pulls;   // digits consumed so far (including the two of the ctor)
-  unsigned int base;    // digit index held by lane 0
-  int reg;
-};
-
-__device__ inline void window_load(DigitWindow& w, int lane) {
-  const long long b = 2ll * (static_cast<long long>(w.base) + lane);
-  unsigned int hi = b < w.len ? w.src[b] : 0u;
-  unsigned int lo = b + 1 < w.len ? w.src[b + 1] : 0u;
-  w.reg = static_cast<int>((hi << 8) | lo);
-}
-
-__device__ inline unsigned int window_pull(DigitWindow& w, int lane) {
-  if (w.pulls - w.base >= 64u) {
-    w.base = w.pulls;
-    window_load(w, lane);
-  }
-  const unsigned int d = __builtin_amdgcn_readlane(w.reg, static_cast<int>(w.pulls - w.base));
-  ++w.pulls;
-  return d;
-}
-
-struct DecoderState {
-  unsigned int base, span_m1, window;
-};
-
-__device__ inline void dec_narrow(DecoderState& st, unsigned int lo, unsigned int hi, int prec,
-                                  DigitWindow& w, int lane) {
-  const unsigned long long span = static_cast<unsigned long long>(st.span_m1) + 1;
-  const unsigned int a = static_cast<unsigned int>((span * lo) >> prec);
-  const unsigned int b = static_cast<unsigned int>(((span * hi) >> prec) - 1);
-  st.base += a;
-  st.span_m1 = b - a;
-  if ((st.span_m1 >> 16) == 0) {
-    st.base <<= 16;
-    st.span_m1 = (st.span_m1 << 16) | 0xFFFFu;
-    st.window = (st.window << 16) | window_pull(w, lane);
-  }
-}
-
-// Decode one binary digit with the uniform cdf {0,1,2}, precision 1
-// (DecodeLinearly, range_coder.h:193-202 with the call at
-// range_coder_kernels.cc:449-471).
-__device__ inline int dec_bit(DecoderState& st, DigitWindow& w, int lane) {
-  const unsigned long long span = static_cast<unsigned long long>(st.span_m1) + 1;
-  const unsigned long long target =
-      (static_cast<unsigned long long>(static_cast<unsigned int>(st.window - st.base)) + 1) << 1;
-  const int bit = (target <= span) ? 0 : 1;
-  dec_narrow(st, bit, bit + 1, 1, w, lane);
-  return bit;
-}
-
-// Finds the first symbol k with target <= span * cdf[k + 1]; all 64 lanes test
-// one candidate each.  `cdf0` = position of cdf[0], `ncdf` = number of cdf
-// entries.  On damaged input (no candidate matches) the last symbol is taken.
-template <typename TabFn>
-__device__ inline int dec_symbol(const TabFn& T, DecoderState& st, int cdf0, int ncdf, int prec,
-                                 DigitWindow& w, int lane) {
-  const unsigned long long span = static_cast<unsigned long long>(st.span_m1) + 1;
-  const unsigned long long target =
-      (static_cast<unsigned long long>(static_cast<unsigned int>(st.window - st.base)) + 1) << prec;
-  const int nsym = ncdf - 1;
-  int sym = nsym - 1;
-  unsigned int lo = 0, hi = 0;
-  bool found = false;
-  for (int c0 = 0; c0 < nsym; c0 += 64) {
-    const int k = c0 + lane;
-    unsigned int lo_k = 0, hi_k = 0;
-    if (k < nsym) {
-      lo_k = static_cast<unsigned int>(T(cdf0 + k));
-      hi_k = static_cast<unsigned int>(T(cdf0 + k + 1));
-    }
-    const bool pred = (k < nsym) && (target <= span * hi_k);
-    const unsigned long long m = __ballot(pred);
-    if (m != 0) {
-      const int kk = __builtin_ctzll(m);
-      lo = __builtin_amdgcn_readlane(static_cast<int>(lo_k), kk);
-      hi = __builtin_amdgcn_readlane(static_cast<int>(hi_k), kk);
-      sym = c0 + kk;
-      found = true;
-      break;
-    }
-  }
-  if (!found) {
-    lo = static_cast<unsigned int>(T(cdf0 + nsym - 1));
-    hi = static_cast<unsigned int>(T(cdf0 + nsym));
-  }
-  dec_narrow(st, lo, hi, prec, w, lane);
-  return sym;
-}
-
-struct OutInt32 {
-  int32_t* out;
-  __device__ void store(int64_t pos, int /*table*/, int32_t sym) const { tfc_gstore(out + pos, sym); }
-  // split form for kernels that collect several elements per store
-  using elem = int32_t;
-  __device__ int32_t make(int /*table*/, int32_t sym) const { return sym; }
-  __device__ int32_t* ptr() const { return out; }
-};
-
-template <typename T>
-struct OutDequant {
-  T* y;
-  const float* qoffset;
-  const int32_t* cdf_offset;
-  __device__ void store(int64_t pos, int table, int32_t sym) const { tfc_gstore(y + pos, make(table, sym)); }
-  using elem = T;
-  __device__ T make(int table, int32_t sym) const {
-    // outputs = cast(symbols + cdf_offset, dtype) (+ quantization_offset)
-    T v = from_float<T>(static_cast<float>(sym + tfc_gload(cdf_offset + table)));
-    if (qoffset) v = from_float<T>(to_float<T>(v) + to_float<T>(from_float<T>(tfc_gload(qoffset + table))));
-    return v;
-  }
-  __device__ T* ptr() const { return y; }
-};
-
 template <bool LDS_TAB, typename Dst>
 __global__ void __launch_bounds__(kBlock) dec_kernel(DecParams p, Dst dst) {
   extern __shared__ int32_t lds_tab[];
@@ -1492,6 +639,149 @@ __global__ void fill_state_many_kernel(uint8_t* ctl, long long ctl_bytes, int64_
 }  // namespace tfc
 
 // ===========================================================================
+// Host side: environment knobs and process-wide state
+// ===========================================================================
+// Everything in this section exists once per process, behind the function that names it.
+
+namespace {
+
+// An integer knob of the environment; `fallback` where it is not set.
+int env_int(const char* name, int fallback) {
+  const char* e = std::getenv(name);
+  return e ? std::atoi(e) : fallback;
+}
+
+// Which image the pipelined decoder's chain runs on — 1 "full" (the lane-per-stream kernels' image, one bit per quotient
+// value), 2 "pairs" (the compact image, TFC_PDEC_STEP_H: half the bitmaps, ~10 % more cycles per row), 0: full where it
+// fits and its chain waves all find a CU, else pairs — and the chain waves per workgroup (0: by launch size).
+// tfc_set_pipe_format / TFC_PIPE_FORMAT, TFC_PIPE_WAVES: an A/B and test switch.
+std::atomic<int>& pipe_format_value() {
+  static std::atomic<int> v{[] {
+    const char* e = std::getenv("TFC_PIPE_FORMAT");
+    if (e && std::strcmp(e, "full") == 0) return 1;
+    if (e && std::strcmp(e, "pairs") == 0) return 2;
+    return 0;
+  }()};
+  return v;
+}
+std::atomic<int>& pipe_waves_value() {
+  static std::atomic<int> v{std::max(0, env_int("TFC_PIPE_WAVES", 0))};
+  return v;
+}
+inline int pipe_format() { return pipe_format_value().load(std::memory_order_relaxed); }
+inline int pipe_waves_env() { return pipe_waves_value().load(std::memory_order_relaxed); }
+
+// The pipelined kernels of range_pipe.h in front of the lane-per-stream kernels (TFC_PIPE=0: the latter alone —
+// an A/B switch for measurements, not a product setting).
+inline bool pipe_enabled() {
+  static const bool on = env_int("TFC_PIPE", 1) != 0;
+  return on;
+}
+// TFC_PIPE_NOFALLBACK=1 (tools/pipe_probe.py): the lane-per-stream kernel is NOT launched behind the pipelined ones, so
+// that a job they gave up on shows as wrong output instead of being covered up
+inline bool pipe_fallback_launch() {
+  static const bool on = env_int("TFC_PIPE_NOFALLBACK", 0) == 0;
+  return on;
+}
+// Launches of the pipelined kernels so far (tfc_pipe_counters)
+std::atomic<long long>& pipe_launches() {
+  static std::atomic<long long> n{0};
+  return n;
+}
+
+// TFC_PIPE_OVERLAP (default 2): how the encoder's chain kernel is launched relative to the expansion that feeds it.
+//   0  behind it, on the caller's stream (the chain starts when every call word is in memory);
+//   1  on a stream of the library's own, enqueued behind the expansion;  2  the same, enqueued in front of it.
+// On its own stream the chain consumes the call words tile by tile while the expansion is still producing them
+// (range_pipe.h: `done` flags); whichever way the two kernels end up scheduled, the result is the same — a chain
+// that went first and is not fed within TFC_PIPE_POLL_MS (default 250) gives its job to the lane-per-stream kernel.
+inline int pipe_overlap() {
+  static const int v = env_int("TFC_PIPE_OVERLAP", 2);
+  return v;
+}
+inline long long pipe_poll_ticks() {
+  static const long long v = static_cast<long long>(env_int("TFC_PIPE_POLL_MS", 250)) * 100000;     // wall_clock64(): 100 MHz
+  return v;
+}
+
+// The library's own stream next to a caller's stream (one per caller stream and device, made on first use, never
+// destroyed), with the two events that tie a launch on it into the caller's order.  It is a HIGH-priority stream
+// (unless the caller's is): HIP multiplexes the streams of one priority onto a few hardware queues and kernels that
+// share a queue run one after the other — a different priority is a different queue, and the chain is the critical
+// path of an encode call.
+struct SideStream {
+  hipStream_t stream = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr;
+};
+inline int side_stream(hipStream_t st, SideStream* out) {
+  static std::mutex mu;
+  static std::map<std::pair<int, hipStream_t>, SideStream> streams;
+  int dev = 0;
+  TFC_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(mu);
+  auto f = streams.find({dev, st});
+  if (f == streams.end()) {
+    SideStream ss;
+    int least = 0, greatest = 0, mine = 0;
+    TFC_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    if (hipStreamGetPriority(st, &mine) != hipSuccess) {
+      (void)hipGetLastError();
+      mine = least;
+    }
+    const int prio = (mine == greatest && least != greatest) ? least : greatest;
+    TFC_HIP(hipStreamCreateWithPriority(&ss.stream, hipStreamNonBlocking, prio));
+    TFC_HIP(hipEventCreateWithFlags(&ss.fork, hipEventDisableTiming));
+    TFC_HIP(hipEventCreateWithFlags(&ss.join, hipEventDisableTiming));
+    f = streams.emplace(std::make_pair(dev, st), ss).first;
+  }
+  *out = f->second;
+  return 0;
+}
+// Temporaries of one pipelined launch (call words / raw rows: ~150 / ~125 MB per 512-stream job of BASELINE config 2) are
+// bounded: more jobs than fit go out as several launches, one behind the other.  6 GB, at most an eighth of the device's
+// memory; TFC_PIPE_TEMP_MB overrides.  Measured (round 5, bench.py `saturation`, profiles/r05_notes.md): a launch takes
+// the same ~14 ms up to ~40 jobs, but more per launch does not help — with 24 GB, 64 jobs in ONE launch took 12.4 ms of
+// encode (the expansion, 0.19 ms per job, is what bounds it beyond ~20 jobs) + 31 ms of decode (512 chain waves: two per
+// CU behind one 149 KB table image, and the parse beside them finds no CU) against 12.0 + 28.6 ms as 39 + 25 jobs.
+// A launch whose temporaries cannot be allocated runs on the lane-per-stream kernels, which need none.
+// (per device ordinal: a process may drive several devices of different memory sizes)
+struct PipeDeviceInfo {
+  size_t temp_bytes = 0;
+  int cus = 0;
+};
+inline const PipeDeviceInfo& pipe_device_info() {
+  constexpr int kMaxDevices = 64;
+  static PipeDeviceInfo info[kMaxDevices];
+  static std::once_flag once[kMaxDevices];
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  dev = std::min(std::max(dev, 0), kMaxDevices - 1);
+  std::call_once(once[dev], [dev] {
+    PipeDeviceInfo& d = info[dev];
+    d.cus = 256;
+    if (hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
+      (void)hipGetLastError();
+      d.cus = 256;
+    }
+    if (std::getenv("TFC_PIPE_TEMP_MB")) {
+      d.temp_bytes = static_cast<size_t>(std::max(1, env_int("TFC_PIPE_TEMP_MB", 0))) << 20;
+      return;
+    }
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+      (void)hipGetLastError();
+      d.temp_bytes = size_t{2} << 30;
+      return;
+    }
+    d.temp_bytes = std::min<size_t>(size_t{6} << 30, total_b / 8);
+  });
+  return info[dev];
+}
+inline size_t pipe_temp_bytes() { return pipe_device_info().temp_bytes; }
+
+}  // namespace
+
+// ===========================================================================
 // Host side: encoder
 // ===========================================================================
 
@@ -1546,27 +836,6 @@ struct tfc_encoder {
 
 namespace {
 
-size_t table_lds_bytes(const tfc_tables* t) {
-  const size_t b = t->host.size() * sizeof(int32_t);
-  return b <= kLdsTableBytes ? b : 0;
-}
-
-TableView view_of(const tfc_tables* t) {
-  TableView v;
-  v.data = t->d_data.as<int32_t>();
-  v.fast16 = t->d_fast.as<uint16_t>();
-  v.rows_fast = t->d_rows_fast.as<int2>();
-  v.dec_image = t->d_dec_image.as<int32_t>();
-  v.dec_dir = t->d_dec_dir.as<DecRow>();
-  v.dec_words = t->dec_words;
-  v.rows = t->d_rows.as<int2>();
-  v.ntab = static_cast<int>(t->rows.size());
-  v.total = static_cast<int>(t->host.size());
-  return v;
-}
-
-inline size_t lds_request(size_t need) { return need; }
-
 // Waves (= code streams) of a workgroup of the wave-per-stream kernels, sharing one LDS copy of the tables: one wave
 // per SIMD of a CU whenever there are that many streams.  Fewer, fuller workgroups: a CU that hosts even one coder wave
 // is lost to a convolution workgroup — which wants all four SIMDs' registers — for as long as that wave runs, so with
@@ -1577,7 +846,7 @@ inline int64_t waves_wanted(int64_t streams) {
   // waves per SIMD, i.e. 64 instead of 128 CUs under a bls2017 batch (C1: 12.0 -> 11.1 ms per step with 8 steps in
   // flight; a lone 512-stream call is 1.4x slower that way, 6.5 -> 8.8 ms, hence not the default); for 128 streams the
   // same packing costs more than it frees (profiles/r03_notes.md)
-  const bool shared = g_chip_shared.load(std::memory_order_relaxed) != 0;
+  const bool shared = chip_shared();
   const int64_t limit = shared && streams >= 512 ? 8 : 4;
   return std::min<int64_t>(limit, std::max<int64_t>(1, streams));
 }
@@ -1597,7 +866,7 @@ int select_family(const tfc_tables* t, int mode, int64_t streams, int64_t elems,
   if (mode == TFC_MODE_AUTO && lanes_ok && streams >= 4096) return kLanes;
   // tfc_set_chip_shared(1): a batch of 256 streams and more goes to the lane kernels where they fit — a wave per 64
   // streams on a handful of CUs instead of a wave per stream on 64-128 CUs that the convolutions then cannot use
-  if (mode == TFC_MODE_AUTO && lanes_ok && streams >= 256 && g_chip_shared.load(std::memory_order_relaxed) != 0)
+  if (mode == TFC_MODE_AUTO && lanes_ok && streams >= 256 && chip_shared())
     return kLanes;
   return fast_ok ? kFast : kGeneric;
 }
@@ -1676,146 +945,6 @@ int encoder_error(tfc_encoder* e, const unsigned long long* host_status) {
   return range_error_text(e->tables, e->indexed_last, static_cast<int32_t>(static_cast<long long>(host_status[2])),
                           ch, static_cast<int32_t>(static_cast<long long>(host_status[1])));
 }
-
-// Which image the pipelined decoder's chain runs on — 1 "full" (the lane-per-stream kernels' image, one bit per quotient
-// value), 2 "pairs" (the compact image, TFC_PDEC_STEP_H: half the bitmaps, ~10 % more cycles per row), 0: full where it
-// fits and its chain waves all find a CU, else pairs — and the chain waves per workgroup (0: by launch size).
-// tfc_set_pipe_format / TFC_PIPE_FORMAT, TFC_PIPE_WAVES: an A/B and test switch.
-std::atomic<int>& pipe_format_value() {
-  static std::atomic<int> v{[] {
-    const char* e = std::getenv("TFC_PIPE_FORMAT");
-    if (!e) return 0;
-    if (std::strcmp(e, "full") == 0) return 1;
-    if (std::strcmp(e, "pairs") == 0) return 2;
-    return 0;
-  }()};
-  return v;
-}
-std::atomic<int>& pipe_waves_value() {
-  static std::atomic<int> v{[] {
-    const char* e = std::getenv("TFC_PIPE_WAVES");
-    return e ? std::max(0, std::atoi(e)) : 0;
-  }()};
-  return v;
-}
-inline int pipe_format() { return pipe_format_value().load(std::memory_order_relaxed); }
-inline int pipe_waves_env() { return pipe_waves_value().load(std::memory_order_relaxed); }
-
-// The pipelined kernels of range_pipe.h in front of the lane-per-stream kernels (TFC_PIPE=0: the latter alone —
-// an A/B switch for measurements, not a product setting).
-inline bool pipe_enabled() {
-  static const bool on = [] {
-    const char* e = std::getenv("TFC_PIPE");
-    return !e || std::atoi(e) != 0;
-  }();
-  return on;
-}
-// TFC_PIPE_NOFALLBACK=1 (tools/pipe_probe.py): the lane-per-stream kernel is NOT launched behind the pipelined ones, so
-// that a job they gave up on shows as wrong output instead of being covered up
-inline bool pipe_fallback_launch() {
-  static const bool on = [] {
-    const char* e = std::getenv("TFC_PIPE_NOFALLBACK");
-    return !e || std::atoi(e) == 0;
-  }();
-  return on;
-}
-std::atomic<long long> g_pipe_launches{0};
-
-// TFC_PIPE_OVERLAP (default 2): how the encoder's chain kernel is launched relative to the expansion that feeds it.
-//   0  behind it, on the caller's stream (the chain starts when every call word is in memory);
-//   1  on a stream of the library's own, enqueued behind the expansion;  2  the same, enqueued in front of it.
-// On its own stream the chain consumes the call words tile by tile while the expansion is still producing them
-// (range_pipe.h: `done` flags); whichever way the two kernels end up scheduled, the result is the same — a chain
-// that went first and is not fed within TFC_PIPE_POLL_MS (default 250) gives its job to the lane-per-stream kernel.
-inline int pipe_overlap() {
-  static const int v = [] {
-    const char* e = std::getenv("TFC_PIPE_OVERLAP");
-    return e ? std::atoi(e) : 2;
-  }();
-  return v;
-}
-inline long long pipe_poll_ticks() {
-  static const long long v = [] {
-    const char* e = std::getenv("TFC_PIPE_POLL_MS");
-    return static_cast<long long>(e ? std::atoi(e) : 250) * 100000;     // wall_clock64(): 100 MHz
-  }();
-  return v;
-}
-
-// The library's own stream next to a caller's stream (one per caller stream and device, made on first use, never
-// destroyed), with the two events that tie a launch on it into the caller's order.  It is a HIGH-priority stream
-// (unless the caller's is): HIP multiplexes the streams of one priority onto a few hardware queues and kernels that
-// share a queue run one after the other — a different priority is a different queue, and the chain is the critical
-// path of an encode call.
-struct SideStream {
-  hipStream_t stream = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr;
-};
-inline int side_stream(hipStream_t st, SideStream* out) {
-  static std::mutex mu;
-  static std::map<std::pair<int, hipStream_t>, SideStream> streams;
-  int dev = 0;
-  TFC_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(mu);
-  auto f = streams.find({dev, st});
-  if (f == streams.end()) {
-    SideStream ss;
-    int least = 0, greatest = 0, mine = 0;
-    TFC_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    if (hipStreamGetPriority(st, &mine) != hipSuccess) {
-      (void)hipGetLastError();
-      mine = least;
-    }
-    const int prio = (mine == greatest && least != greatest) ? least : greatest;
-    TFC_HIP(hipStreamCreateWithPriority(&ss.stream, hipStreamNonBlocking, prio));
-    TFC_HIP(hipEventCreateWithFlags(&ss.fork, hipEventDisableTiming));
-    TFC_HIP(hipEventCreateWithFlags(&ss.join, hipEventDisableTiming));
-    f = streams.emplace(std::make_pair(dev, st), ss).first;
-  }
-  *out = f->second;
-  return 0;
-}
-// Temporaries of one pipelined launch (call words / raw rows: ~150 / ~125 MB per 512-stream job of BASELINE config 2) are
-// bounded: more jobs than fit go out as several launches, one behind the other.  6 GB, at most an eighth of the device's
-// memory; TFC_PIPE_TEMP_MB overrides.  Measured (round 5, bench.py `saturation`, profiles/r05_notes.md): a launch takes
-// the same ~14 ms up to ~40 jobs, but more per launch does not help — with 24 GB, 64 jobs in ONE launch took 12.4 ms of
-// encode (the expansion, 0.19 ms per job, is what bounds it beyond ~20 jobs) + 31 ms of decode (512 chain waves: two per
-// CU behind one 149 KB table image, and the parse beside them finds no CU) against 12.0 + 28.6 ms as 39 + 25 jobs.
-// A launch whose temporaries cannot be allocated runs on the lane-per-stream kernels, which need none.
-// (per device ordinal: a process may drive several devices of different memory sizes)
-struct PipeDeviceInfo {
-  size_t temp_bytes = 0;
-  int cus = 0;
-};
-inline const PipeDeviceInfo& pipe_device_info() {
-  constexpr int kMaxDevices = 64;
-  static PipeDeviceInfo info[kMaxDevices];
-  static std::once_flag once[kMaxDevices];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  dev = std::min(std::max(dev, 0), kMaxDevices - 1);
-  std::call_once(once[dev], [dev] {
-    PipeDeviceInfo& d = info[dev];
-    d.cus = 256;
-    if (hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
-      (void)hipGetLastError();
-      d.cus = 256;
-    }
-    if (const char* e = std::getenv("TFC_PIPE_TEMP_MB")) {
-      d.temp_bytes = static_cast<size_t>(std::max(1, std::atoi(e))) << 20;
-      return;
-    }
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-      (void)hipGetLastError();
-      d.temp_bytes = size_t{2} << 30;
-      return;
-    }
-    d.temp_bytes = std::min<size_t>(size_t{6} << 30, total_b / 8);
-  });
-  return info[dev];
-}
-inline size_t pipe_temp_bytes() { return pipe_device_info().temp_bytes; }
 
 // Lane-per-stream family: n handles (same tables, same stream count) coded by one launch per
 // kMaxLaneJobs of them; no counting pass, no read-back unless a handle wants its range errors now.
@@ -1932,7 +1061,7 @@ int encode_lanes_many(tfc_encoder* const* es, int n, const Src* srcs, const int3
         pa.fallback = reinterpret_cast<unsigned int*>(base + calls_bytes + stage_bytes + status_bytes + done_bytes);
         pa.started = pa.fallback + 64;          // (behind the 64 jobs' flags)
         pa.groups = static_cast<int>(groups);
-        g_pipe_launches.fetch_add(1, std::memory_order_relaxed);
+        pipe_launches().fetch_add(1, std::memory_order_relaxed);
         pa.fast16 = t->d_fast.as<uint16_t>();
         pa.rows_fast = t->d_rows_fast.as<int2>();
         pa.ntab = la.ntab;
@@ -2045,10 +1174,9 @@ size_t speculative_slab_bytes(const tfc_tables* t, int64_t streams, int64_t elem
   bytes += 64u << 10;
   // test hook (tests/test_pipeline_gpu.py): TFC_SPECULATIVE_SLAB_DIV=n shrinks the slab so that the
   // "outgrown" path can be exercised with ordinary data
-  if (const char* e = std::getenv("TFC_SPECULATIVE_SLAB_DIV")) {
-    const long n = std::strtol(e, nullptr, 10);
-    if (n > 1) bytes = std::max<size_t>(bytes / static_cast<size_t>(n), 256);
-  }
+  // (read at every call: the test sets it around its own calls)
+  const int n = env_int("TFC_SPECULATIVE_SLAB_DIV", 0);
+  if (n > 1) bytes = std::max<size_t>(bytes / static_cast<size_t>(n), 256);
   return bytes;
 }
 
@@ -2245,10 +1373,10 @@ int run_encode(tfc_encoder* e, const int32_t* index, int64_t elems, const Src& s
     KernelTimer timer("enc_kernel", st);
     TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&enc_fast_kernel<Src>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                static_cast<int>(lds_request(e->fast_lds))));
+                                static_cast<int>(e->fast_lds)));
     hipLaunchKernelGGL((enc_fast_kernel<Src>),
                        dim3(static_cast<unsigned>(ceil_div(e->streams, e->fast_waves))),
-                       dim3(64 * e->fast_waves), lds_request(e->fast_lds), st, p, src);
+                       dim3(64 * e->fast_waves), e->fast_lds, st, p, src);
   } else {
     KernelTimer timer("enc_kernel", st);
     if (lds) {
@@ -2463,7 +1591,7 @@ extern "C" int tfc_debug_enc_clocks(unsigned long long* out4) {
 }
 
 extern "C" int tfc_pipe_counters(int64_t* launches, int64_t* fallback_blocks) {
-  if (launches) *launches = g_pipe_launches.load();
+  if (launches) *launches = pipe_launches().load();
   if (fallback_blocks) {
     unsigned long long v = 0;
     TFC_HIP(hipDeviceSynchronize());
@@ -2839,12 +1967,6 @@ extern "C" int tfc_decoder_set_mode(tfc_decoder* d, int mode) {
 
 namespace {
 
-// LDS bytes of dec_fast_kernel (decoder image + row directory), or 0 where the tables cannot take that kernel.
-size_t dec_fast_lds(const tfc_tables* t) {
-  const size_t b = sizeof(int32_t) * ((t->dec_words + 3) & ~3) + sizeof(int4) * t->rows.size();
-  return t->dec_fast_ok && b <= 160 * 1024 ? b : 0;
-}
-
 // One wave per stream (dec_fast_kernel where the tables qualify, else dec_kernel) for ONE handle; `job_guard` (or null): a
 // device flag without which the launch does nothing.
 template <typename Dst>
@@ -2870,10 +1992,10 @@ int launch_wave_decoder(tfc_decoder* d, const int32_t* index, int64_t elems, con
     const int waves = static_cast<int>(waves_wanted(d->streams));
     TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_fast_kernel<Dst>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                static_cast<int>(lds_request(fast_lds))));
+                                static_cast<int>(fast_lds)));
     hipLaunchKernelGGL((dec_fast_kernel<Dst>),
                        dim3(static_cast<unsigned>(ceil_div(d->streams, waves))), dim3(64 * waves),
-                       lds_request(fast_lds), st, p, dst);
+                       fast_lds, st, p, dst);
   } else if (lds) {
     TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_kernel<true, Dst>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
@@ -2958,7 +2080,7 @@ int decode_lanes_many(tfc_decoder* const* ds, int n, const Dst* dsts, const int3
   // waves per workgroup: as few as host the call on the chip's CUs (a chain wave wants a SIMD to itself); under
   // tfc_set_chip_shared — other kernels beside the coder's — four, so that the chains hold few CUs' LDS
   int per = static_cast<int>(std::min<int64_t>(8, std::max<int64_t>(1, ceil_div(waves_call, static_cast<int64_t>(cus_d)))));
-  if (g_chip_shared.load(std::memory_order_relaxed) != 0) per = std::max(per, static_cast<int>(std::min<int64_t>(4, pa.groups_per_job)));
+  if (chip_shared()) per = std::max(per, static_cast<int>(std::min<int64_t>(4, pa.groups_per_job)));
   if (pipe_waves_env() > 0) per = pipe_waves_env();
   per = std::min(per, std::min(fit, pa.groups_per_job));
   const int pblock = 64 * std::max(per, 0);
@@ -3039,7 +2161,7 @@ int decode_lanes_many(tfc_decoder* const* ds, int n, const Dst* dsts, const int3
       pa.poll_ticks = 200000;         // 2 ms: the chain releases rows every ~0.2 ms
       // (kend of a group the chain gave up on stays unset: the parse skips the whole job under its fallback flag)
       TFC_HIP(hipMemsetAsync(pa.fallback, 0, flags_all, st));
-      g_pipe_launches.fetch_add(1, std::memory_order_relaxed);
+      pipe_launches().fetch_add(1, std::memory_order_relaxed);
       PipeDecJobs cj;
       cj.streams = streams;
       cj.elems = elems;
@@ -3299,590 +2421,3 @@ extern "C" int tfc_decoder_finalize(tfc_decoder* d, uint8_t* ok, void* stream) {
 }
 
 extern "C" void tfc_decoder_destroy(tfc_decoder* d) { delete d; }
-
-// ===========================================================================
-// Deprecated single-stream ops: RangeEncode / RangeDecode
-// (cc/kernels/range_coding_kernels.cc:60-379, range_coding_kernels_util.cc:34-91)
-// ===========================================================================
-
-namespace tfc {
-
-// Merged broadcast geometry: data index -> cdf row offset.
-struct Broadcast {
-  int nd;
-  long long shape[6];       // merged data shape
-  long long cdf_stride[6];  // cdf elements per step along the axis (0 when broadcast)
-  long long width;          // cdf entries per row
-};
-
-__device__ inline long long cdf_row_of(const Broadcast& b, long long k) {
-  long long off = 0;
-  for (int i = b.nd - 1; i >= 0; --i) {
-    const long long q = k / b.shape[i];
-    off += (k - q * b.shape[i]) * b.cdf_stride[i];
-    k = q;
-  }
-  return off;
-}
-
-// RangeEncoder::Finalize (cc/lib/range_coder.cc:266-307) behind the digits already stored:
-// returns the stream length.  One lane.
-__device__ inline unsigned int finalize_bytes(const EncoderState& st, const DigitSink& o, uint8_t* out) {
-  unsigned int n = o.nbytes;
-  uint8_t* dst = out + n;
-  if (st.pend_digit != 0) {
-    dst[0] = (st.pend_digit >> 8) & 0xFF; ++n;
-    if ((st.pend_digit & 0xFF) != 0) { dst[1] = st.pend_digit & 0xFF; ++n; }
-  } else if (st.base != 0) {
-    const unsigned int top = st.base + st.span_m1;
-    const unsigned int r24 = ((st.base - 1) >> 24) + 1;
-    if (r24 <= (top >> 24)) {
-      dst[0] = r24 & 0xFF; ++n;
-    } else {
-      const unsigned int r16 = ((st.base - 1) >> 16) + 1;
-      dst[0] = (r16 >> 8) & 0xFF; ++n;
-      if ((r16 & 0xFF) != 0) { dst[1] = r16 & 0xFF; ++n; }
-    }
-  }
-  return n;
-}
-
-struct LegacyEncParams {
-  const int16_t* data;
-  const int32_t* cdf;
-  Broadcast geo;
-  long long total;
-  int precision;
-  int check;                         // debug_level > 0
-  uint8_t* out;
-  unsigned int cap;
-  unsigned int* out_len;
-  unsigned long long* first_error;
-};
-
-__global__ void __launch_bounds__(64) legacy_enc_kernel(LegacyEncParams p) {
-  const int lane = threadIdx.x;
-  EncoderState st{0u, 0xFFFFFFFFu, 0u, 0u};
-  DigitSink o;
-  o.dst = p.out;
-  o.cap = p.cap;
-  o.nbytes = 0;
-  o.n = 0;
-  o.reg = 0;
-  o.overflow = 0;
-  const int sh = 16 - p.precision;
-  bool failed = false;
-  for (long long k0 = 0; k0 < p.total && !failed; k0 += 64) {
-    const long long k = k0 + lane;
-    int lo = 0, hi = 0;
-    bool bad = false;
-    if (k < p.total) {
-      const long long row = cdf_row_of(p.geo, k);
-      long long v = p.data[k];
-      if (v < 0 || p.geo.width <= v + 1) {
-        bad = true;
-        v = 0;
-      }
-      lo = p.cdf[row + v] << sh;
-      hi = p.cdf[row + v + 1] << sh;
-    }
-    const unsigned long long badmask = __ballot(bad);
-    int cnt = static_cast<int>(min<long long>(64, p.total - k0));
-    if (badmask != 0) {
-      // debug_level 1 reports the first offender; debug_level 0 leaves it
-      // undefined in the reference (DCHECK only) — we stop there too.
-      const int first = __builtin_ctzll(badmask);
-      if (lane == 0) atomicMin(p.first_error, static_cast<unsigned long long>(k0 + first));
-      cnt = first;
-      failed = true;
-    }
-    for (int n = 0; n < cnt; ++n) {
-      const unsigned int l = __builtin_amdgcn_readlane(lo, n);
-      const unsigned int h = __builtin_amdgcn_readlane(hi, n);
-      enc_update(st, l, h, o, lane);
-    }
-  }
-  sink_flush(o, lane);
-  if (lane == 0) *p.out_len = finalize_bytes(st, o, p.out);
-}
-
-struct LegacyDecParams {
-  const uint8_t* bytes;
-  long long nbytes;
-  const int32_t* cdf;
-  Broadcast geo;
-  long long total;
-  int precision;
-  int16_t* out;
-};
-
-__global__ void __launch_bounds__(64) legacy_dec_kernel(LegacyDecParams p) {
-  const int lane = threadIdx.x;
-  DecoderState st{0u, 0xFFFFFFFFu, 0u};
-  DigitWindow w;
-  w.src = p.bytes;
-  w.len = p.nbytes;
-  w.pulls = 0;
-  w.base = 0;
-  window_load(w, lane);
-  st.window = window_pull(w, lane) << 16;
-  st.window |= window_pull(w, lane);
-  for (long long k0 = 0; k0 < p.total; k0 += 64) {
-    const long long k = k0 + lane;
-    long long row = 0;
-    if (k < p.total) row = cdf_row_of(p.geo, k);
-    const int cnt = static_cast<int>(min<long long>(64, p.total - k0));
-    int outv = 0;
-    for (int n = 0; n < cnt; ++n) {
-      const unsigned int rlo = __builtin_amdgcn_readlane(static_cast<int>(row & 0xFFFFFFFFll), n);
-      const unsigned int rhi = __builtin_amdgcn_readlane(static_cast<int>(row >> 32), n);
-      const long long r = (static_cast<long long>(rhi) << 32) | rlo;
-      const int32_t* base = p.cdf + r;
-      auto T = [&](int i) -> int32_t { return base[i]; };
-      const int sym = dec_symbol(T, st, 0, static_cast<int>(p.geo.width), p.precision, w, lane);
-      outv = tfc_writelane(sym, n, outv);
-    }
-    if (k < p.total) p.out[k] = static_cast<int16_t>(outv);
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Deprecated UnboundedIndexRangeEncode / Decode
-// (cc/kernels/unbounded_index_range_coding_kernels.cc:185-249, 307-367): ONE stream for the
-// whole tensor, so one wave; the per-element table work (row, clamping, overflow value, the
-// two cdf entries) is done 64 elements at a time across the lanes, the interval updates
-// are the serial part.  Out-of-range values: the row's last symbol, then the digit count
-// (unary in units of the largest digit) and the digits of the overflow value, least
-// significant first, each a uniform `overflow_width`-bit symbol.
-// ---------------------------------------------------------------------------
-struct UnboundedParams {
-  const int32_t* data;        // encode
-  int32_t* out_values;        // decode
-  const int32_t* index;
-  const int32_t* cdf;
-  const int32_t* cdf_size;
-  const int32_t* offset;
-  long long total, rows, width;
-  int precision, overflow_width;
-  uint8_t* out;               // encode
-  unsigned int cap;
-  unsigned int* out_len;
-  const uint8_t* bytes;       // decode
-  long long nbytes;
-};
-
-__global__ void __launch_bounds__(64) unbounded_enc_kernel(UnboundedParams p) {
-  const int lane = threadIdx.x;
-  EncoderState st{0u, 0xFFFFFFFFu, 0u, 0u};
-  DigitSink o;
-  o.dst = p.out; o.cap = p.cap; o.nbytes = 0; o.n = 0; o.reg = 0; o.overflow = 0;
-  const int sh = 16 - p.precision, osh = 16 - p.overflow_width;
-  const unsigned int max_overflow = (1u << p.overflow_width) - 1u;
-  for (long long k0 = 0; k0 < p.total; k0 += 64) {
-    const long long k = k0 + lane;
-    int lo = 0, hi = 0, clamped = 0;
-    unsigned int ovf = 0;
-    if (k < p.total) {
-      const long long row = min<long long>(max(p.index[k], 0), p.rows - 1);   // debug_level 0: DCHECK only
-      const int max_value = p.cdf_size[row] - 2;
-      int value = p.data[k] - p.offset[row];
-      if (value < 0) {
-        ovf = static_cast<unsigned int>(-2 * value - 1);
-        value = max_value;
-      } else if (value >= max_value) {
-        ovf = static_cast<unsigned int>(2 * (value - max_value));
-        value = max_value;
-      }
-      clamped = value == max_value;
-      lo = p.cdf[row * p.width + value] << sh;
-      hi = p.cdf[row * p.width + value + 1] << sh;
-    }
-    const int cnt = static_cast<int>(min<long long>(64, p.total - k0));
-    for (int n = 0; n < cnt; ++n) {
-      enc_update(st, __builtin_amdgcn_readlane(lo, n), __builtin_amdgcn_readlane(hi, n), o, lane);
-      if (__builtin_amdgcn_readlane(clamped, n)) {
-        const unsigned int v = __builtin_amdgcn_readlane(static_cast<int>(ovf), n);
-        int widths = 0;
-        while (widths * p.overflow_width < 32 && (v >> (widths * p.overflow_width)) != 0) ++widths;
-        unsigned int val = static_cast<unsigned int>(widths);
-        while (val >= max_overflow) {
-          enc_update(st, max_overflow << osh, (max_overflow + 1u) << osh, o, lane);
-          val -= max_overflow;
-        }
-        enc_update(st, val << osh, (val + 1u) << osh, o, lane);
-        for (int j = 0; j < widths; ++j) {
-          const unsigned int d = (v >> (j * p.overflow_width)) & max_overflow;
-          enc_update(st, d << osh, (d + 1u) << osh, o, lane);
-        }
-      }
-    }
-  }
-  sink_flush(o, lane);
-  if (lane == 0) *p.out_len = o.overflow ? 0xFFFFFFFFu : finalize_bytes(st, o, p.out);
-}
-
-// One uniform symbol of `width` bits: cdf = 0, 1, ..., 2^width at precision `width`; the
-// reference's search (first k with target <= span * k) in closed form.
-__device__ inline unsigned int dec_uniform(DecoderState& st, int width, DigitWindow& w, int lane) {
-  const unsigned long long span = static_cast<unsigned long long>(st.span_m1) + 1;
-  const unsigned long long target =
-      (static_cast<unsigned long long>(static_cast<unsigned int>(st.window - st.base)) + 1) << width;
-  unsigned long long sym = (target - 1) / span;
-  const unsigned long long last = (1ull << width) - 1;
-  if (sym > last) sym = last;                      // damaged input
-  dec_narrow(st, static_cast<unsigned int>(sym), static_cast<unsigned int>(sym) + 1u, width, w, lane);
-  return static_cast<unsigned int>(sym);
-}
-
-__global__ void __launch_bounds__(64) unbounded_dec_kernel(UnboundedParams p) {
-  const int lane = threadIdx.x;
-  DecoderState st{0u, 0xFFFFFFFFu, 0u};
-  DigitWindow w;
-  w.src = p.bytes; w.len = p.nbytes; w.pulls = 0; w.base = 0;
-  window_load(w, lane);
-  st.window = window_pull(w, lane) << 16;
-  st.window |= window_pull(w, lane);
-  const unsigned int max_overflow = (1u << p.overflow_width) - 1u;
-  for (long long k0 = 0; k0 < p.total; k0 += 64) {
-    const long long k = k0 + lane;
-    long long row = 0;
-    int ncdf = 3, off = 0;
-    if (k < p.total) {
-      row = min<long long>(max(p.index[k], 0), p.rows - 1);
-      ncdf = p.cdf_size[row];
-      off = p.offset[row];
-    }
-    const int cnt = static_cast<int>(min<long long>(64, p.total - k0));
-    int outv = 0;
-    for (int n = 0; n < cnt; ++n) {
-      const long long r = __builtin_amdgcn_readlane(static_cast<int>(row), n);
-      const int nc = __builtin_amdgcn_readlane(ncdf, n);
-      const int32_t* base = p.cdf + r * p.width;
-      auto T = [&](int i) -> int32_t { return base[i]; };
-      int value = dec_symbol(T, st, 0, nc, p.precision, w, lane);
-      const int max_value = nc - 2;
-      if (value == max_value) {
-        int widths = 0;
-        unsigned int val;
-        do {
-          val = dec_uniform(st, p.overflow_width, w, lane);
-          widths += static_cast<int>(val);
-        } while (val == max_overflow && widths < 64);
-        unsigned int ovf = 0;
-        for (int j = 0; j < widths; ++j) {
-          const unsigned int d = dec_uniform(st, p.overflow_width, w, lane);
-          if (j * p.overflow_width < 32) ovf |= d << (j * p.overflow_width);
-        }
-        value = static_cast<int>(ovf >> 1);
-        if (ovf & 1u) value = -value - 1; else value += max_value;
-      }
-      outv = tfc_writelane(value, n, outv);
-    }
-    if (k < p.total) p.out_values[k] = outv + off;
-  }
-}
-
-// CheckArgumentValues (unbounded_index_range_coding_kernels.cc:54-113): first offending
-// index position / cdf_size row / cdf row (min), bit 0 ends wrong, bit 1 not monotonic.
-__global__ void unbounded_check_kernel(const int32_t* index, long long total, const int32_t* cdf,
-                                       long long rows, long long width, const int32_t* cdf_size,
-                                       int precision, unsigned long long* first) {
-  const long long i = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x;
-  if (i < total && (index[i] < 0 || rows <= index[i])) atomicMin(first, static_cast<unsigned long long>(i));
-  if (i < rows) {
-    const int n = cdf_size[i];
-    if (n < 3 || width < n) {
-      atomicMin(first + 1, static_cast<unsigned long long>(i));
-    } else {
-      const int32_t* s = cdf + i * width;
-      if (s[0] != 0 || s[n - 1] != (1 << precision)) atomicMin(first + 2, static_cast<unsigned long long>(i));
-      for (int j = 0; j + 1 < n; ++j)
-        if (s[j + 1] <= s[j]) { atomicMin(first + 3, static_cast<unsigned long long>(i)); break; }
-    }
-  }
-}
-
-// cdf[..., 0] == 0, cdf[..., -1] == 1 << precision, strictly increasing
-// (CheckCdfValues, range_coding_kernels.cc:149-173).  flag: bit0 ends wrong,
-// bit1 not monotonic; bad_row = first offending row (min).
-__global__ void check_cdf_kernel(const int32_t* cdf, long long rows, long long width,
-                                 int precision, unsigned int* flag, unsigned long long* bad_row) {
-  const long long r = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x;
-  if (r >= rows) return;
-  const int32_t* s = cdf + r * width;
-  if (s[0] != 0 || s[width - 1] != (1 << precision)) {
-    atomicOr(flag, 1u);
-    atomicMin(bad_row, static_cast<unsigned long long>(r));
-  }
-  for (long long j = 0; j + 1 < width; ++j)
-    if (s[j + 1] <= s[j]) { atomicOr(flag, 2u); break; }
-}
-
-}  // namespace tfc
-
-namespace {
-
-std::string shape_str(const int64_t* s, int n) {
-  std::string r = "[";
-  for (int i = 0; i < n; ++i) r += (i ? "," : "") + std::to_string(s[i]);
-  return r + "]";
-}
-
-// MergeAxes (range_coding_kernels_util.cc:34-91) + the stride table the
-// kernels use instead of BroadcastRange's incremental displacement.
-int make_broadcast(const int64_t* data_shape, int nd, const int64_t* cdf_shape, int nc,
-                   Broadcast* out) {
-  if (nc != nd + 1)
-    return fail("`cdf` should have one more axis than `data`: data shape=%s, cdf shape=%s",
-                shape_str(data_shape, nd).c_str(), shape_str(cdf_shape, nc).c_str());
-  if (cdf_shape[nc - 1] <= 1)
-    return fail("The last dimension of `cdf` should be > 1: %s", shape_str(cdf_shape, nc).c_str());
-  std::vector<int64_t> md(1, 1), mc(1, 1);
-  for (int j = 0; j < nd; ++j) {
-    if (data_shape[j] != cdf_shape[j] && cdf_shape[j] != 1)
-      return fail("Cannot broadcast shape %s to %s", shape_str(cdf_shape, nc).c_str(),
-                  shape_str(data_shape, nd).c_str());
-    const bool was_b = mc.back() == 1;
-    const bool is_b = cdf_shape[j] == 1;
-    if (was_b == is_b || data_shape[j] <= 1 || md.back() <= 1) {
-      md.back() *= data_shape[j];
-      mc.back() *= cdf_shape[j];
-    } else {
-      md.push_back(data_shape[j]);
-      mc.push_back(cdf_shape[j]);
-    }
-  }
-  if (md.size() > 6)
-    return fail("Irregular broadcast pattern: %s, %s", shape_str(data_shape, nd).c_str(),
-                shape_str(cdf_shape, nc).c_str());
-  out->nd = static_cast<int>(md.size());
-  out->width = cdf_shape[nc - 1];
-  long long stride = out->width;
-  for (int i = out->nd - 1; i >= 0; --i) {
-    out->shape[i] = md[i];
-    out->cdf_stride[i] = mc[i] <= 1 ? 0 : stride;
-    stride *= mc[i];
-  }
-  return 0;
-}
-
-int check_cdf_values(const int32_t* cdf, const int64_t* cdf_shape, int nc, int precision,
-                     hipStream_t st) {
-  const long long width = cdf_shape[nc - 1];
-  if (width <= 2) return fail("CDF size should be > 2: %lld", width);
-  long long rows = 1;
-  for (int i = 0; i + 1 < nc; ++i) rows *= cdf_shape[i];
-  if (rows == 0) return 0;
-  DevBuf flag;
-  TFC_HIP(flag.alloc(16, st));
-  const unsigned long long init[2] = {0ull, ~0ull};
-  TFC_HIP(hipMemcpyAsync(flag.p, init, 16, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(check_cdf_kernel, dim3(static_cast<unsigned>(ceil_div(rows, 256))), dim3(256),
-                     0, st, cdf, rows, width, precision, flag.as<unsigned int>(),
-                     flag.as<unsigned long long>() + 1);
-  unsigned long long h[2];
-  TFC_HIP(hipMemcpyAsync(h, flag.p, 16, hipMemcpyDeviceToHost, st));
-  TFC_HIP(hipStreamSynchronize(st));
-  const unsigned int f = static_cast<unsigned int>(h[0] & 0xFFFFFFFFu);
-  if (f & 1u) {
-    int32_t ends[2] = {0, 0};
-    (void)hipMemcpy(&ends[0], cdf + h[1] * width, 4, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(&ends[1], cdf + h[1] * width + width - 1, 4, hipMemcpyDeviceToHost);
-    return fail("CDF should start from 0 and end at %d: cdf[0]=%d, cdf[^1]=%d", 1 << precision,
-                ends[0], ends[1]);
-  }
-  if (f & 2u) return fail("CDF is not monotonic");
-  return 0;
-}
-
-}  // namespace
-
-extern "C" int tfc_range_encode(const int16_t* data, const int64_t* data_shape, int nd,
-                                const int32_t* cdf, const int64_t* cdf_shape, int nc,
-                                int precision, int debug_level, void* stream, uint8_t** out,
-                                int64_t* out_len) {
-  *out = nullptr;
-  *out_len = 0;
-  if (!(0 < precision && precision <= 16)) return fail("`precision` must be in [1, 16]: %d", precision);
-  if (debug_level != 0 && debug_level != 1) return fail("`debug_level` must be 0 or 1: %d", debug_level);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  Broadcast geo;
-  if (nc != nd + 1 || cdf_shape[nc - 1] <= 1) return make_broadcast(data_shape, nd, cdf_shape, nc, &geo);
-  if (debug_level > 0 && check_cdf_values(cdf, cdf_shape, nc, precision, st)) return 1;
-  if (make_broadcast(data_shape, nd, cdf_shape, nc, &geo)) return 1;
-  long long total = 1;
-  for (int i = 0; i < nd; ++i) total *= data_shape[i];
-  if (2 * total + 16 >= (1ll << 32)) return fail("`data` too large for a single code stream");
-  DevBuf buf, meta;
-  const unsigned int cap = static_cast<unsigned int>(2 * total + 16);
-  TFC_HIP(buf.alloc(cap, st));
-  TFC_HIP(meta.alloc(16, st));
-  const unsigned long long init[2] = {~0ull, 0ull};
-  TFC_HIP(hipMemcpyAsync(meta.p, init, 16, hipMemcpyHostToDevice, st));
-  LegacyEncParams p;
-  p.data = data;
-  p.cdf = cdf;
-  p.geo = geo;
-  p.total = total;
-  p.precision = precision;
-  p.check = debug_level;
-  p.out = buf.as<uint8_t>();
-  p.cap = cap - 4;
-  p.first_error = meta.as<unsigned long long>();
-  p.out_len = reinterpret_cast<unsigned int*>(meta.as<unsigned long long>() + 1);
-  hipLaunchKernelGGL(legacy_enc_kernel, dim3(1), dim3(64), 0, st, p);
-  TFC_HIP(hipGetLastError());
-  unsigned long long h[2];
-  TFC_HIP(hipMemcpyAsync(h, meta.p, 16, hipMemcpyDeviceToHost, st));
-  TFC_HIP(hipStreamSynchronize(st));
-  if (h[0] != ~0ull) {
-    int16_t v = 0;
-    (void)hipMemcpy(&v, data + h[0], 2, hipMemcpyDeviceToHost);
-    return fail("'data' value not in [0, %lld): value=%d", static_cast<long long>(geo.width - 1), v);
-  }
-  const unsigned int n = static_cast<unsigned int>(h[1] & 0xFFFFFFFFu);
-  uint8_t* host = static_cast<uint8_t*>(std::malloc(n ? n : 1));
-  if (n) TFC_HIP(hipMemcpy(host, buf.p, n, hipMemcpyDeviceToHost));
-  *out = host;
-  *out_len = n;
-  return 0;
-}
-
-extern "C" int tfc_range_decode(const uint8_t* encoded, int64_t encoded_len,
-                                const int64_t* out_shape, int nd, const int32_t* cdf,
-                                const int64_t* cdf_shape, int nc, int precision, int debug_level,
-                                void* stream, int16_t* out) {
-  if (!(0 < precision && precision <= 16)) return fail("`precision` must be in [1, 16]: %d", precision);
-  if (debug_level != 0 && debug_level != 1) return fail("`debug_level` must be 0 or 1: %d", debug_level);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  Broadcast geo;
-  if (nc != nd + 1 || cdf_shape[nc - 1] <= 1) return make_broadcast(out_shape, nd, cdf_shape, nc, &geo);
-  if (debug_level > 0 && check_cdf_values(cdf, cdf_shape, nc, precision, st)) return 1;
-  if (make_broadcast(out_shape, nd, cdf_shape, nc, &geo)) return 1;
-  long long total = 1;
-  for (int i = 0; i < nd; ++i) total *= out_shape[i];
-  if (total == 0) return 0;
-  DevBuf bytes;
-  TFC_HIP(bytes.alloc(static_cast<size_t>(encoded_len), st));
-  if (encoded_len)
-    TFC_HIP(hipMemcpyAsync(bytes.p, encoded, static_cast<size_t>(encoded_len), hipMemcpyHostToDevice, st));
-  LegacyDecParams p;
-  p.bytes = bytes.as<uint8_t>();
-  p.nbytes = encoded_len;
-  p.cdf = cdf;
-  p.geo = geo;
-  p.total = total;
-  p.precision = precision;
-  p.out = out;
-  hipLaunchKernelGGL(legacy_dec_kernel, dim3(1), dim3(64), 0, st, p);
-  TFC_HIP(hipGetLastError());
-  TFC_HIP(hipStreamSynchronize(st));  // `encoded` is a host buffer the caller may free
-  return 0;
-}
-
-// ===========================================================================
-// Deprecated UnboundedIndexRangeEncode / Decode
-// ===========================================================================
-
-namespace {
-
-int unbounded_validate(const char* who, const int32_t* index, int64_t total, const int32_t* cdf, int64_t rows,
-                       int64_t width, const int32_t* cdf_size, int precision, int overflow_width,
-                       int debug_level, hipStream_t st) {
-  if (!(0 < precision && precision <= 16)) return fail("`precision` must be in [1, 16]: %d", precision);
-  if (!(0 < overflow_width && overflow_width <= 16))
-    return fail("`overflow_width` must be in [1, 16]: %d", overflow_width);
-  if (debug_level != 0 && debug_level != 1) return fail("`debug_level` must be 0 or 1: %d", debug_level);
-  if (width < 3) return fail("'cdf' should be 2-D and cdf.dim_size(1) >= 3: [%lld,%lld]",
-                             static_cast<long long>(rows), static_cast<long long>(width));
-  if (rows < 1) return fail("%s: 'cdf' has no rows", who);
-  if (debug_level == 0) return 0;
-  DevBuf first;
-  TFC_HIP(first.alloc(4 * sizeof(unsigned long long), st));
-  TFC_HIP(hipMemsetAsync(first.p, 0xFF, 4 * sizeof(unsigned long long), st));
-  const long long n = std::max<long long>(total, rows);
-  hipLaunchKernelGGL(unbounded_check_kernel, dim3(static_cast<unsigned>(ceil_div(n, 256))), dim3(256), 0, st,
-                     index, total, cdf, rows, width, cdf_size, precision, first.as<unsigned long long>());
-  unsigned long long h[4];
-  TFC_HIP(hipMemcpyAsync(h, first.p, sizeof(h), hipMemcpyDeviceToHost, st));
-  TFC_HIP(hipStreamSynchronize(st));
-  if (h[0] != ~0ull) {
-    int32_t v = 0;
-    (void)hipMemcpy(&v, index + h[0], 4, hipMemcpyDeviceToHost);
-    return fail("'index' has a value not in [0, %lld): value=%d", static_cast<long long>(rows), v);
-  }
-  if (h[1] != ~0ull) {
-    int32_t v = 0;
-    (void)hipMemcpy(&v, cdf_size + h[1], 4, hipMemcpyDeviceToHost);
-    return fail("'cdf_size' has a value not in [3, %lld]: value=%d", static_cast<long long>(width), v);
-  }
-  if (h[2] != ~0ull) {
-    int32_t n0 = 0, ends[2] = {0, 0};
-    (void)hipMemcpy(&n0, cdf_size + h[2], 4, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(&ends[0], cdf + h[2] * width, 4, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(&ends[1], cdf + h[2] * width + n0 - 1, 4, hipMemcpyDeviceToHost);
-    return fail("Each cdf should start from 0 and end at %d: cdf[0]=%d, cdf[^1]=%d", 1 << precision, ends[0],
-                ends[1]);
-  }
-  if (h[3] != ~0ull) return fail("CDF is not monotonic");
-  return 0;
-}
-
-}  // namespace
-
-extern "C" int tfc_unbounded_index_range_encode(const int32_t* data, const int32_t* index, int64_t total,
-                                                const int32_t* cdf, int64_t rows, int64_t width,
-                                                const int32_t* cdf_size, const int32_t* offset, int precision,
-                                                int overflow_width, int debug_level, void* stream,
-                                                uint8_t** out, int64_t* out_len) {
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  *out = nullptr;
-  *out_len = 0;
-  if (int rc = unbounded_validate("tfc_unbounded_index_range_encode", index, total, cdf, rows, width, cdf_size,
-                                  precision, overflow_width, debug_level, st))
-    return rc;
-  // worst case per element: the symbol, ceil(32 / w) digits and their count in unary — 2 bytes per call
-  const long long digits = (32 + overflow_width - 1) / overflow_width;
-  const unsigned long long cap64 = 2ull * total * (2 + 2 * digits) + 16;
-  if (cap64 >= (1ull << 32)) return fail("tfc_unbounded_index_range_encode: tensor too large for one stream");
-  DevBuf buf, len;
-  TFC_HIP(buf.alloc(cap64, st));
-  TFC_HIP(len.alloc(sizeof(unsigned int), st));
-  UnboundedParams p{};
-  p.data = data; p.index = index; p.cdf = cdf; p.cdf_size = cdf_size; p.offset = offset;
-  p.total = total; p.rows = rows; p.width = width; p.precision = precision; p.overflow_width = overflow_width;
-  p.out = buf.as<uint8_t>(); p.cap = static_cast<unsigned int>(cap64 - 8); p.out_len = len.as<unsigned int>();
-  hipLaunchKernelGGL(unbounded_enc_kernel, dim3(1), dim3(64), 0, st, p);
-  unsigned int n = 0;
-  TFC_HIP(hipMemcpyAsync(&n, len.p, sizeof(n), hipMemcpyDeviceToHost, st));
-  TFC_HIP(hipStreamSynchronize(st));
-  if (n == 0xFFFFFFFFu) return fail("internal error: unbounded encoder ran out of output space");
-  uint8_t* host = static_cast<uint8_t*>(std::malloc(std::max<size_t>(n, 1)));
-  if (!host) return fail("out of host memory");
-  if (n) TFC_HIP(hipMemcpy(host, buf.p, n, hipMemcpyDeviceToHost));
-  *out = host;
-  *out_len = n;
-  return 0;
-}
-
-extern "C" int tfc_unbounded_index_range_decode(const uint8_t* encoded, int64_t encoded_len, const int32_t* index,
-                                                int64_t total, const int32_t* cdf, int64_t rows, int64_t width,
-                                                const int32_t* cdf_size, const int32_t* offset, int precision,
-                                                int overflow_width, int debug_level, int32_t* out, void* stream) {
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (int rc = unbounded_validate("tfc_unbounded_index_range_decode", index, total, cdf, rows, width, cdf_size,
-                                  precision, overflow_width, debug_level, st))
-    return rc;
-  if (total == 0) return 0;
-  DevBuf bytes;
-  TFC_HIP(bytes.alloc(static_cast<size_t>(encoded_len), st));
-  if (encoded_len) TFC_HIP(hipMemcpyAsync(bytes.p, encoded, static_cast<size_t>(encoded_len), hipMemcpyHostToDevice, st));
-  UnboundedParams p{};
-  p.out_values = out; p.index = index; p.cdf = cdf; p.cdf_size = cdf_size; p.offset = offset;
-  p.total = total; p.rows = rows; p.width = width; p.precision = precision; p.overflow_width = overflow_width;
-  p.bytes = bytes.as<uint8_t>(); p.nbytes = encoded_len;
-  hipLaunchKernelGGL(unbounded_dec_kernel, dim3(1), dim3(64), 0, st, p);
-  TFC_HIP(hipGetLastError());
-  TFC_HIP(hipStreamSynchronize(st));      // the host copy of `encoded` may go away
-  return 0;
-}

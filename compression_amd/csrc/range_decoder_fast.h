@@ -23,13 +23,6 @@
 
 namespace tfc {
 
-// Row directory entry of the decoder's LDS image (built on the host).
-//   x: index of the first stage-1 upper bound (narrow: cdf0 + 1, wide: pivot array)
-//   y: index of cdf[0]
-//   z: nsym | chunk << 16   (chunk = symbols per pivot; 1 for narrow rows)
-//   w: escape symbol index (nsym - 1) if the row has negative precision, else -1
-struct DecRow { int x, y, z, w; };
-
 // span - 1 is kept unnormalised-aware: after a renormalisation span = (t + 1) << 16 exactly, so
 // the next bound (span * hi) >> 16 is just t * hi + hi with NO shift.  Keeping t and the shift
 // amount (instead of the shifted value) takes the compare + select that would build

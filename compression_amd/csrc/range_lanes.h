@@ -254,8 +254,6 @@ __host__ __device__ constexpr int lane_stride(int payload) {
 // Encoder
 // ---------------------------------------------------------------------------------------------
 
-constexpr unsigned int kLaneDirRepeat = 16;     // directory entries repeated behind its end (tfc_tables_create, kDirRepeat)
-constexpr unsigned int kEncCadence = 16;        // steps between memory phases (= steps of the hand-scheduled block)
 constexpr unsigned int kEncDigitBytes = 32;     // digit bytes staged per lane between two phases (<= 2 digits per step)
 
 // LDS of one encoder wave: per lane digits, value window (2 cadences of elements), index window
@@ -798,9 +796,6 @@ __global__ void __launch_bounds__(512) enc_lanes_kernel(const EncLaneJobs<Src> j
 // ---------------------------------------------------------------------------------------------
 // Decoder
 // ---------------------------------------------------------------------------------------------
-
-constexpr unsigned int kDecCadence = 16;
-static_assert(kEncCadence <= kLaneDirRepeat && kDecCadence <= kLaneDirRepeat, "a block reads cadence consecutive directory entries");
 
 // LDS of one decoder wave: per lane the code-byte window (a step consumes <= 2 bytes), the decoded
 // elements of one cadence, and the index window.

@@ -1436,7 +1436,7 @@ __global__ void __launch_bounds__(512) dec_chain_kernel(const PipeDecJobs jobs, 
     //    tables' own scale (0xFFFF, which no quotient reaches at precision <= 15, for a row without one; 2^(p-1) for the
     //    binary row behind the repeated entries: there q >= ESCLO is the decoded bit); bits - 8 and cum - 2 (the step
     //    addresses a word from the NEGATED quotient).
-    const unsigned int entries = static_cast<unsigned int>(la.ntab) + kLaneDirRepeat + 1u;
+    const unsigned int entries = static_cast<unsigned int>(la.ntab) + kDirRepeat + 1u;
     const unsigned int nw = max(1u, (1u << la.precision) >> 6) + 1u;      // counts of a row: its words and the word behind it
     for (unsigned int i = threadIdx.x; i < entries; i += blockDim.x) {
       if (i >= static_cast<unsigned int>(la.ntab) && i + 1u != entries) continue;     // (repeated entries: tables patched already)
@@ -1524,7 +1524,7 @@ __global__ void __launch_bounds__(512) dec_chain_kernel(const PipeDecJobs jobs, 
   const unsigned int pair_nsh = 0u - (1u << pair_sh);
   const unsigned int dir_end = 16u * static_cast<unsigned int>(la.ntab);
   // the built-in binary row: directory entry behind the repeated ones
-  const unsigned int bin_addr = dir_end + 16u * kLaneDirRepeat;
+  const unsigned int bin_addr = dir_end + 16u * kDirRepeat;
   uint4 bin = *reinterpret_cast<const uint4*>(lanes_lds + bin_addr);
   asm volatile("" : "+v"(bin.x), "+v"(bin.y), "+v"(bin.z), "+v"(bin.w));
   unsigned int bin_addr_v = bin_addr;     // (in vector registers: v_cndmask takes one scalar operand, and that is vcc)

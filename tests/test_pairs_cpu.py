@@ -1,4 +1,4 @@
-"""The pipelined decoder's COMPACT table image (csrc/range_coder.hip tfc_tables_create "Compact image"; csrc/range_pipe.h
+"""The pipelined decoder's COMPACT table image (csrc/range_tables.hip tfc_tables_create "Compact image"; csrc/range_pipe.h
 TFC_PDEC_STEP_H), restated in numpy and checked exhaustively.  The bitmap marks every SECOND bound of a row (k = o mod 2,
 o = symbols mod 2; a one-symbol row: o = -1) at PAIR resolution; for EVERY quotient q the rank i among the marked bounds
 whose pair is not behind q's names a window of four entries cdf[k - 1 .. k + 2], k = 2 i + o, and two comparisons of the

@@ -1,4 +1,4 @@
-"""GPU tier: the pipelined decoder on the COMPACT table image (round 6; csrc/range_coder.hip tfc_tables_create "Compact
+"""GPU tier: the pipelined decoder on the COMPACT table image (round 6; csrc/range_tables.hip tfc_tables_create "Compact
 image", csrc/range_pipe.h TFC_PDEC_STEP_H: every second bound of a row at pair resolution — half the bitmaps — and a
 three-way choice among four entries per step; tests/test_pairs_cpu.py holds its arithmetic).  Decoded symbols must equal
 the oracle's (cc/kernels/range_coder_kernels.cc:360-471, cc/lib/range_coder.h:193-282) whichever image the chain runs on:
