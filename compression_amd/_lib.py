@@ -140,6 +140,10 @@ SIGNATURES = {
     "tfc_gan_loss_backward": (_int, [_vp, _vp, _int, _i64, _int, _vp, _vp]),
     "tfc_vecvq_assign": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, _int, _vp, _vp, _vp, _vp, _vp]),
     "tfc_vecvq_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
+    "tfc_y4m_unpack": (_int, [_vp, _i64, _i64, _i64, _i64, _int, _i64, _i64, _vp, _vp, _vp]),
+    "tfc_y4m_pack": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _i64, _i64, _vp]),
+    "tfc_ycbcr_to_rgb": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _vp]),
+    "tfc_rgb_to_ycbcr": (_int, [_vp, _int, _vp, _vp, _i64, _i64, _i64, _int, _int, _int, _vp]),
 }
 
 ABI_VERSION = 2          # include/tfc_hip.h TFC_ABI_VERSION this binding was written against

@@ -796,6 +796,49 @@ int tfc_vecvq_backward(const float* x, const float* codebook, const int* index, 
                        const float* g_dist, int64_t n, int64_t k, int64_t d, int distortion, float* d_rates,
                        float* d_codebook, float* d_x, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* YUV4MPEG2 frames and YCbCr <-> RGB (python/datasets/y4m_dataset.py)      */
+/* ------------------------------------------------------------------------ */
+
+/* The de-interleaving of cc/kernels/y4m_dataset_kernels.cc:165-178 (one frame, one byte at a time, on the host) for
+ * num_frames frames at once.  raw DEV u8 [raw_bytes]: frame n's planes Y [height, width], U and V [h, w] lie back to
+ * back from byte first_offset + n frame_stride; chroma is 420 (h = height / 2, w = width / 2) or 444 (h = height,
+ * w = width), as the header's C parameter reads.  y DEV u8 [num_frames, height, width, 1], cbcr DEV u8
+ * [num_frames, h, w, 2] with cbcr[..., 0] = U and cbcr[..., 1] = V, both contiguous; cbcr 2-byte aligned, nothing else
+ * need be aligned.  Only plane bytes are read.  Checked on the host before anything is launched: sizes positive (width,
+ * height up to 2^20, num_frames height < 2^31), even width and height for 420, frame_stride >= the bytes of a frame,
+ * first_offset >= 0, and first_offset + (num_frames - 1) frame_stride + frame bytes <= raw_bytes.  num_frames == 0
+ * launches nothing. */
+int tfc_y4m_unpack(const void* raw, int64_t raw_bytes, int64_t num_frames, int64_t width, int64_t height, int chroma,
+                   int64_t frame_stride, int64_t first_offset, void* y, void* cbcr, void* stream);
+
+/* The inverse, for writing frames (the reference has no writer): the planes of y and cbcr go to raw at the same
+ * offsets.  Only plane bytes are written: what lies in front of first_offset, between frames (frame_stride beyond the
+ * bytes of a frame) and behind the last frame is left as it is.  Arguments and checks as for tfc_y4m_unpack. */
+int tfc_y4m_pack(const void* y, const void* cbcr, void* raw, int64_t raw_bytes, int64_t num_frames, int64_t width,
+                 int64_t height, int chroma, int64_t frame_stride, int64_t first_offset, void* stream);
+
+/* (y, cbcr) as tfc_y4m_unpack writes them -> rgb DEV [num_frames, height, width, 3] on the 0...255 scale, in one kernel.
+ * The reference has no counterpart (its models are fed RGB PNGs).  With (Kr, Kb) = (0.299, 0.114) for matrix 0
+ * (bt601) or (0.2126, 0.0722) for matrix 1 (bt709) and Kg = 1 - Kr - Kb:
+ *   Y' = y, C' = c - 128 (full_range 1)  or  Y' = (y - 16) 255 / 219, C' = (c - 128) 255 / 224 (full_range 0);
+ *   R = Y' + 2 (1 - Kr) Cr',  B = Y' + 2 (1 - Kb) Cb',  G = Y' - (2 Kr (1 - Kr) / Kg) Cr' - (2 Kb (1 - Kb) / Kg) Cb'
+ * (the four coefficients in float64 on the host, float32 in the kernel).  420 chroma is upsampled first: upsample 0
+ * (nearest) c[i / 2, j / 2]; upsample 1 (bilinear, centre siting, separable) row 2m takes 0.75 c[m] + 0.25 c[max(m - 1,
+ * 0)], row 2m + 1 takes 0.75 c[m] + 0.25 c[min(m + 1, h - 1)], columns alike.  clip != 0 clamps to [0, 255].
+ * dtype 0: uint8, always clamped, rounded half to even; 1: float32; 2: bfloat16 (round to nearest even).
+ * Checked on the host: the sizes as for tfc_y4m_unpack, and the matrix, full_range, upsample and dtype codes. */
+int tfc_ycbcr_to_rgb(const void* y, const void* cbcr, void* rgb, int64_t num_frames, int64_t width, int64_t height,
+                     int chroma, int matrix, int full_range, int upsample, int dtype, int clip, void* stream);
+
+/* The inverse (no counterpart in the reference): rgb DEV [num_frames, height, width, 3] of dtype (codes as above), 0...255
+ * -> y, cbcr DEV u8 as above, in one kernel:
+ *   Y' = Kr R + Kg G + Kb B,  Cb' = (B - Y') / (2 (1 - Kb)),  Cr' = (R - Y') / (2 (1 - Kr));
+ * 420 chroma is the mean of each 2 x 2 block of Cb' / Cr'; then the range scaling is undone, the result clamped to
+ * [0, 255] and rounded half to even.  The same host-side checks. */
+int tfc_rgb_to_ycbcr(const void* rgb, int dtype, void* y, void* cbcr, int64_t num_frames, int64_t width,
+                     int64_t height, int chroma, int matrix, int full_range, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
