@@ -1,5 +1,6 @@
 """Datasets (the reference's `python/datasets`)."""
-from . import y4m_dataset
+from . import patch_dataset, y4m_dataset
+from .patch_dataset import PatchDataset  # noqa: F401
 from .y4m_dataset import Y4MDataset, Y4MWriter  # noqa: F401
 
-__all__ = ["Y4MDataset", "Y4MWriter"]
+__all__ = ["Y4MDataset", "Y4MWriter"]      # the reference's `python/datasets`; PatchDataset is exported by name

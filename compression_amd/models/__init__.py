@@ -1,11 +1,12 @@
 """Callers of the hot path: the model definitions (architecture and shapes of models/bls2017.py,
-models/bmshj2018.py, models/ms2020.py and models/hific; no dataset plumbing; HiFiC's GAN training step is
-hific_train), and the toy-source family of models/toy_sources/ (toy_sources)."""
-from . import bls2017, bmshj2018, hific, hific_train, ms2020, toy_sources
+models/bmshj2018.py, models/ms2020.py and models/hific; `train` is their compile + fit, `codec_io` their command line; HiFiC's GAN
+training step is hific_train), and the toy-source family of models/toy_sources/ (toy_sources)."""
+from . import bls2017, bmshj2018, hific, hific_train, ms2020, toy_sources, train
 from .bls2017 import BLS2017Model
 from .bmshj2018 import BMSHJ2018Model
 from .ms2020 import MS2020Model
 from .hific import Discriminator, HiFiCModel
 from .hific_train import HiFiCTrainer
+from .train import Trainer
 from .codec_io import compress_file, decompress_file, read_png, write_png  # noqa: F401
 from .toy_sources import NTCModel, VECVQModel  # noqa: F401

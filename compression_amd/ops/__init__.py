@@ -1,7 +1,8 @@
 """Operator-level API (the reference's `python/ops`)."""
-from . import gen_ops, image_ops, math_ops, padding_ops, round_ops, video_ops, vq_ops
+from . import gen_ops, image_ops, math_ops, padding_ops, round_ops, train_ops, video_ops, vq_ops
 from .gen_ops import *  # noqa: F401,F403
 from .image_ops import ssim, ssim_multiscale, ssim_multiscale_reference, ssim_reference  # noqa: F401
 from .vq_ops import ecvq_assign, ecvq_assign_reference, ecvq_counts  # noqa: F401
+from .train_ops import crop_patches, crop_patches_reference, keras_adam, keras_adam_reference  # noqa: F401
 from .video_ops import (pack_frames, pack_frames_reference, rgb_to_ycbcr, rgb_to_ycbcr_reference,  # noqa: F401
                         unpack_frames, unpack_frames_reference, ycbcr_to_rgb, ycbcr_to_rgb_reference)

@@ -839,6 +839,46 @@ int tfc_ycbcr_to_rgb(const void* y, const void* cbcr, void* rgb, int64_t num_fra
 int tfc_rgb_to_ycbcr(const void* rgb, int dtype, void* y, void* cbcr, int64_t num_frames, int64_t width,
                      int64_t height, int chroma, int matrix, int full_range, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Training: random crops and the Keras Adam step (models/bls2017.py:198-270) */
+/* ------------------------------------------------------------------------ */
+
+/* num_patches random crops in one launch (tf.image.random_crop per image on host threads, bls2017.py:198-200).
+ * pool DEV u8 [pool_bytes]: decoded images back to back, each [H_i, W_i, 3] row-major.  table DEV int64
+ * [num_patches, 4], 8-byte aligned: per patch the byte offset of the image's first pixel in pool, the image width in
+ * pixels, top and left.  out DEV [num_patches, patchsize, patchsize, 3], contiguous and 16-byte aligned, of dtype 0
+ * (uint8), 1 (float32) or 2 (bfloat16): out[b, r, c, k] = pool[offset_b + ((top_b + r) W_b + left_b + c) 3 + k], the
+ * integers 0...255, which all three types hold exactly.  Only the 3 patchsize bytes of each patch row are read, from
+ * whatever address they have, so no byte outside [0, pool_bytes) is touched.  The table lives on the device and is
+ * not read by the host: a row with a negative entry, a width, top or left above 2^24, or with
+ * offset + ((top + patchsize - 1) W + left + patchsize) 3 > pool_bytes is not read from at all and yields zeros; callers
+ * check their rows before the upload (ops/train_ops.py raises).  Checked on the host: patchsize in [1, 2^15], the dtype
+ * code, num_patches patchsize^2 3 < 2^31, the pointers and their alignment.  num_patches == 0 launches nothing. */
+int tfc_crop_patches(const void* pool, int64_t pool_bytes, const int64_t* table, int64_t num_patches,
+                     int64_t patchsize, int dtype, void* out, void* stream);
+
+/* One launch takes at most this many tensors; a workgroup takes one chunk of this many elements of one tensor. */
+#define TFC_KERAS_ADAM_CAPACITY 64
+#define TFC_KERAS_ADAM_CHUNK 4096
+
+/* One optimiser step of tf.keras.optimizers.Adam (Keras 2.14 `update_step`; third-party code, not part of the
+ * reference tree) over count <= TFC_KERAS_ADAM_CAPACITY float32 tensors in one launch.  params, grads, ms, vs and
+ * numels are HOST arrays of count entries: DEV pointers (4-byte aligned; 16-byte aligned tensors take 16-byte
+ * accesses) and element counts; numels[k] == 0 is legal.  Every element is updated in float32, in exactly this order
+ * of individually rounded operations (no fused multiply-add; division and square root correctly rounded):
+ *   m' = m + (g - m) * c1
+ *   v' = v + (g * g - v) * c2
+ *   p' = p - (m' * alpha) / (sqrt(v') + eps)
+ * The caller passes c1 = float32(1 - beta_1), c2 = float32(1 - beta_2), eps = float32(epsilon) and
+ * alpha = float32(lr sqrt(1 - beta_2^t) / (1 - beta_1^t)), computed in float64 and rounded once, t counting from 1.
+ * So epsilon is added to sqrt(v'), not to the bias-corrected sqrt(v_hat), and both bias corrections sit in alpha.
+ * skip: DEV int32, 4-byte aligned, or null.  When *skip != 0 the launch writes nothing at all: a non-finite loss stops
+ * the update without a host round trip.  The table travels in the kernel arguments: nothing is uploaded or allocated.
+ * Checked on the host: count, null pointers of non-empty tensors, alignment, non-negative element counts. */
+int tfc_keras_adam(void* const* params, const void* const* grads, void* const* ms, void* const* vs,
+                   const int64_t* numels, int count, float alpha, float c1, float c2, float eps, const int32_t* skip,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
