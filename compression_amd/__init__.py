@@ -11,12 +11,14 @@ from .ops.image_ops import ssim, ssim_multiscale, ssim_multiscale_reference, ssi
 from .ops.math_ops import lower_bound, perturb_and_apply, upper_bound  # noqa: F401
 from .ops.padding_ops import same_padding_for_kernel  # noqa: F401
 from .ops.train_ops import crop_patches, crop_patches_reference, keras_adam, keras_adam_reference  # noqa: F401
+from .ops.train_ops import scale_crop_patches, scale_crop_patches_reference  # noqa: F401
 from .ops.video_ops import (pack_frames, pack_frames_reference, rgb_to_ycbcr, rgb_to_ycbcr_reference,  # noqa: F401
                             unpack_frames, unpack_frames_reference, ycbcr_to_rgb, ycbcr_to_rgb_reference)
 from .ops.vq_ops import ecvq_assign, ecvq_assign_reference, ecvq_counts  # noqa: F401
 from .ops.round_ops import round_st, soft_round, soft_round_conditional_mean, soft_round_inverse  # noqa: F401
 from .datasets import *  # noqa: F401,F403
 from .datasets.patch_dataset import PatchDataset  # noqa: F401
+from .datasets.scaled_patch_dataset import ScaledPatchDataset  # noqa: F401
 from .distributions import *  # noqa: F401,F403
 from .entropy_models import *  # noqa: F401,F403
 from .layers import *  # noqa: F401,F403

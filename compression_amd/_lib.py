@@ -145,6 +145,7 @@ SIGNATURES = {
     "tfc_ycbcr_to_rgb": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _vp]),
     "tfc_rgb_to_ycbcr": (_int, [_vp, _int, _vp, _vp, _i64, _i64, _i64, _int, _int, _int, _vp]),
     "tfc_crop_patches": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp, _vp]),
+    "tfc_scale_crop_patches": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp, _vp]),
     "tfc_keras_adam": (_int, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64), _int,
                               C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp]),
 }

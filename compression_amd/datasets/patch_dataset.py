@@ -73,8 +73,7 @@ class PatchDataset:
         with ThreadPoolExecutor(self.threads) as pool:
             sizes = list(pool.map(_image_size, files))
         for name, (w, h) in zip(files, sizes):
-            if h < self.patchsize or w < self.patchsize:
-                raise ValueError(f"{name} is {h} x {w}, smaller than the {self.patchsize} x {self.patchsize} patch")
+            self._check_image_size(name, h, w)
         self._width = torch.tensor([w for w, _ in sizes], dtype=torch.int64)
         self._height = torch.tensor([h for _, h in sizes], dtype=torch.int64)
         self._bytes = 3 * self._width * self._height
@@ -89,6 +88,19 @@ class PatchDataset:
         self._slice_left = 0
         self._next = None           # (future of the next slice, its first item as (pass_no, offset))
         self._worker = None
+
+    # ---------------------------------------------------------------------------------------------------------------
+    # what a subclass with another kind of patch replaces (ScaledPatchDataset): which images it takes, what an item of
+    # the stream is beyond its file index (`_draw_pass`), and how a batch is cut from the pool
+
+    def _check_image_size(self, name, h, w):
+        if h < self.patchsize or w < self.patchsize:
+            raise ValueError(f"{name} is {h} x {w}, smaller than the {self.patchsize} x {self.patchsize} patch")
+
+    def _cut(self, piece, items):
+        table = torch.tensor([[piece.where[i], int(self._width[i]), top, left] for i, top, left in items],
+                             dtype=torch.int64)
+        return train_ops.crop_patches(piece.pool, table, self.patchsize, self.dtype)
 
     # ---------------------------------------------------------------------------------------------------------------
     # the stream
@@ -242,9 +254,7 @@ class PatchDataset:
             raise StopIteration
         items = self._peek(self.batchsize)
         piece = self._current_slice()
-        table = torch.tensor([[piece.where[i], int(self._width[i]), top, left] for i, top, left in items],
-                             dtype=torch.int64)
-        batch = train_ops.crop_patches(piece.pool, table, self.patchsize, self.dtype)
+        batch = self._cut(piece, items)
         self._advance(self.batchsize)
         if not self._fits:
             self._slice_left -= self.batchsize

@@ -1,7 +1,7 @@
 """Callers of the hot path: the model definitions (architecture and shapes of models/bls2017.py,
 models/bmshj2018.py, models/ms2020.py and models/hific; `train` is their compile + fit, `codec_io` their command line; HiFiC's GAN
-training step is hific_train), and the toy-source family of models/toy_sources/ (toy_sources)."""
-from . import bls2017, bmshj2018, hific, hific_train, ms2020, toy_sources, train
+training step and command are hific_train, its evaluation command hific_evaluate), and the toy-source family of models/toy_sources/ (toy_sources)."""
+from . import bls2017, bmshj2018, hific, hific_evaluate, hific_train, ms2020, toy_sources, train
 from .bls2017 import BLS2017Model
 from .bmshj2018 import BMSHJ2018Model
 from .ms2020 import MS2020Model

@@ -1,12 +1,14 @@
-"""The two streaming ops of the training loop (csrc/train.hip): the random crops of the input pipeline and the Keras
-Adam step.
+"""The streaming ops of the training loop (csrc/train.hip, csrc/scale_crop.hip): the random crops of the input
+pipeline, with and without HiFiC's random resize, and the Keras Adam step.
 
-    crop_patches     B patches [P, P, 3] out of a flat pool of decoded images -> [B, P, P, 3]   (models/bls2017.py:198-200)
-    keras_adam       one step of tf.keras.optimizers.Adam over a list of float32 tensors, in place
+    crop_patches         B patches [P, P, 3] out of a flat pool of decoded images -> [B, P, P, 3]   (models/bls2017.py:198-200)
+    scale_crop_patches   the same out of the bilinearly RESIZED images, which never exist      (models/hific/model.py:316-351)
+    keras_adam           one step of tf.keras.optimizers.Adam over a list of float32 tensors, in place
 
-Each runs one kernel (tfc_crop_patches, tfc_keras_adam; one per KERAS_ADAM_CAPACITY tensors) on device tensors and has
-a `*_reference` twin of plain tensor ops, which CPU tensors take.  include/tfc_hip.h states both definitions in full;
-tests/train_ref.py holds the numpy / float64 forms.  The Adam rule, every operation rounded to float32 on its own:
+Each runs one kernel (tfc_crop_patches, tfc_scale_crop_patches, tfc_keras_adam; one per KERAS_ADAM_CAPACITY tensors) on
+device tensors and has a `*_reference` twin of plain tensor ops, which CPU tensors take.  include/tfc_hip.h states the
+definitions in full; tests/train_ref.py and tests/scale_crop_ref.py hold the numpy / float64 forms.  The Adam rule, every
+operation rounded to float32 on its own:
 
     m' = m + (g - m) * c1                      c1 = float32(1 - beta_1)
     v' = v + (g * g - v) * c2                  c2 = float32(1 - beta_2)
@@ -24,7 +26,8 @@ import torch
 from .. import _lib
 from .video_ops import DTYPE_CODE
 
-__all__ = ["crop_patches", "crop_patches_reference", "keras_adam", "keras_adam_reference", "keras_adam_constants",
+__all__ = ["crop_patches", "crop_patches_reference", "scale_crop_patches", "scale_crop_patches_reference",
+           "keras_adam", "keras_adam_reference", "keras_adam_constants",
            "KERAS_ADAM_CAPACITY", "KERAS_ADAM_CHUNK"]
 
 KERAS_ADAM_CAPACITY = 64       # tensors per launch (TFC_KERAS_ADAM_CAPACITY)
@@ -89,6 +92,111 @@ def crop_patches(pool, table, patchsize, dtype=torch.uint8):
     with torch.cuda.device(pool.device):
         _lib.check(_lib.lib().tfc_crop_patches(pool.data_ptr(), pool.numel(), dev_table.data_ptr(), table.shape[0], P,
                                                DTYPE_CODE[dtype], out.data_ptr(), _lib.stream_ptr()))
+    return out
+
+
+# -------------------------------------------------------------------------------------------------------------------
+# crops of resized images
+
+
+def _check_scale_crop(pool, table, patchsize, dtype):
+    if pool.dtype != torch.uint8:
+        raise TypeError(f"pool must be uint8, got {pool.dtype}")
+    if pool.dim() != 1 or not pool.is_contiguous():
+        raise ValueError(f"pool must be a flat contiguous tensor, received shape {tuple(pool.shape)}")
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"dtype must be torch.float32 or bfloat16 (the values are not integers), got {dtype}")
+    if table.device.type != "cpu" or table.dtype != torch.int64:
+        raise TypeError(f"table must be a CPU int64 tensor, got {table.dtype} on {table.device}")
+    if table.dim() != 2 or table.shape[1] != 7:
+        raise ValueError("table must be [B, 7] (offset, width, height, resized width, resized height, top, left), "
+                         f"received shape {tuple(table.shape)}")
+    patchsize = int(patchsize)
+    if patchsize < 1 or patchsize > 2 ** 15:
+        raise ValueError(f"patchsize must be in [1, 2^15], got {patchsize}")
+    if table.shape[0] * patchsize * patchsize * 3 >= 2 ** 31:
+        raise ValueError(f"{table.shape[0]} patches of {patchsize} x {patchsize} x 3 values: one call takes fewer than "
+                         "2^31 values")
+    table = table.contiguous()
+    off, width, height, new_width, new_height, top, left = table.unbind(1)
+    sizes = table[:, 1:5]
+    negative = (table < 0).any(dim=1)
+    # a negative entry is reported as such; the products below are formed for the other rows only
+    out_of_range = ~negative & ((sizes < 1) | (sizes > 2 ** 24)).any(dim=1)
+    sound = ~negative & ~out_of_range
+    outside = sound & ((top + patchsize > new_height) | (left + patchsize > new_width))
+    end = off + 3 * width.clamp(0, 2 ** 24) * height.clamp(0, 2 ** 24)
+    past = sound & ((off > pool.numel()) | (end > pool.numel()))
+    bad = negative | out_of_range | outside | past
+    if bad.any():
+        row = int(bad.nonzero()[0])
+        o, w, h, ow, oh, t, l = table[row].tolist()
+        if negative[row]:
+            raise ValueError(f"table row {row} has a negative entry: offset {o}, width {w}, height {h}, resized width "
+                             f"{ow}, resized height {oh}, top {t}, left {l}")
+        if out_of_range[row]:
+            raise ValueError(f"table row {row}: width {w}, height {h}, resized width {ow} and resized height {oh} must "
+                             "be in [1, 2^24]")
+        if outside[row]:
+            raise ValueError(f"table row {row}: a {patchsize} x {patchsize} patch at top {t}, left {l} does not fit the "
+                             f"resized image of {oh} x {ow}")
+        raise ValueError(f"table row {row}: the {h} x {w} image at byte {o} ends at byte {int(end[row])}, the pool has "
+                         f"{pool.numel()}")
+    return table, patchsize
+
+
+def scale_crop_patches_reference(pool, table, patchsize, dtype=torch.float32):
+    """`scale_crop_patches` as tensor ops, one float32 operation per line of the definition (no lerp or addcmul, which
+    may fuse): what the kernel is bit-identical to."""
+    table, P = _check_scale_crop(pool, table, patchsize, dtype)
+    f32 = torch.float32
+    off, width, height, new_width, new_height, top, left = table.unbind(1)
+    steps = torch.arange(P, dtype=torch.int64)
+
+    def axis(size, new_size, first):
+        scale = size.to(f32) / new_size.to(f32)
+        pos = (first[:, None] + steps).to(f32) * scale[:, None]                   # [B, P]
+        low_f = torch.minimum(torch.floor(pos), (size - 1).to(f32)[:, None])
+        low = low_f.to(torch.int64)
+        high = torch.minimum(low + 1, (size - 1)[:, None])
+        return low, high, pos - low_f
+
+    y0, y1, wy = axis(height, new_height, top)
+    x0, x1, wx = axis(width, new_width, left)
+    channel = torch.arange(3, dtype=torch.int64)
+
+    def pixels(y, x):
+        at = off[:, None, None] + (y[:, :, None] * width[:, None, None] + x[:, None, :]) * 3      # [B, P, P]
+        return pool[(at[..., None] + channel).to(pool.device)].to(f32)
+
+    wx = wx[:, None, :, None].to(pool.device)
+    wy = wy[:, :, None, None].to(pool.device)
+    tl, tr, bl, br = pixels(y0, x0), pixels(y0, x1), pixels(y1, x0), pixels(y1, x1)
+    upper = tl + (tr - tl) * wx
+    lower = bl + (br - bl) * wx
+    return (upper + (lower - upper) * wy).to(dtype)
+
+
+def scale_crop_patches(pool, table, patchsize, dtype=torch.float32):
+    """B patches [P, P, 3] of bilinearly resized images, computed from the decoded images: the resized images never
+    exist (TF1 `resize_bilinear`, align_corners=False, half_pixel_centers=False, as `tf.image.resize_images` of
+    models/hific/model.py:346 runs it; the definition is stated in include/tfc_hip.h).
+
+    pool: flat uint8, decoded images [H_i, W_i, 3] back to back; table: CPU int64 [B, 7], per patch the byte offset of
+    the image's first pixel, its width W and height H, the resized width OW and height OH, and top and left IN THE
+    RESIZED IMAGE -> [B, P, P, 3] of `dtype` (float32, or bfloat16: the float32 value rounded to nearest even).  The
+    table is checked here (no negative entry, the four sizes in [1, 2^24], the patch inside the resized image, the
+    image inside the pool; ValueError names the row) and then uploaded, one small copy.  One kernel on a device pool,
+    bit-exact with `scale_crop_patches_reference`, which a CPU pool takes."""
+    if not pool.is_cuda:
+        return scale_crop_patches_reference(pool, table, patchsize, dtype)
+    table, P = _check_scale_crop(pool, table, patchsize, dtype)
+    out = torch.empty((table.shape[0], P, P, 3), dtype=dtype, device=pool.device)
+    dev_table = table.to(pool.device, non_blocking=True)
+    with torch.cuda.device(pool.device):
+        _lib.check(_lib.lib().tfc_scale_crop_patches(pool.data_ptr(), pool.numel(), dev_table.data_ptr(),
+                                                     table.shape[0], P, DTYPE_CODE[dtype], out.data_ptr(),
+                                                     _lib.stream_ptr()))
     return out
 
 

@@ -857,6 +857,28 @@ int tfc_rgb_to_ycbcr(const void* rgb, int dtype, void* y, void* cbcr, int64_t nu
 int tfc_crop_patches(const void* pool, int64_t pool_bytes, const int64_t* table, int64_t num_patches,
                      int64_t patchsize, int dtype, void* out, void* stream);
 
+/* num_patches random crops of RESIZED images in one launch: HiFiC's training input (models/hific/model.py:316-351), where
+ * tf.image.resize_images resizes every whole image on a host thread and tf.image.random_crop keeps one patch.  Here
+ * only the patch's pixels are computed and the resized image never exists.  pool DEV u8 [pool_bytes] as for
+ * tfc_crop_patches.  table DEV int64 [num_patches, 7], 8-byte aligned: per patch the byte offset of the image's first
+ * pixel in pool, the image's width W and height H, the resized width OW and height OH, and top and left IN THE RESIZED
+ * IMAGE.  out DEV [num_patches, patchsize, patchsize, 3], contiguous and 16-byte aligned, of dtype 1 (float32) or 2
+ * (bfloat16); uint8 is not offered, the values are not integers.  The definition is TF1's resize_bilinear with
+ * align_corners=False and half_pixel_centers=False (third-party code, not part of the reference tree).  For out[b, i, j, c]:
+ *   sy = float32(H) / float32(OH)          sx = float32(W) / float32(OW)          (float32 division)
+ *   py = float32(top + i) * sy             px = float32(left + j) * sx            (float32 product)
+ *   y0 = min(floor(py), H - 1)   y1 = min(y0 + 1, H - 1)   wy = py - float32(y0)  (x0, x1, wx alike)
+ *   t = tl + (tr - tl) * wx      b = bl + (br - bl) * wx   v = t + (b - t) * wy
+ * with tl, tr, bl, br the bytes of channel c at (y0, x0), (y0, x1), (y1, x0), (y1, x1) as float32.  Every operation is
+ * rounded to float32 on its own: no fused multiply-add.  bfloat16 is v rounded to nearest even.  Only bytes of the
+ * image itself are read.  The table lives on the device and is not read by the host: a row with a negative entry, with
+ * W, H, OW or OH outside [1, 2^24], with top + patchsize > OH or left + patchsize > OW, or with offset + 3 W H >
+ * pool_bytes is not read from at all and yields zeros; callers check their rows before the upload (ops/train_ops.py
+ * raises).  Checked on the host: patchsize in [1, 2^15], the dtype code, num_patches patchsize^2 3 < 2^31, the pointers
+ * and their alignment.  num_patches == 0 launches nothing. */
+int tfc_scale_crop_patches(const void* pool, int64_t pool_bytes, const int64_t* table, int64_t num_patches,
+                           int64_t patchsize, int dtype, void* out, void* stream);
+
 /* One launch takes at most this many tensors; a workgroup takes one chunk of this many elements of one tensor. */
 #define TFC_KERAS_ADAM_CAPACITY 64
 #define TFC_KERAS_ADAM_CHUNK 4096
