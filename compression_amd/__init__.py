@@ -15,6 +15,8 @@ from .ops.train_ops import scale_crop_patches, scale_crop_patches_reference  # n
 from .ops.video_ops import (pack_frames, pack_frames_reference, rgb_to_ycbcr, rgb_to_ycbcr_reference,  # noqa: F401
                             unpack_frames, unpack_frames_reference, ycbcr_to_rgb, ycbcr_to_rgb_reference)
 from .ops.vq_ops import ecvq_assign, ecvq_assign_reference, ecvq_counts  # noqa: F401
+from .ops.lvac_ops import (PointBlocks, RahtTree, point_mlp_loss, point_mlp_loss_reference, raht_synthesize,  # noqa: F401
+                           raht_synthesize_reference)
 from .ops.round_ops import round_st, soft_round, soft_round_conditional_mean, soft_round_inverse  # noqa: F401
 from .datasets import *  # noqa: F401,F403
 from .datasets.patch_dataset import PatchDataset  # noqa: F401

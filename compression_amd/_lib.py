@@ -148,6 +148,13 @@ SIGNATURES = {
     "tfc_scale_crop_patches": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp, _vp]),
     "tfc_keras_adam": (_int, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64), _int,
                               C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp]),
+    "tfc_raht_forward": (_int, [_vp, _i64, C.POINTER(_vp), C.POINTER(_i64), _vp, _vp, _i64, _int, _i64, _vp, _i64, _vp]),
+    "tfc_raht_backward": (_int, [_vp, _i64, C.POINTER(_vp), C.POINTER(_i64), _vp, _vp, _i64, _int, _i64, _vp, _i64,
+                                 _vp]),
+    "tfc_point_mlp_forward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_float), _vp, _i64, _i64, _int,
+                                     _int, _int, _vp, _vp, _vp, _vp]),
+    "tfc_point_mlp_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_float), _vp, _vp, _i64,
+                                      _i64, _int, _int, _vp, _vp, _vp]),
 }
 
 ABI_VERSION = 2          # include/tfc_hip.h TFC_ABI_VERSION this binding was written against

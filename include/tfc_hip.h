@@ -901,6 +901,61 @@ int tfc_keras_adam(void* const* params, const void* const* grads, void* const* m
                    const int64_t* numels, int count, float alpha, float c1, float c2, float eps, const int32_t* skip,
                    void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* LVAC: inverse RAHT and the per-point decoder (models/lvac/lvac.ipynb)    */
+/* ------------------------------------------------------------------------ */
+
+/* Inverse RAHT down a binary tree of octree prefixes (the notebook's Model.synthesize without its repeat and
+ * unsorted_segment_sum).  Level l turns rows[l] parent rows into child rows:
+ *   child[c, :] = parent[child_parent[c], :] + child_weight[c] * ac[l][child_ac[c], :]     (child_ac < 0: no AC term)
+ * dc DEV f32 [n_root, channels]; ac HOST array of `levels` DEV f32 pointers [AC rows of the level, channels] (ignored
+ * for a level without AC rows); out DEV f32 [n_out, channels].  desc HOST and desc_dev DEV hold the same int64
+ * [levels, 10]: child rows, parent rows, AC rows, then the offsets, in 4-byte words of `tables`, of child_parent (i32),
+ * child_ac (i32), child_weight (f32), parent_first (i32), parent_count (i32), ac_left (i32), ac_coeff (f32).  tables DEV,
+ * table_words words long.  Checked on the host before any launch: levels <= 64, channels in [1, 65536], every level's
+ * children = parents + AC rows, the chain n_root -> ... -> n_out, every table inside the buffer.  The table VALUES are
+ * the caller's (ops/lvac_ops.py RahtTree checks them once); whatever they hold, a kernel reads nothing outside the
+ * tensors: an index out of range contributes zero.  A level without AC rows is the identity and launches nothing;
+ * consecutive levels of at most 4096 elements share one single-workgroup launch.  Gathers only, no atomics:
+ * bit-identical from call to call. */
+int tfc_raht_forward(const float* dc, int64_t n_root, const float* const* ac, const int64_t* desc,
+                     const int64_t* desc_dev, const int32_t* tables, int64_t table_words, int levels, int64_t channels,
+                     float* out, int64_t n_out, void* stream);
+/* Its gradients, from d_out DEV f32 [n_out, channels], level by level upwards:
+ *   d_parent[i, :] = sum of d_child over the node's parent_count[i] (1 or 2) children from parent_first[i]
+ *   d_ac[l][k, :]  = ac_coeff[k] * d_child[ac_left[k], :] + d_child[ac_left[k] + 1, :]
+ * d_ac HOST array of `levels` DEV f32 pointers (written; ignored for a level without AC rows), d_dc DEV f32
+ * [n_root, channels]. */
+int tfc_raht_backward(const float* d_out, int64_t n_out, float* const* d_ac, const int64_t* desc,
+                      const int64_t* desc_dev, const int32_t* tables, int64_t table_words, int levels,
+                      int64_t channels, float* d_dc, int64_t n_root, void* stream);
+
+/* The per-point decoder and its squared error (Model.reconstruct_at_level and evaluate_reconstruction_at_level with
+ * the "mlp" extractor), without the [N, hidden] activations:
+ *   recon[n, :] = A (W2^T relu(W1^T [position[n]; z[index[n]]] + b1) + b2) + o,   clipped to [0, 255] if clip
+ *   sse         = sum_n sum_r (recon[n, r] - target[n, r])^2
+ * z DEV f32 [n_blocks, channels]; index DEV i32 [n]; position DEV f32 [n, 3] or NULL (W1 then has `channels` rows,
+ * else 3 + channels with the position rows first); w1 [rows, hidden], b1 [hidden], w2 [hidden, 3], b2 [3] DEV f32;
+ * affine HOST f32 [12]: A row-major, then o; target DEV f32 [n, 3].  Outputs: recon DEV f32 [n, 3] or NULL; gerr DEV
+ * f32 [n, 3] or NULL, recon - target where the gradient flows and 0 where the clip cut it (what the backward needs);
+ * sse DEV f32 [1], per-workgroup partial sums added in a fixed order.  All float32 on the vector unit.  channels in
+ * [1, 32], hidden in [1, 1024] (csrc/lvac_params.h), checked on the host.  An index outside [0, n_blocks) reads nothing
+ * and stands for a zero latent.  n == 0 writes sse = 0. */
+int tfc_point_mlp_forward(const float* z, const int32_t* index, const float* position, const float* w1,
+                          const float* b1, const float* w2, const float* b2, const float* affine, const float* target,
+                          int64_t n, int64_t n_blocks, int channels, int hidden, int clip, float* recon, float* gerr,
+                          float* sse, void* stream);
+/* Its gradients for g_sse = dL/dsse (DEV f32 [1]) and the gerr of the forward call.  d_params DEV f32
+ * [rows hidden + hidden + 3 hidden + 3] or NULL: dW1, db1, dW2, db2 one after the other; d_z DEV f32
+ * [n_blocks, channels] or NULL.  block_offset DEV int64 [n_blocks + 1]: the points of block b are
+ * [block_offset[b], block_offset[b + 1]) (index non-decreasing).  The hidden activations are recomputed per tile of 128
+ * points.  Deterministic, no atomics: parameter gradients are accumulated by at most 128 tile groups and merged in
+ * ascending order; the latent gradient is written per point ([n, channels]) and summed per block in a fixed order. */
+int tfc_point_mlp_backward(const float* z, const int32_t* index, const int64_t* block_offset, const float* position,
+                           const float* w1, const float* b1, const float* w2, const float* b2, const float* affine,
+                           const float* gerr, const float* g_sse, int64_t n, int64_t n_blocks, int channels,
+                           int hidden, float* d_params, float* d_z, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
