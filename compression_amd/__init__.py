@@ -17,8 +17,11 @@ from .ops.video_ops import (pack_frames, pack_frames_reference, rgb_to_ycbcr, rg
 from .ops.vq_ops import ecvq_assign, ecvq_assign_reference, ecvq_counts  # noqa: F401
 from .ops.lvac_ops import (PointBlocks, RahtTree, point_mlp_loss, point_mlp_loss_reference, raht_synthesize,  # noqa: F401
                            raht_synthesize_reference)
+from .ops.flow_ops import (gaussian_scale_space, gaussian_scale_space_reference, scale_space_predict,  # noqa: F401
+                           scale_space_predict_reference, scale_space_warp, scale_space_warp_reference)
 from .ops.round_ops import round_st, soft_round, soft_round_conditional_mean, soft_round_inverse  # noqa: F401
 from .datasets import *  # noqa: F401,F403
+from .datasets.clip_dataset import ClipDataset  # noqa: F401
 from .datasets.patch_dataset import PatchDataset  # noqa: F401
 from .datasets.scaled_patch_dataset import ScaledPatchDataset  # noqa: F401
 from .distributions import *  # noqa: F401,F403

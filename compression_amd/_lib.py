@@ -155,6 +155,12 @@ SIGNATURES = {
                                      _int, _int, _vp, _vp, _vp, _vp]),
     "tfc_point_mlp_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_float), _vp, _vp, _i64,
                                       _i64, _int, _int, _vp, _vp, _vp]),
+    "tfc_scale_space_volume": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _int, C.c_double, _vp]),
+    "tfc_scale_space_volume_backward": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _int, C.c_double, _vp]),
+    "tfc_scale_space_warp_forward": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _int, _vp]),
+    "tfc_scale_space_warp_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _i64, _i64, _i64, _int, _int,
+                                             _vp]),
+    "tfc_scale_space_workspace": (_i64, [_i64, _i64, _i64, _int, _int]),
 }
 
 ABI_VERSION = 2          # include/tfc_hip.h TFC_ABI_VERSION this binding was written against

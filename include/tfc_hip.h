@@ -956,6 +956,65 @@ int tfc_point_mlp_backward(const float* z, const int32_t* index, const int64_t* 
                            const float* gerr, const float* g_sse, int64_t n, int64_t n_blocks, int channels,
                            int hidden, float* d_params, float* d_z, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Scale-space warp (Agustsson et al., "Scale-space flow for end-to-end     */
+/* optimized video compression", CVPR 2020, section 3.1)                    */
+/* ------------------------------------------------------------------------ */
+
+/* The definition is this project's own (the paper fixes the idea, not the taps, the borders or the clamps); parity with
+ * the authors' trained models is unpinned.  All tensors DEV f32, contiguous, channels last, 16-byte aligned.
+ *
+ * The scale-space volume (section 3.1, "scale-space volume"): x [n, h, w, channels] -> volume
+ * [n, num_levels + 1, h, w, channels].  Plane 0 is x.  Plane p >= 1 is x blurred separably, along W then along H, with
+ * sigma_p = sigma0 2^(p - 1) and taps w_t = exp(-t^2 / (2 sigma_p^2)), |t| <= R_p = ceil(3 sigma_p).  Taps that fall
+ * outside the image are dropped and the rest renormalised:
+ *   out[i] = sum_t w_t x[i + t] / sum_t w_t,     both sums over the t with 0 <= i + t < n
+ * so a constant image stays constant; the norm of a pixel is norm_row[j] norm_col[i].  No pyramid approximation.
+ * Two launches: one row pass that reads each row segment once and writes plane 0 and all row-blurred planes, one column
+ * pass with the plane as a grid dimension.  The taps and their running sums are computed here in double and travel in
+ * the kernel arguments.  Checked on the host before any launch: channels in [1, 8], num_levels in [1, 8], sigma0 > 0,
+ * sigma0 2^(num_levels - 1) <= 64, h and w in [1, 2^14], n (num_levels + 1) h w channels < 2^31, null pointers,
+ * alignment.  n == 0 launches nothing.  The row-blurred planes (4 n num_levels h w channels bytes) come from the
+ * library's block cache. */
+int tfc_scale_space_volume(const float* x, float* volume, int64_t n, int64_t h, int64_t w, int channels,
+                           int num_levels, double sigma0, void* stream);
+/* Its adjoint: g_volume [n, num_levels + 1, h, w, channels] -> g_x [n, h, w, channels],
+ *   g_x = g_volume[:, 0] + sum over p (ascending) of corr_W(corr_H(g_volume[:, p] / norm_p))
+ * where corr is the same zero-padded symmetric correlation and norm_p[i, j] = norm_row[j] norm_col[i] of plane p: a
+ * gather, no scatter, bit-identical from call to call.  The same checks. */
+int tfc_scale_space_volume_backward(const float* g_volume, float* g_x, int64_t n, int64_t h, int64_t w, int channels,
+                                    int num_levels, double sigma0, void* stream);
+/* The warp (section 3.1, "scale-space warp"): flow [n, h, w, 3] = (dx along W in pixels, dy along H, s the plane
+ * coordinate) samples the volume trilinearly.  For output pixel (i, j), with M = num_levels:
+ *   px = fminf(fmaxf(float32(j) + dx, 0), w - 1)    py likewise with i, dy, h    pz = fminf(fmaxf(s, 0), M)
+ *   x0 = min(floor(px), max(w - 2, 0))   x1 = min(x0 + 1, w - 1)   wx = px - x0      (y and z alike; z1 = min(z0 + 1, M))
+ *   out[n, i, j, c] = sum over the 8 corners of (wz wy) wx volume[n, z, y, x, c]     (z outermost, x innermost)
+ * fmaxf sends a NaN coordinate to 0; whatever flow holds, no address outside the volume is formed.  One launch, one
+ * output pixel per lane, the channels of a corner loaded together, 16-byte accesses when channels is 4 or 8. */
+int tfc_scale_space_warp_forward(const float* volume, const float* flow, float* out, int64_t n, int64_t h, int64_t w,
+                                 int channels, int num_levels, void* stream);
+/* The warp's gradients for g [n, h, w, channels]; each output may be NULL.
+ *   g_flow [n, h, w, 3]: a gather per output pixel (needs `volume`).  d out / d dx is the x-derivative of the trilinear
+ *     form (differences of corners, weighted by the other two axes) where 0 < float32(j) + dx < w - 1 strictly, and 0
+ *     where the coordinate was clamped or is NaN; dy and s alike (0 < s < M).  Channels are summed in ascending order.
+ *   g_volume [n, M + 1, h, w, channels]: d out / d volume is the corner weights.  The scatter of g weight accumulates
+ *     in 64-bit integers with vector global atomics; integer addition is associative, so the sums do not depend on the
+ *     arrival order.  A two-stage, fixed-order device reduction yields gmax = max |g| (NaN if any g is not finite); with
+ *     e = floor(log2 gmax) + 1 a contribution is llrint(double(g weight) 2^(40 - e)) and the gradient is
+ *     float32(double(sum) 2^(e - 40)).  gmax == 0 gives all-zero gradients without a scatter; a non-finite gmax fills
+ *     g_flow, g_volume and g_x with NaN.  Nothing is read back to the host.
+ *   g_x [n, h, w, channels]: tfc_scale_space_volume_backward (with sigma0, otherwise unused) applied to the integer
+ *     planes directly; the float volume gradient is not formed unless g_volume is asked for as well.
+ * The scatter requires h w <= 2^22 (then a sum of h w contributions below 2^40 fits 63 bits), checked on the host like
+ * the rest.  The integer planes (tfc_scale_space_workspace bytes) come from the library's block cache and are zeroed
+ * in stream order. */
+int tfc_scale_space_warp_backward(const float* g, const float* volume, const float* flow, float* g_flow,
+                                  float* g_volume, float* g_x, double sigma0, int64_t n, int64_t h, int64_t w,
+                                  int channels, int num_levels, void* stream);
+/* The bytes of the backward's integer planes, 8 n (num_levels + 1) h w channels; -1 (and tfc_last_error) when the
+ * shape fails the checks above. */
+int64_t tfc_scale_space_workspace(int64_t n, int64_t h, int64_t w, int channels, int num_levels);
+
 #ifdef __cplusplus
 }
 #endif
