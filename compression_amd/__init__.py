@@ -19,6 +19,8 @@ from .ops.lvac_ops import (PointBlocks, RahtTree, point_mlp_loss, point_mlp_loss
                            raht_synthesize_reference)
 from .ops.flow_ops import (gaussian_scale_space, gaussian_scale_space_reference, scale_space_predict,  # noqa: F401
                            scale_space_predict_reference, scale_space_warp, scale_space_warp_reference)
+from .ops.context_ops import (ContextParams, ContextScan, context_decode, context_parameters_reference,  # noqa: F401
+                              context_scan, context_scan_reference)
 from .ops.round_ops import round_st, soft_round, soft_round_conditional_mean, soft_round_inverse  # noqa: F401
 from .datasets import *  # noqa: F401,F403
 from .datasets.clip_dataset import ClipDataset  # noqa: F401

@@ -161,6 +161,11 @@ SIGNATURES = {
     "tfc_scale_space_warp_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _i64, _i64, _i64, _int, _int,
                                              _vp]),
     "tfc_scale_space_workspace": (_i64, [_i64, _i64, _i64, _int, _int]),
+    "tfc_context_workspace": (_i64, [_i64, _i64, _i64, _int, _int, _int, _int]),
+    "tfc_context_scan": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp,
+                                _vp, _vp, _vp]),
+    "tfc_context_decode": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _int,
+                                  _vp, _vp, _vp, _vp]),
 }
 
 ABI_VERSION = 2          # include/tfc_hip.h TFC_ABI_VERSION this binding was written against

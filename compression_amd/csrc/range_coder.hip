@@ -526,15 +526,7 @@ __global__ void __launch_bounds__(kBlock) dec_kernel(DecParams p, Dst dst) {
       const int sp = __builtin_amdgcn_readfirstlane(T(start));
       const int prec = sp < 0 ? -sp : sp;
       int sym = dec_symbol(T, st, start + 1, nints - 1, prec, w, lane);
-      if (sp < 0 && sym == nints - 3) {
-        int nb = 0;
-        // bound the unary prefix so damaged input cannot spin forever
-        while (nb < 31 && dec_bit(st, w, lane) == 0) ++nb;
-        int v = 1 << nb;
-        while (--nb >= 0) v |= dec_bit(st, w, lane) << nb;
-        const int neg = dec_bit(st, w, lane);
-        sym = neg ? -v : v + (nints - 3) - 1;
-      }
+      if (sp < 0 && sym == nints - 3) sym = dec_escape(st, w, lane, nints);
       outv = tfc_writelane(sym, n, outv);
     }
     if (j < p.elems) dst.store(s * p.elems + j, t, outv);

@@ -333,6 +333,18 @@ __device__ inline int dec_symbol(const TabFn& T, DecoderState& st, int cdf0, int
   return sym;
 }
 
+// The value behind the escape symbol of a row with negative precision (`nints` = ints of the row, header included):
+// an Elias-gamma code and a sign bit (range_coder_kernels.cc:449-471).
+__device__ inline int dec_escape(DecoderState& st, DigitWindow& w, int lane, int nints) {
+  int nb = 0;
+  // bound the unary prefix so damaged input cannot spin forever
+  while (nb < 31 && dec_bit(st, w, lane) == 0) ++nb;
+  int v = 1 << nb;
+  while (--nb >= 0) v |= dec_bit(st, w, lane) << nb;
+  const int neg = dec_bit(st, w, lane);
+  return neg ? -v : v + (nints - 3) - 1;
+}
+
 struct OutInt32 {
   int32_t* out;
   __device__ void store(int64_t pos, int /*table*/, int32_t sym) const { tfc_gstore(out + pos, sym); }

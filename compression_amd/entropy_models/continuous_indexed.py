@@ -98,9 +98,18 @@ class ContinuousIndexedEntropyModel(continuous_base.ContinuousEntropyModelBase):
         # elementwise: integer matmul / tensordot has no HIP kernel ("addmm_cuda" not implemented for 'Int')
         return (indexes.movedim(self.channel_axis, -1) * strides).sum(-1, dtype=torch.int32)
 
-    def forward(self, bottleneck, indexes, training=True):
+    def forward(self, bottleneck, indexes, training=True, noise=None):
+        """`noise` (training only): the sample u in [-0.5, 0.5) to perturb with instead of a fresh one, for callers
+        that condition other quantities on the same bottleneck + u (the context model of models/mbt2018.py)."""
         bottleneck = torch.as_tensor(bottleneck).to(self.bottleneck_dtype)
         indexes = self._normalize_indexes(torch.as_tensor(indexes))
+        if noise is not None:
+            if not training:
+                raise ValueError("`noise` is the training perturbation; it has no meaning with training=False")
+            noise = torch.as_tensor(noise).to(bottleneck.device, bottleneck.dtype)
+            if noise.shape != bottleneck.shape:
+                raise ValueError(f"`noise` must have the bottleneck's shape {tuple(bottleneck.shape)}, "
+                                 f"received {tuple(noise.shape)}")
         ltm = bottleneck_ops.fused_tail_mass(self.laplace_tail_mass)
         fused = training and ltm is not None and bottleneck_ops.fused_noisy_normal_supported(
             self.prior_fn, self.parameter_fns, bottleneck, self.coding_rank)
@@ -115,7 +124,8 @@ class ContinuousIndexedEntropyModel(continuous_base.ContinuousEntropyModelBase):
             # the parameter functions stay differentiable tensor ops, their gradients flow through `scale`
             scale = torch.as_tensor(self.parameter_fns["scale"](idx), dtype=self.prior_dtype, device=bottleneck.device)
             shifted = bottleneck - loc if (torch.is_tensor(loc) or loc != 0) else bottleneck
-            noise = torch.rand_like(bottleneck) - 0.5
+            if noise is None:
+                noise = torch.rand_like(bottleneck) - 0.5
             perturbed, bits = bottleneck_ops.noisy_normal_bits(shifted, scale, self.coding_rank, noise,
                                                                expected_grads=self.expected_grads,
                                                                laplace_tail_mass=ltm)
@@ -126,7 +136,7 @@ class ContinuousIndexedEntropyModel(continuous_base.ContinuousEntropyModelBase):
             def log_prob_fn(perturbed, idx):
                 return self._log_prob(self._make_prior(idx), perturbed)
             log_probs, perturbed = math_ops.perturb_and_apply(
-                log_prob_fn, bottleneck, indexes, expected_grads=self.expected_grads)
+                log_prob_fn, bottleneck, indexes, u=noise, expected_grads=self.expected_grads)
         else:
             prior = self._make_prior(indexes)
             perturbed = self.quantize(bottleneck)
@@ -327,10 +337,10 @@ class LocationScaleIndexedEntropyModel(ContinuousIndexedEntropyModel):
             range_coder_precision=range_coder_precision, bottleneck_dtype=bottleneck_dtype,
             prior_dtype=prior_dtype, laplace_tail_mass=laplace_tail_mass)
 
-    def forward(self, bottleneck, scale_indexes, loc=None, training=True):
+    def forward(self, bottleneck, scale_indexes, loc=None, training=True, noise=None):
         if loc is None:
-            return super().forward(bottleneck, scale_indexes, training=training)
-        perturbed, bits = super().forward(bottleneck - loc, scale_indexes, training=training)
+            return super().forward(bottleneck, scale_indexes, training=training, noise=noise)
+        perturbed, bits = super().forward(bottleneck - loc, scale_indexes, training=training, noise=noise)
         return perturbed + loc, bits
 
     def quantize(self, bottleneck, loc=None):

@@ -154,11 +154,20 @@ class GDN(CachedValues, torch.nn.Module):
         self.build(x.shape[-1], x.device)
         beta, gamma = self.beta.to(x.device), self.gamma.to(x.device)
         alpha, epsilon = self.alpha, self.epsilon
+        # The kernels take multiples of 32 channels.  Other widths (small test models) get zero channels up to the
+        # next one, with beta 1 and gamma 0 there: the real channels' sums gain exact zeros, the added outputs are 0
+        # and are sliced off.
+        channels = x.shape[-1]
+        pad = -channels % 32 if x.is_cuda else 0
+        if pad:
+            x = torch.nn.functional.pad(x, (0, pad))
+            beta = torch.cat([beta, beta.new_ones(pad)])
+            gamma = torch.nn.functional.pad(gamma, (0, pad, 0, pad))
         fast = (not torch.is_tensor(alpha) and not torch.is_tensor(epsilon)
                 and float(alpha) in (1.0, 2.0) and float(epsilon) in (1.0, 0.5))
         needs_grad = torch.is_grad_enabled() and any(
             torch.is_tensor(t) and t.requires_grad for t in (x, beta, gamma, alpha, epsilon))
-        if fast and not needs_grad and self._beta_fixed is None and self._gamma_fixed is None \
+        if fast and not needs_grad and not pad and self._beta_fixed is None and self._gamma_fixed is None \
                 and x.is_cuda and x.dtype in functional._DTYPE_CODE \
                 and (x.dtype != torch.float32 or x.shape[-1] <= 192):
             # inference on the layer's own variables: the kernels' parameter image is prepared once per
@@ -176,6 +185,8 @@ class GDN(CachedValues, torch.nn.Module):
         else:
             y = functional.gdn_forward(x.contiguous(), beta, gamma, self.inverse, self.rectify,
                                        float(alpha), float(epsilon))
+        if pad:
+            y = y[..., :channels]
         if self.data_format == "channels_first" and y.dim() > 2:
             y = y.movedim(-1, 1)
         return y

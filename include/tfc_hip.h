@@ -1015,6 +1015,54 @@ int tfc_scale_space_warp_backward(const float* g, const float* volume, const flo
  * shape fails the checks above. */
 int64_t tfc_scale_space_workspace(int64_t n, int64_t h, int64_t w, int channels, int num_levels);
 
+/* ------------------------------------------------------------------------ */
+/* Spatial context model (Minnen, Ballé, Toderici 2018)                     */
+/* ------------------------------------------------------------------------ */
+
+/* The autoregressive half of "Joint autoregressive and hierarchical priors for learned image compression" (NeurIPS
+ * 2018, section 2 and figure 2): the reference tree publishes that model's rate-distortion curves
+ * (results/image_compression) and lists its context-free variant (models/tfci.py, `mbt2018-mean`) but carries no
+ * program text for the context model, so the definition is this project's own.  With y [batch, Hl, Wl, M] the latent,
+ * psi [batch, Hl, Wl, P] the hyper-synthesis output, y_hat = 0 outside the latent, and positions taken in any order
+ * that puts (i - 2 .. i, all j) above and (i, < j) to the left first:
+ *   ctx[i, j]  = bc + sum over the 12 causal taps (di < 0, or di == 0 and dj < 0; |di|, |dj| <= 2)
+ *                of y_hat[i + di, j + dj] . Wc[di + 2, dj + 2]                                   M -> 2M
+ *   h1 = lrelu(b1 + [ctx, psi] W1)   h2 = lrelu(b2 + h1 W2)   out = b3 + h2 W3                   lrelu slope 0.2
+ *   mu = out[:M]     index_float = out[M:]     idx = tfc_index_prepare(index_float, num_scales)
+ *   sym = int32(rint(y - mu))  (half to even)        y_hat = float32(sym) + mu
+ * all float32.  Each dot product is summed in four partial sums (k mod 4, k ascending inside a tap, taps in
+ * row-major order) combined as (s0 + s1) + (s2 + s3) and added to the bias; both entry points run the same device
+ * function, so the decoder's y_hat equals the encoder's bit for bit on the same build and device kind.
+ * `packed` DEV float32 [packed_floats], 16-byte aligned: the weights in the layout of csrc/context_params.h
+ * (ctx_layout; the mask already applied).  `workspace` DEV, 16-byte aligned, tfc_context_workspace bytes.
+ * Checked on the host before any launch: sizes (M, P, H1, H2 in [1, 65536] and one position's activations within
+ * 60 KiB of LDS), Hl, Wl in [1, 2^24], batch Hl Wl <= 2^40, num_scales, packed_floats, null pointers, alignment.
+ * batch == 0 launches nothing. */
+
+/* Bytes of the workspace of the two calls below (the hyperprior half of the first layer for every position and one
+ * decoder state per row); -1 (and tfc_last_error) when the sizes fail the checks.  Replaces nothing: TensorFlow's
+ * allocator owns an op's scratch memory. */
+int64_t tfc_context_workspace(int64_t batch, int64_t hl, int64_t wl, int m, int p, int h1, int h2);
+/* The encoder side and the evaluation: every output is [batch, Hl, Wl, M].  ONE launch, one workgroup per image;
+ * position (i, j) is of wavefront step j + 3 i, a step's positions go through the network together.  Replaces a host
+ * loop over the Hl Wl positions of a masked convolution (python/layers/signal_conv.py:663-690 with a masked kernel),
+ * three 1x1 convolutions and tf.round per position. */
+int tfc_context_scan(const float* y, const float* psi, const float* packed, int64_t packed_floats, int64_t batch,
+                     int64_t hl, int64_t wl, int m, int p, int h1, int h2, int num_scales, void* workspace,
+                     int32_t* sym, int32_t* idx, float* mu, float* index_float, float* y_hat, void* stream);
+/* The decoder side: blob / offsets DEV describe batch * Hl strings as tfc_decoder_create takes them with
+ * src_on_device = 1 (row i of image b is string b * Hl + i, coded in raster order along the row, channels
+ * innermost: what tfc_encoder_encode_quantized_indexed writes for [batch, Hl] streams of Wl * M elements, escapes
+ * included); cdf_offset DEV int32 [num_scales].  y_hat = float32(symbol + cdf_offset[idx]) + mu.  ok DEV uint8
+ * [batch * Hl]: EntropyDecodeFinalize's check per string (tfc_decoder_finalize_device).  ONE launch: the network and
+ * the range decoder alternate inside it.  Replaces a host loop of the same network and one EntropyDecodeIndex call
+ * (cc/kernels/range_coder_kernels.cc:360-429) per position.  Damaged strings end the call like intact ones (reads
+ * past a string's end yield zeros, an escape's unary part is bounded) and show in `ok`. */
+int tfc_context_decode(const tfc_tables* tables, const uint8_t* blob, const int64_t* offsets, const float* psi,
+                       const float* packed, int64_t packed_floats, const int32_t* cdf_offset, int64_t batch,
+                       int64_t hl, int64_t wl, int m, int p, int h1, int h2, int num_scales, void* workspace,
+                       float* y_hat, uint8_t* ok, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
