@@ -1576,6 +1576,15 @@ extern "C" int tfc_debug_pipe_clocks(unsigned long long* out8) {
   TFC_HIP(hipMemcpyFromSymbol(out8, HIP_SYMBOL(tfc::g_pipe_clock), 8 * sizeof(unsigned long long)));
   return 0;
 }
+extern "C" int tfc_debug_pipe_window(int64_t* phases, int64_t* refills, int64_t* index_refills) {
+  unsigned long long v[3] = {0, 0, 0};
+  TFC_HIP(hipDeviceSynchronize());
+  TFC_HIP(hipMemcpyFromSymbol(v, HIP_SYMBOL(tfc::g_pipe_window), sizeof(v)));
+  if (phases) *phases = static_cast<int64_t>(v[0]);
+  if (refills) *refills = static_cast<int64_t>(v[1]);
+  if (index_refills) *index_refills = static_cast<int64_t>(v[2]);
+  return 0;
+}
 extern "C" int tfc_debug_enc_clocks(unsigned long long* out4) {
   TFC_HIP(hipDeviceSynchronize());
   TFC_HIP(hipMemcpyFromSymbol(out4, HIP_SYMBOL(tfc::g_enc_clock), 4 * sizeof(unsigned long long)));

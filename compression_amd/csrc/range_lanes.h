@@ -66,6 +66,9 @@ __device__ unsigned long long g_pipe_fallback_blocks;
 // (measurement aid, tools/chain_clock_probe.py) core-clock cycles and 100 MHz ticks the first chain workgroup of the
 // last pipelined encode / decode launch ran for: the clock the chain ran at
 __device__ unsigned long long g_pipe_clock[8];
+// the first chain wave of the last pipelined decode launch: memory phases, phases that requested the code window, phases
+// that requested the window of row addresses (index mode) — tfc_debug_pipe_window
+__device__ unsigned long long g_pipe_window[3];
 // (TFC_PIPE_TIMING builds) the encoder chain's hand-scheduled blocks: cycles inside them, their number, blocks repeated
 // call by call, cycles of those repetitions
 __device__ unsigned long long g_enc_clock[4];
@@ -213,35 +216,41 @@ struct LaneWindow {
       if (q0 + k < len) word |= static_cast<unsigned int>(lanes_gload8(g + q0 + k)) << (8u * k);
     return word;
   }
-  __device__ void request(unsigned int pos) {
-    pbase = pos;
+  // (the words of a request in the caller's own registers: a caller that parks them inside the iteration that requested
+  // them keeps them out of its loop-carried state)
+  __device__ void request(unsigned int pos, uint2 (&words)[WORDS]) const {
     if (pos + 8u * WORDS <= len) {
 #pragma unroll
       for (int w = 0; w < WORDS; w += 2) {
 #if defined(TFC_PDEC_ABL) && (TFC_PDEC_ABL & 2)
         // (timing experiment, results wrong: one 16-byte load per request instead of WORDS / 2)
-        const uint4 v = w == 0 ? lanes_gload16(g + pos) : make_uint4(pend[0].x, pend[0].y, pend[1].x, pend[1].y);
+        const uint4 v = w == 0 ? lanes_gload16(g + pos) : make_uint4(words[0].x, words[0].y, words[1].x, words[1].y);
 #else
         const uint4 v = lanes_gload16(g + pos + 8u * w);
 #endif
-        pend[w] = make_uint2(v.x, v.y);
-        pend[w + 1] = make_uint2(v.z, v.w);
+        words[w] = make_uint2(v.x, v.y);
+        words[w + 1] = make_uint2(v.z, v.w);
       }
     } else {
       // the stream ends inside the window (its last phases only): byte by byte, zero behind the end
-      // (the word loops are unrolled so that `pend` stays in registers)
+      // (the word loops are unrolled so that `words` stays in registers)
 #pragma unroll
       for (int w = 0; w < WORDS; ++w) {
-        pend[w].x = tail_word(pos + 8u * w);
-        pend[w].y = tail_word(pos + 8u * w + 4u);
+        words[w].x = tail_word(pos + 8u * w);
+        words[w].y = tail_word(pos + 8u * w + 4u);
       }
     }
   }
-  __device__ void commit() {
+  __device__ void commit(unsigned int pos, const uint2 (&words)[WORDS]) {
 #pragma unroll
-    for (int w = 0; w < WORDS; ++w) reinterpret_cast<uint2*>(lds)[w] = pend[w];
-    base = pbase;
+    for (int w = 0; w < WORDS; ++w) reinterpret_cast<uint2*>(lds)[w] = words[w];
+    base = pos;
   }
+  __device__ void request(unsigned int pos) {
+    pbase = pos;
+    request(pos, pend);
+  }
+  __device__ void commit() { commit(pbase, pend); }
 };
 
 // byte stride between the staging areas of neighbouring lanes: payload rounded up to 8, plus 8 when that

@@ -1139,10 +1139,14 @@ __global__ void __launch_bounds__(256) dec_rows_kernel(const PipeRowJobs jobs, u
 }
 
 // LDS of one decoder wave behind the tables' image: per lane a code-byte window and (index mode) a window of
-// row addresses, two blocks' worth each (a step consumes at most one 16-bit digit and one element)
+// row addresses (a step consumes at most one 16-bit digit and one element)
 struct PipeDecLds {
-  // (two blocks of 2-byte entries and the one entry a step requests ahead, in whole 16-byte loads)
-  static constexpr int kWords = 2 * kPipeBlock * 2 / 8 + 2;
+  // Two blocks of 2-byte entries and the one entry a step requests ahead (66 bytes: what a memory phase that requests
+  // nothing needs in front of it, dec_chain_kernel) and 30 bytes a lane may be into its window and still skip — 96 bytes in
+  // whole 16-byte loads.  Measured on the headline (20 batches of config 2, 4.07 bits per symbol): 80 bytes request at
+  // 0.62 of the phases, 96 at 0.29, and the launch group is 1.2 % faster for it (profiles/window_refill.md); 104 bytes have
+  // the same lane stride, 112 no longer fit config 2's full image.
+  static constexpr int kWords = 2 * kPipeBlock * 2 / 8 + 4;
   static constexpr int kStride = lane_stride(8 * kWords);
   static constexpr int kCodes = 0;
   static constexpr int kRows = kCodes + 64 * kStride;
@@ -1691,23 +1695,51 @@ __global__ void __launch_bounds__(512) dec_chain_kernel(const PipeDecJobs jobs, 
   // (measurement aid, tools/chain_clock_probe.py: cycles inside the hand-scheduled blocks / their number)
   unsigned long long t_asm = 0ull, n_asm = 0ull, t_commit = 0ull, t_rest = 0ull;
 #endif
-  // memory phase of a block: park the windows requested at the previous phase, send the previous block's raw rows off,
-  // request the windows from the current positions
-  auto memory_phase = [&]() __attribute__((always_inline)) {
+  // Code window (and, index mode, the window of row addresses): refilled only when a lane runs low.  One parked window
+  // of W = 8 * kWords bytes per lane, `base` the stream position of its first byte, o = position - base.  Invariant:
+  //  * between two memory phases every path — a hand-scheduled block, its step-by-step repeat, sixteen generic steps, the
+  //    block that finishes an escape code — consumes at most 2 * kPipeBlock = 32 bytes per lane and reads at most 2 bytes
+  //    ahead of what it consumes (the digit / row address a step requests before it knows whether it needs it);
+  //  * a phase that SKIPS the request needs its own block (32 bytes) and the next block's reads (34) inside the parked
+  //    window — a window requested at the next phase is parked behind that phase's block, usable from the one after:
+  //    o + 66 <= W;
+  //  * a phase that requests needs its own block's reads inside the parked window, o + 34 <= W: the phase before either
+  //    skipped (o was 32 smaller at most, + 66) or requested at its own position (o <= 32 now, 66 <= W).
+  // The decision is the wave's (every lane, also those without a stream: they decode zeros from their own windows), the
+  // flags are scalars.  Order of events: request -> block (and its repeat) -> park.  The requested words are locals of
+  // the iteration (WindowRefill): they die inside it — no copy and no wait for them on the back edge — and the park
+  // still follows every read of the old window and precedes the next flush and request.
+  static_assert(8 * L::kWords >= 4 * kPipeBlock + 2, "a window holds two blocks and the entry read ahead");
+  constexpr unsigned int kWindowNeed = 4u * kPipeBlock + 2u;      // 66
+  struct WindowRefill {
+    uint2 code[L::kWords], rows[L::kWords];
+    unsigned int code_pos, rows_pos;
+    bool code_pending, rows_pending;                              // wave-uniform
+  };
+  unsigned int n_phase = 0u, n_refill = 0u, n_irefill = 0u;       // tfc_debug_pipe_window
+  auto park = [&](const WindowRefill& rq) __attribute__((always_inline)) {
 #if TFC_PIPE_TIMING
     const unsigned long long tm0 = clock64();
 #endif
-    const unsigned int cpos = cw.base + (cp - cw_off);
-    cw.commit();
-    cp = cw_off + (cpos - cw.base);
-    if (INDEXED) {
-      iw.commit();
+    if (rq.code_pending) {
+      const unsigned int cpos = cw.base + (cp - cw_off);
+      cw.commit(rq.code_pos, rq.code);
+      cp = cw_off + (cpos - cw.base);
+    }
+    if (INDEXED && rq.rows_pending) {
+      iw.commit(rq.rows_pos, rq.rows);
       pw = iw_off + (2u * pos - iw.base);
     }
 #if TFC_PIPE_TIMING
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    t_commit += clock64() - tm0;
+#endif
+  };
+  // memory phase of a block, first half: send the previous block's raw rows off, decide — THE rule, its one copy —
+  // which windows the wave requests from the current positions
+  auto phase_decide = [&](WindowRefill& rq) __attribute__((always_inline)) {
+#if TFC_PIPE_TIMING
     const unsigned long long tm1 = clock64();
-    t_commit += tm1 - tm0;
 #endif
     flush();
     if (k != 0u && (k / kPipeBlock) % kPipeRelease == 0u) {
@@ -1717,13 +1749,47 @@ __global__ void __launch_bounds__(512) dec_chain_kernel(const PipeDecJobs jobs, 
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
       if (lane == 0u) __hip_atomic_store(&pa.progress[gi], k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    cw.request(cpos);
-    if (INDEXED) iw.request(2u * pos);
     // elements STARTED before row k (an escape code in progress has its first row behind us)
     posrec[static_cast<size_t>(k / kPipeBlock) * 64] = pos + (M != 0 ? 1u : 0u);
+    ++n_phase;
+    rq.code_pos = cw.base + (cp - cw_off);
+    rq.code_pending = !__all((cp - cw_off) + kWindowNeed <= 8u * L::kWords);
+    rq.rows_pos = 2u * pos;
+    rq.rows_pending = INDEXED && !__all((rq.rows_pos - iw.base) + kWindowNeed <= 8u * L::kWords);
+    n_refill += rq.code_pending ? 1u : 0u;
+    n_irefill += rq.rows_pending ? 1u : 0u;
 #if TFC_PIPE_TIMING
     t_rest += clock64() - tm1;
 #endif
+  };
+  // ... second half: the requests; park(rq) follows the block.  (The words of a window that is not requested are defined
+  // by an empty statement: left undefined, the compiler kept the previous iteration's words for them — twenty registers
+  // carried and copied round the loop, and a wait for the loads on its back edge.)
+  auto phase_request = [&](WindowRefill& rq) __attribute__((always_inline)) {
+#if TFC_PIPE_TIMING
+    const unsigned long long tm1 = clock64();
+#endif
+    if (rq.code_pending) {
+      cw.request(rq.code_pos, rq.code);
+    } else {
+#pragma unroll
+      for (int w = 0; w < L::kWords; ++w) asm("" : "=v"(rq.code[w].x), "=v"(rq.code[w].y));
+    }
+    if (INDEXED) {
+      if (rq.rows_pending) {
+        iw.request(rq.rows_pos, rq.rows);
+      } else {
+#pragma unroll
+        for (int w = 0; w < L::kWords; ++w) asm("" : "=v"(rq.rows[w].x), "=v"(rq.rows[w].y));
+      }
+    }
+#if TFC_PIPE_TIMING
+    t_rest += clock64() - tm1;
+#endif
+  };
+  auto memory_phase = [&](WindowRefill& rq) __attribute__((always_inline)) {
+    phase_decide(rq);
+    phase_request(rq);
   };
   // kPipeBlock hand-scheduled steps of the lanes in EXEC
   auto fast_block = [&](unsigned int& flag) __attribute__((always_inline)) {
@@ -1759,6 +1825,9 @@ __global__ void __launch_bounds__(512) dec_chain_kernel(const PipeDecJobs jobs, 
     }
 #undef TFC_PDEC_OPERANDS
   };
+  // the windows requested in front of the set-up above: parked once, nothing is pending when a memory phase begins
+  cw.commit();
+  if (INDEXED) iw.commit();
   bool gave_up = false;
   while (__any(pos < elems)) {
     // Steady state — every stream of the wave has a whole block of elements left — as a loop of its own: a memory
@@ -1770,44 +1839,53 @@ __global__ void __launch_bounds__(512) dec_chain_kernel(const PipeDecJobs jobs, 
     if (lds0 == 0u && row_loaded && (INDEXED || static_cast<unsigned int>(la.ntab) >= kPipeBlock)) {
       // (M > -16: a lane's unary prefix cannot reach its 31st zero — where the reference stops counting — inside a block)
       while (__all(!live || (pos + kPipeBlock <= elems && M > -16)) && k + kPipeBlock <= static_cast<unsigned int>(pa.rows)) {
-        memory_phase();
-        const unsigned int D0 = D, s10 = s1, cp0 = cp, pw0 = pw;
-        const int M0 = M;
-        const uint4 R0 = R;
-        unsigned int flag = 0u;
-        // (every lane, also those of a last group that have no stream — they decode zeros from their own windows and
-        // are ignored: under `if (live)` the compiler copied the block's nine operands twice)
-        fast_block(flag);
-        if (__builtin_expect(__any(live && flag != 0u), 0)) {
-          // A verification failed somewhere in the block (the quotient estimate one off: ~1e-5 of the symbols, 2.5 % of the
-          // blocks): again from the saved state, one hand-scheduled step at a time, and only the step that fails again
-          // takes the generic path (16 generic steps are ~20 000 cycles; this is ~7 000).
-          D = D0; s1 = s10; cp = cp0; pw = pw0; M = M0; R = R0;
-#pragma nounroll
-          for (unsigned int i = 0; i < kPipeBlock; ++i) {
-            const unsigned int D1 = D, s11 = s1, cp1 = cp, pw1 = pw;
-            const int M1 = M;
-            const uint4 R1 = R;
-            unsigned int f1 = 0u;
-            if (live) fast_step(f1, i);
-            if (__any(live && f1 != 0u)) {
-              D = D1; s1 = s11; cp = cp1; pw = pw1; M = M1; R = R1;
-              gstep(live, k + i, true);
-            } else {
-              pos += (pw - pw1) / (INDEXED ? 2u : 16u);
-              if (!INDEXED) pw -= pw >= dir_end ? dir_end : 0u;
+        WindowRefill rq;
+        phase_decide(rq);
+        auto block = [&]() __attribute__((always_inline)) {
+          const unsigned int D0 = D, s10 = s1, cp0 = cp, pw0 = pw;
+          const int M0 = M;
+          const uint4 R0 = R;
+          unsigned int flag = 0u;
+          // (every lane, also those of a last group that have no stream — they decode zeros from their own windows and
+          // are ignored: under `if (live)` the compiler copied the block's nine operands twice)
+          fast_block(flag);
+          if (__builtin_expect(__any(live && flag != 0u), 0)) {
+            // A verification failed somewhere in the block (the quotient estimate one off: ~1e-5 of the symbols, 2.5 % of the
+            // blocks): again from the saved state, one hand-scheduled step at a time, and only the step that fails again
+            // takes the generic path (16 generic steps are ~20 000 cycles; this is ~7 000).
+            D = D0; s1 = s10; cp = cp0; pw = pw0; M = M0; R = R0;
+  #pragma nounroll
+            for (unsigned int i = 0; i < kPipeBlock; ++i) {
+              const unsigned int D1 = D, s11 = s1, cp1 = cp, pw1 = pw;
+              const int M1 = M;
+              const uint4 R1 = R;
+              unsigned int f1 = 0u;
+              if (live) fast_step(f1, i);
+              if (__any(live && f1 != 0u)) {
+                D = D1; s1 = s11; cp = cp1; pw = pw1; M = M1; R = R1;
+                gstep(live, k + i, true);
+              } else {
+                pos += (pw - pw1) / (INDEXED ? 2u : 16u);
+                if (!INDEXED) pw -= pw >= dir_end ? dir_end : 0u;
+              }
             }
+          } else {
+            pos += (pw - pw0) / (INDEXED ? 2u : 16u);
+            if (!INDEXED) pw -= pw >= dir_end ? dir_end : 0u;      // (a block is at most one turn of the directory: ntab >= kPipeBlock)
           }
           staged = true;
           staged_k = k;
           k += kPipeBlock;
-          continue;
+        };
+        // (two copies of the block: in the one behind a request the words are plain values from the loads to the park, in
+        // the other there are none — one copy made them a merge of "loaded" and "nothing" that lived round the loop)
+        if (rq.code_pending || rq.rows_pending) {
+          phase_request(rq);
+          block();
+          park(rq);                  // behind every read of the old window: the requested words do not cross the back edge
+        } else {
+          block();
         }
-        pos += (pw - pw0) / (INDEXED ? 2u : 16u);
-        if (!INDEXED) pw -= pw >= dir_end ? dir_end : 0u;      // (a block is at most one turn of the directory: ntab >= kPipeBlock)
-        staged = true;
-        staged_k = k;
-        k += kPipeBlock;
       }
       if (!__any(pos < elems)) break;
     }
@@ -1815,7 +1893,8 @@ __global__ void __launch_bounds__(512) dec_chain_kernel(const PipeDecJobs jobs, 
       gave_up = true;                // more rows than planned for (escape codes far beyond the tables' tail mass)
       break;
     }
-    memory_phase();
+    WindowRefill rq;
+    memory_phase(rq);
     if (!row_loaded) {
       if (M == 0) load_row(); else R = bin;
       row_loaded = true;
@@ -1832,6 +1911,7 @@ __global__ void __launch_bounds__(512) dec_chain_kernel(const PipeDecJobs jobs, 
 #pragma nounroll
       for (unsigned int i = 0; i < kPipeBlock; ++i) gstep(!whole && pos < elems && M != 0, k + i);
       k += kPipeBlock;
+      park(rq);
       continue;
     }
     const bool busy = blocks ? whole : pos < elems;
@@ -1860,6 +1940,7 @@ __global__ void __launch_bounds__(512) dec_chain_kernel(const PipeDecJobs jobs, 
         staged = true;
         staged_k = k;
         k += kPipeBlock;
+        park(rq);
         continue;
       }
       D = D0; s1 = s10; cp = cp0; pw = pw0; M = M0; R = R0;      // an exception somewhere in the wave: the generic steps
@@ -1872,6 +1953,7 @@ __global__ void __launch_bounds__(512) dec_chain_kernel(const PipeDecJobs jobs, 
 #pragma nounroll
     for (unsigned int i = 0; i < kPipeBlock; ++i) gstep(busy && pos < elems, k + i);
     k += kPipeBlock;
+    park(rq);
   }
   flush();
   posrec[static_cast<size_t>(k / kPipeBlock) * 64] = pos;
@@ -1888,6 +1970,9 @@ __global__ void __launch_bounds__(512) dec_chain_kernel(const PipeDecJobs jobs, 
   if (gi == 0 && lane == 0) {
     g_pipe_clock[2] = clock64() - clk0;
     g_pipe_clock[3] = wall_clock64() - wall0;
+    g_pipe_window[0] = n_phase;
+    g_pipe_window[1] = n_refill;
+    g_pipe_window[2] = n_irefill;
 #if TFC_PIPE_TIMING
     g_pipe_clock[5] = t_asm | (t_commit << 32);
     g_pipe_clock[7] = n_asm | (static_cast<unsigned long long>(k) << 16) | (t_rest << 32);

@@ -48,6 +48,11 @@ int tfc_profile_query(const char* kernel, double* total_ms, int64_t* launches);
  * kernels (csrc/range_pipe.h) since the library was loaded, and workgroups of the lane-per-stream kernels that
  * ran behind them as the fallback for a job they gave up on (synchronises the device).  Either may be null. */
 int tfc_pipe_counters(int64_t* launches, int64_t* fallback_blocks);
+/* Diagnostics of the pipelined decoder's chain kernel (csrc/range_pipe.h), first chain wave (streams 0 ... 63) of the
+ * last decode launch: its memory phases (one per 16-row block), the phases that requested a new code window, and (index
+ * mode) those that requested a new window of row addresses — a window is refilled only when a lane of the wave runs low.
+ * Synchronises the device.  Any pointer may be null. */
+int tfc_debug_pipe_window(int64_t* phases, int64_t* refills, int64_t* index_refills);
 /* A/B and test switch of the pipelined decoder (csrc/range_pipe.h): which table image its chain kernel runs on —
  * 0 by launch (the full image where it fits a CU and the launch's chain waves all find one, else the compact image),
  * 1 the full image (one bit per quotient value), 2 the compact image (every second bound at pair resolution: half the
