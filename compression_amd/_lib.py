@@ -7,6 +7,9 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
+
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtfc_hip.so")
@@ -169,6 +172,10 @@ SIGNATURES = {
                                   _vp, _vp, _vp, _vp]),
 }
 
+# the dtype argument of the C ABI: entries on float32 / bfloat16 tensors, and those that take float16 as well
+DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1}
+DTYPE_CODE_F16 = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+
 ABI_VERSION = 2          # include/tfc_hip.h TFC_ABI_VERSION this binding was written against
 
 _lib = None
@@ -216,8 +223,6 @@ def check(rc: int) -> None:
 
 
 def require_device():
-    import torch
-
     if not torch.cuda.is_available():
         raise RuntimeError(
             "compression_amd needs a HIP device (MI355X): torch.cuda.is_available() is False "
@@ -226,6 +231,21 @@ def require_device():
 
 
 def stream_ptr() -> int:
-    import torch
-
     return torch.cuda.current_stream().cuda_stream
+
+
+def ptr(t):
+    """A tensor's address as a pointer argument; None (NULL) for None."""
+    return None if t is None else t.data_ptr()
+
+
+def kernel_constants(header_name, prefixes):
+    """The named `constexpr int` constants of csrc/<header_name> whose names start with one of `prefixes`, read from that
+    file: what a binding has to know of its kernels' tile sizes and argument limits."""
+    path = os.path.join(_HERE, "csrc", header_name)
+    with open(path) as f:
+        found = re.findall(r"constexpr\s+int\s+((?:%s)_[A-Z0-9_]+)\s*=\s*(\d+)\s*;" % "|".join(prefixes), f.read())
+    if not found:
+        raise RuntimeError(f"no constants found in {path}")
+    return {name: int(value) for name, value in found}
+

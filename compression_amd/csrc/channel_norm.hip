@@ -42,15 +42,12 @@
 #include <initializer_list>
 
 #include "../../include/tfc_hip.h"
+#include "bf16_io.h"
 #include "common.h"
 #include "unit_sum.h"
 
 namespace tfc {
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) unsigned int cn_u32x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 cn_bf16x2;
-typedef __attribute__((ext_vector_type(2))) float cn_f32x2;
 
 struct CnormParams {
   const void* x;
@@ -71,44 +68,6 @@ struct CnormParams {
   int relu;
   int nt;               // non-temporal stores
 };
-
-__device__ inline unsigned int cn_pack_bf16(float lo, float hi) {
-  return __builtin_bit_cast(unsigned int, __builtin_convertvector(cn_f32x2{lo, hi}, cn_bf16x2));
-}
-
-template <bool BF16>
-__device__ inline void cn_unpack(const cn_u32x4 raw, float* v) {
-  if (BF16) {
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      v[2 * w] = __uint_as_float(raw[w] << 16);
-      v[2 * w + 1] = __uint_as_float(raw[w] & 0xFFFF0000u);
-    }
-  } else {
-#pragma unroll
-    for (int w = 0; w < 4; ++w) v[w] = __uint_as_float(raw[w]);
-  }
-}
-
-template <bool BF16>
-__device__ inline cn_u32x4 cn_repack(const float* v) {
-  cn_u32x4 out;
-  if (BF16) {
-#pragma unroll
-    for (int w = 0; w < 4; ++w) out[w] = cn_pack_bf16(v[2 * w], v[2 * w + 1]);
-  } else {
-#pragma unroll
-    for (int w = 0; w < 4; ++w) out[w] = __float_as_uint(v[w]);
-  }
-  return out;
-}
-
-__device__ inline void cn_store(cn_u32x4* dst, cn_u32x4 v, int nt) {
-  // (by hand: with __builtin_nontemporal_store in one branch and a plain store in the other the optimiser merges the
-  // two into one plain store — csrc/gdn_common.h)
-  if (nt) asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(dst), "v"(v) : "memory");
-  else *dst = v;
-}
 
 // NG granules per lane; PAIR: a unit is two rows; BWD: dx and the parameter partials instead of y.
 template <int NG, bool BF16, bool PAIR, bool BWD>
@@ -159,16 +118,16 @@ __global__ void __launch_bounds__(256) cnorm_vec_kernel(CnormParams p) {
     for (int k = 0; k < NE; ++k) dgam[k] = dbet[k] = 0.f;
   }
 
-  const cn_u32x4* const xg = static_cast<const cn_u32x4*>(p.x);
-  auto fetch = [&](const cn_u32x4* base, long long step, cn_u32x4* raw) {
+  const u32x4* const xg = static_cast<const u32x4*>(p.x);
+  auto fetch = [&](const u32x4* base, long long step, u32x4* raw) {
     const long long u = step * rw + grp;
 #pragma unroll
     for (int j = 0; j < NG; ++j) {
-      raw[j] = cn_u32x4{0u, 0u, 0u, 0u};
+      raw[j] = u32x4{0u, 0u, 0u, 0u};
       if (on[j] && u < p.units) raw[j] = base[u * p.V + j * lpr + l];
     }
   };
-  cn_u32x4 xn[NG];
+  u32x4 xn[NG];
   if (wave < steps) fetch(xg, wave, xn);
 
   for (long long step = wave; step < steps; step += nwaves) {
@@ -176,10 +135,10 @@ __global__ void __launch_bounds__(256) cnorm_vec_kernel(CnormParams p) {
     const bool live = u < p.units;
     float v[NE];
 #pragma unroll
-    for (int j = 0; j < NG; ++j) cn_unpack<BF16>(xn[j], v + j * EPG);
-    cn_u32x4 extra[NG];                            // forward: the residual; backward: g
-    if (BWD) fetch(static_cast<const cn_u32x4*>(p.g), step, extra);
-    else if (p.res) fetch(static_cast<const cn_u32x4*>(p.res), step, extra);
+    for (int j = 0; j < NG; ++j) unpack<BF16>(xn[j], v + j * EPG);
+    u32x4 extra[NG];                            // forward: the residual; backward: g
+    if (BWD) fetch(static_cast<const u32x4*>(p.g), step, extra);
+    else if (p.res) fetch(static_cast<const u32x4*>(p.res), step, extra);
     if (step + nwaves < steps) fetch(xg, step + nwaves, xn);
 
     // mean (masked slots hold zeros)
@@ -218,7 +177,7 @@ __global__ void __launch_bounds__(256) cnorm_vec_kernel(CnormParams p) {
 #pragma unroll
       for (int j = 0; j < NG; ++j) {
         float r[EPG];
-        if (p.res) cn_unpack<BF16>(extra[j], r);
+        if (p.res) unpack<BF16>(extra[j], r);
 #pragma unroll
         for (int e = 0; e < EPG; ++e) {
           const bool r1 = e < HALF ? lo1[j] : hi1[j];
@@ -227,7 +186,7 @@ __global__ void __launch_bounds__(256) cnorm_vec_kernel(CnormParams p) {
           if (p.res) yv += r[e];
           v[j * EPG + e] = yv;
         }
-        if (on[j] && live) cn_store(static_cast<cn_u32x4*>(p.y) + u * p.V + j * lpr + l, cn_repack<BF16>(v + j * EPG), p.nt);
+        if (on[j] && live) store_granule(static_cast<u32x4*>(p.y) + u * p.V + j * lpr + l, repack<BF16>(v + j * EPG), p.nt);
       }
     } else {
       float gg[NE];
@@ -235,7 +194,7 @@ __global__ void __launch_bounds__(256) cnorm_vec_kernel(CnormParams p) {
 #pragma unroll
       for (int j = 0; j < NG; ++j) {
         float gv[EPG];
-        cn_unpack<BF16>(extra[j], gv);
+        unpack<BF16>(extra[j], gv);
 #pragma unroll
         for (int e = 0; e < EPG; ++e) {
           const int k = j * EPG + e;
@@ -270,7 +229,7 @@ __global__ void __launch_bounds__(256) cnorm_vec_kernel(CnormParams p) {
           const bool r1 = PAIR && (e < HALF ? lo1[j] : hi1[j]);
           v[k] = (r1 ? rstd1 : rstd0) * (gg[k] - (r1 ? a1 : a0) - v[k] * (r1 ? b1 : b0));
         }
-        if (on[j] && live) cn_store(static_cast<cn_u32x4*>(p.y) + u * p.V + j * lpr + l, cn_repack<BF16>(v + j * EPG), 0);
+        if (on[j] && live) store_granule(static_cast<u32x4*>(p.y) + u * p.V + j * lpr + l, repack<BF16>(v + j * EPG), 0);
       }
     }
   }
@@ -309,39 +268,31 @@ __global__ void __launch_bounds__(256) cnorm_row_kernel(CnormParams p) {
   const int lane = threadIdx.x & 63;
   const long long wave = static_cast<long long>(blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const long long nwaves = static_cast<long long>(gridDim.x) * (blockDim.x >> 6);
-  auto ld = [&](const void* base, long long at) -> float {
-    if (BF16) return __uint_as_float(static_cast<unsigned int>(static_cast<const unsigned short*>(base)[at]) << 16);
-    return static_cast<const float*>(base)[at];
-  };
-  auto st = [&](void* base, long long at, float v) {
-    if (BF16) static_cast<unsigned short*>(base)[at] = static_cast<unsigned short>(cn_pack_bf16(v, 0.f) & 0xFFFFu);
-    else static_cast<float*>(base)[at] = v;
-  };
   float* const mine = BWD ? p.part + (p.part0 + wave) * 2 * p.C : nullptr;
   for (long long r = wave; r < p.pixels; r += nwaves) {
     const long long at = (p.row0 + r) * p.C;
     float s = 0.f;
-    for (int c = lane; c < p.C; c += 64) s += ld(p.x, at + c);
+    for (int c = lane; c < p.C; c += 64) s += load<BF16>(p.x, at + c);
     const float mean = unit_sum(s, 6) / p.cf;
     float q = 0.f;
     for (int c = lane; c < p.C; c += 64) {
-      const float d = ld(p.x, at + c) - mean;
+      const float d = load<BF16>(p.x, at + c) - mean;
       q = fmaf(d, d, q);
     }
     const float rstd = __builtin_amdgcn_rsqf(unit_sum(q, 6) / p.cm1f + p.eps);
     if (!BWD) {
       for (int c = lane; c < p.C; c += 64) {
-        float yv = (ld(p.x, at + c) - mean) * rstd * (p.gamma ? p.gamma[c] : 1.f) + (p.beta ? p.beta[c] : 0.f);
+        float yv = (load<BF16>(p.x, at + c) - mean) * rstd * (p.gamma ? p.gamma[c] : 1.f) + (p.beta ? p.beta[c] : 0.f);
         if (p.relu) yv = fmaxf(yv, 0.f);
-        if (p.res) yv += ld(p.res, at + c);
-        st(p.y, at + c, yv);
+        if (p.res) yv += load<BF16>(p.res, at + c);
+        store<BF16>(p.y, at + c, yv);
       }
     } else {
       float a = 0.f, b = 0.f;
       for (int c = lane; c < p.C; c += 64) {
-        const float xh = (ld(p.x, at + c) - mean) * rstd;
+        const float xh = (load<BF16>(p.x, at + c) - mean) * rstd;
         const float gm = p.gamma ? p.gamma[c] : 1.f;
-        float gp = ld(p.g, at + c);
+        float gp = load<BF16>(p.g, at + c);
         if (p.relu) gp = xh * gm + (p.beta ? p.beta[c] : 0.f) > 0.f ? gp : 0.f;
         mine[c] = fmaf(gp, xh, mine[c]);
         mine[p.C + c] += gp;
@@ -351,11 +302,11 @@ __global__ void __launch_bounds__(256) cnorm_row_kernel(CnormParams p) {
       a = unit_sum(a, 6) / p.cf;
       b = unit_sum(b, 6) / p.cm1f;
       for (int c = lane; c < p.C; c += 64) {
-        const float xh = (ld(p.x, at + c) - mean) * rstd;
+        const float xh = (load<BF16>(p.x, at + c) - mean) * rstd;
         const float gm = p.gamma ? p.gamma[c] : 1.f;
-        float gp = ld(p.g, at + c);
+        float gp = load<BF16>(p.g, at + c);
         if (p.relu) gp = xh * gm + (p.beta ? p.beta[c] : 0.f) > 0.f ? gp : 0.f;
-        st(p.y, at + c, rstd * (gp * gm - a - xh * b));
+        store<BF16>(p.y, at + c, rstd * (gp * gm - a - xh * b));
       }
     }
   }
@@ -390,7 +341,7 @@ struct CnormPlan {
 // How the rows of [pixels, C] go onto waves (see the top of the file).
 CnormPlan cnorm_plan(int dtype, long long pixels, long long C, std::initializer_list<const void*> tensors) {
   CnormPlan plan;
-  const long long row_bytes = C * (dtype == 1 ? 2 : 4);
+  const long long row_bytes = C * dtype_bytes(dtype);
   bool aligned = true;
   for (const void* t : tensors) aligned = aligned && reinterpret_cast<uintptr_t>(t) % 16 == 0;
   if (!aligned || row_bytes % 8 != 0) return plan;
@@ -422,7 +373,7 @@ void cnorm_launch_vec(const CnormPlan& plan, int dtype, unsigned blocks, hipStre
 }
 
 int cnorm_validate(const char* name, int dtype, int64_t pixels, int64_t channels, float epsilon) {
-  if (dtype != 0 && dtype != 1) return fail("%s: dtype must be 0 (float32) or 1 (bfloat16)", name);
+  if (int rc = check_dtype(name, dtype)) return rc;
   if (pixels < 0) return fail("%s: pixels must be non-negative, got %lld", name, static_cast<long long>(pixels));
   if (channels < 2 || channels > (1 << 24))
     return fail("%s: channels must be at least 2 (the variance divides by channels - 1), got %lld", name,
@@ -458,7 +409,7 @@ extern "C" int tfc_channel_norm_forward(const void* x, const float* gamma, const
   // x + y beyond half the 256 MB Infinity Cache: y goes out non-temporal — the rule and the figure of the GDN
   // kernels (csrc/gdn_common.h, TFC_GDN_NT), inherited, not measured here.  TFC_CNORM_NT = 0 / 1: never / always.
   static const int nt_env = [] { const char* e = std::getenv("TFC_CNORM_NT"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
-  const long long bytes = pixels * channels * (dtype == 1 ? 2 : 4);
+  const long long bytes = pixels * channels * dtype_bytes(dtype);
   p.nt = nt_env >= 0 ? nt_env : (2 * bytes > (128ll << 20) ? 1 : 0);
   const CnormPlan plan = cnorm_plan(dtype, pixels, channels, {x, y, residual, gamma, beta});
   KernelTimer timer("channel_norm_forward", st);

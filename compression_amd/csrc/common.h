@@ -273,4 +273,10 @@ bool chip_shared();
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// The dtype code of the entries that take float32 or bfloat16 tensors: 0 = float32, 1 = bfloat16.
+inline int check_dtype(const char* name, int dtype) {
+  return dtype == 0 || dtype == 1 ? 0 : fail("%s: dtype must be 0 (float32) or 1 (bfloat16)", name);
+}
+inline int dtype_bytes(int dtype) { return dtype == 1 ? 2 : 4; }
+
 }  // namespace tfc

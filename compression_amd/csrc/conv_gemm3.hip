@@ -318,10 +318,8 @@ __global__ void __launch_bounds__(256, 1) conv3_bf16_kernel(const __bf16* x, con
         const int e = 4 * (q0 + half);
 #pragma unroll
         for (int p = 0; p < MT; ++p) {
-          xb[p][s][2 * half] = __builtin_bit_cast(unsigned int, __builtin_convertvector(
-                                   f32x2{acc[p][t0][e] + b4[0], acc[p][t0][e + 1] + b4[1]}, bf16x2));
-          xb[p][s][2 * half + 1] = __builtin_bit_cast(unsigned int, __builtin_convertvector(
-                                       f32x2{acc[p][t0][e + 2] + b4[2], acc[p][t0][e + 3] + b4[3]}, bf16x2));
+          xb[p][s][2 * half] = pack_bf16(acc[p][t0][e] + b4[0], acc[p][t0][e + 1] + b4[1]);
+          xb[p][s][2 * half + 1] = pack_bf16(acc[p][t0][e + 2] + b4[2], acc[p][t0][e + 3] + b4[3]);
         }
       }
       __builtin_amdgcn_sched_barrier(0);      // (16 channels at a time: registers)
@@ -450,8 +448,8 @@ __global__ void __launch_bounds__(256, 1) conv3_bf16_kernel(const __bf16* x, con
                   float v[4];
 #pragma unroll
                   for (int r = 0; r < 4; ++r) v[r] = elem(p, t, 2 * qp + half, r, b4);
-                  o[2 * half] = __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{v[0], v[1]}, bf16x2));
-                  o[2 * half + 1] = __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{v[2], v[3]}, bf16x2));
+                  o[2 * half] = pack_bf16(v[0], v[1]);
+                  o[2 * half + 1] = pack_bf16(v[2], v[3]);
                 }
                 // the halves trade their inner words: this lane then holds channels 32 t + 16 qp + 8 h + {0 .. 7}
                 const auto s0 = __builtin_amdgcn_permlane32_swap(o.x, o.z, false, false);

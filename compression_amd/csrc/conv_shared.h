@@ -9,9 +9,9 @@
 #include <type_traits>
 
 #include "../../include/tfc_hip.h"
+#include "bf16_io.h"
 #include "common.h"
 #include "gdn_params.h"
-#include "mfma_types.h"
 
 namespace tfc {
 

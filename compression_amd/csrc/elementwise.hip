@@ -11,21 +11,16 @@
 #include <cstdint>
 
 #include "../../include/tfc_hip.h"
+#include "bf16_io.h"
 #include "common.h"
 
 namespace tfc {
-
-__device__ inline float bf16_bits_to_float(unsigned short b) { return __builtin_bit_cast(float, static_cast<unsigned int>(b) << 16); }
-__device__ inline unsigned short float_to_bf16_bits(float f) {
-  return __builtin_bit_cast(unsigned short, static_cast<__bf16>(f));       // round to nearest even
-}
 
 // A thread takes 16 consecutive elements (8 for the indexes): one 16-byte load on the narrow side, two 16-byte stores or
 // loads on the wide one — a wave instruction is 1 KB contiguous, whole lines.  (Round 6.  Before: four elements per thread,
 // one at a time — 1-, 2- and 4-byte accesses, 64 partial lines per store instruction: 1.5 TB/s of their bytes; the
 // arithmetic per element is unchanged.)  The last, partial group of a tensor and tensors whose base is not 16-byte aligned
 // go element by element.
-typedef __attribute__((ext_vector_type(4))) unsigned int ew_u32x4;
 
 template <bool BF>
 __device__ inline void image_to_unit_one(const uint8_t* x, void* y, long long i) {
@@ -39,24 +34,24 @@ __global__ void image_to_unit_kernel(const uint8_t* x, void* y, long long n, int
   const long long i = (blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x) * 16;
   if (i >= n) return;
   if (vec && i + 16 <= n) {
-    const ew_u32x4 in = *reinterpret_cast<const ew_u32x4*>(x + i);
+    const u32x4 in = *reinterpret_cast<const u32x4*>(x + i);
     float v[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) v[k] = static_cast<float>((in[k >> 2] >> (8 * (k & 3))) & 0xFFu) / 255.0f;
     if (BF) {
-      ew_u32x4 o[2];
+      u32x4 o[2];
 #pragma unroll
       for (int k = 0; k < 8; ++k)
         o[k >> 2][k & 3] = static_cast<unsigned int>(float_to_bf16_bits(v[2 * k])) |
                            (static_cast<unsigned int>(float_to_bf16_bits(v[2 * k + 1])) << 16);
-      ew_u32x4* const dst = reinterpret_cast<ew_u32x4*>(static_cast<unsigned short*>(y) + i);
+      u32x4* const dst = reinterpret_cast<u32x4*>(static_cast<unsigned short*>(y) + i);
       dst[0] = o[0];
       dst[1] = o[1];
     } else {
-      ew_u32x4* const dst = reinterpret_cast<ew_u32x4*>(static_cast<float*>(y) + i);
+      u32x4* const dst = reinterpret_cast<u32x4*>(static_cast<float*>(y) + i);
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        dst[q] = ew_u32x4{__float_as_uint(v[4 * q]), __float_as_uint(v[4 * q + 1]), __float_as_uint(v[4 * q + 2]), __float_as_uint(v[4 * q + 3])};
+        dst[q] = u32x4{__float_as_uint(v[4 * q]), __float_as_uint(v[4 * q + 1]), __float_as_uint(v[4 * q + 2]), __float_as_uint(v[4 * q + 3])};
     }
     return;
   }
@@ -77,27 +72,19 @@ __global__ void unit_to_image_kernel(const void* x, uint8_t* y, long long n, int
   if (vec && i + 16 <= n) {
     float v[16];
     if (BF) {
-      const ew_u32x4* const src = reinterpret_cast<const ew_u32x4*>(static_cast<const unsigned short*>(x) + i);
-      const ew_u32x4 in[2] = {src[0], src[1]};
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const unsigned int w = in[k >> 2][k & 3];
-        v[2 * k] = __uint_as_float(w << 16);
-        v[2 * k + 1] = __uint_as_float(w & 0xFFFF0000u);
-      }
+      const u32x4* const src = reinterpret_cast<const u32x4*>(static_cast<const unsigned short*>(x) + i);
+      const u32x4 in[2] = {src[0], src[1]};
+      unpack<true>(in[0], v);
+      unpack<true>(in[1], v + 8);
     } else {
-      const ew_u32x4* const src = reinterpret_cast<const ew_u32x4*>(static_cast<const float*>(x) + i);
+      const u32x4* const src = reinterpret_cast<const u32x4*>(static_cast<const float*>(x) + i);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const ew_u32x4 w = src[q];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[4 * q + e] = __uint_as_float(w[e]);
-      }
+      for (int q = 0; q < 4; ++q) unpack<false>(src[q], v + 4 * q);
     }
-    ew_u32x4 o = {0u, 0u, 0u, 0u};
+    u32x4 o = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int k = 0; k < 16; ++k) o[k >> 2] |= unit_to_image_value<BF>(v[k]) << (8 * (k & 3));
-    *reinterpret_cast<ew_u32x4*>(y + i) = o;
+    *reinterpret_cast<u32x4*>(y + i) = o;
     return;
   }
   for (int k = 0; k < 16 && i + k < n; ++k) {
@@ -117,25 +104,16 @@ __global__ void index_prepare_kernel(const void* idx, int32_t* out, long long n,
   if (vec && i + 8 <= n) {
     float v[8];
     if (BF) {
-      const ew_u32x4 in = *reinterpret_cast<const ew_u32x4*>(static_cast<const unsigned short*>(idx) + i);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        v[2 * k] = __uint_as_float(in[k] << 16);
-        v[2 * k + 1] = __uint_as_float(in[k] & 0xFFFF0000u);
-      }
+      unpack<true>(*reinterpret_cast<const u32x4*>(static_cast<const unsigned short*>(idx) + i), v);
     } else {
-      const ew_u32x4* const src = reinterpret_cast<const ew_u32x4*>(static_cast<const float*>(idx) + i);
+      const u32x4* const src = reinterpret_cast<const u32x4*>(static_cast<const float*>(idx) + i);
 #pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const ew_u32x4 w = src[q];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[4 * q + e] = __uint_as_float(w[e]);
-      }
+      for (int q = 0; q < 2; ++q) unpack<false>(src[q], v + 4 * q);
     }
-    ew_u32x4* const dst = reinterpret_cast<ew_u32x4*>(out + i);
+    u32x4* const dst = reinterpret_cast<u32x4*>(out + i);
 #pragma unroll
     for (int q = 0; q < 2; ++q)
-      dst[q] = ew_u32x4{static_cast<unsigned int>(index_prepare_value(v[4 * q], hi)), static_cast<unsigned int>(index_prepare_value(v[4 * q + 1], hi)),
+      dst[q] = u32x4{static_cast<unsigned int>(index_prepare_value(v[4 * q], hi)), static_cast<unsigned int>(index_prepare_value(v[4 * q + 1], hi)),
                         static_cast<unsigned int>(index_prepare_value(v[4 * q + 2], hi)), static_cast<unsigned int>(index_prepare_value(v[4 * q + 3], hi))};
     return;
   }
@@ -205,7 +183,7 @@ extern "C" int tfc_pad2d(const void* x, void* y, int elem_bytes, int64_t n, int6
 }
 
 extern "C" int tfc_image_to_unit(const void* x, void* y, int dtype, int64_t n, void* stream) {
-  if (dtype != 0 && dtype != 1) return tfc::fail("tfc_image_to_unit: dtype must be 0 (float32) or 1 (bfloat16)");
+  if (int rc = tfc::check_dtype("tfc_image_to_unit", dtype)) return rc;
   if (n <= 0) return 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned blocks = static_cast<unsigned>((n + 4095) / 4096);
@@ -218,7 +196,7 @@ extern "C" int tfc_image_to_unit(const void* x, void* y, int dtype, int64_t n, v
 }
 
 extern "C" int tfc_unit_to_image(const void* x, int dtype, void* y, int64_t n, void* stream) {
-  if (dtype != 0 && dtype != 1) return tfc::fail("tfc_unit_to_image: dtype must be 0 (float32) or 1 (bfloat16)");
+  if (int rc = tfc::check_dtype("tfc_unit_to_image", dtype)) return rc;
   if (n <= 0) return 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned blocks = static_cast<unsigned>((n + 4095) / 4096);
@@ -231,7 +209,7 @@ extern "C" int tfc_unit_to_image(const void* x, int dtype, void* y, int64_t n, v
 }
 
 extern "C" int tfc_index_prepare(const void* indexes, int dtype, int32_t* out, int64_t n, int num_tables, void* stream) {
-  if (dtype != 0 && dtype != 1) return tfc::fail("tfc_index_prepare: dtype must be 0 (float32) or 1 (bfloat16)");
+  if (int rc = tfc::check_dtype("tfc_index_prepare", dtype)) return rc;
   if (num_tables < 1) return tfc::fail("tfc_index_prepare: num_tables must be positive");
   if (n <= 0) return 0;
   hipStream_t st = static_cast<hipStream_t>(stream);

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/tfc_hip.h"
+#include "bf16_io.h"
 #include "common.h"
 #include "laplace_tail.h"
 #include "reduce_rows.h"
@@ -90,17 +91,6 @@ __device__ inline float log_interval(float upper, float lower) {
   const float big = right ? log_sigmoid(-lower) : log_sigmoid(upper);
   const float small = right ? log_sigmoid(-upper) : log_sigmoid(lower);
   return fast_log1p(-__expf(small - big)) + big;
-}
-
-template <typename T> __device__ inline float load_as_float(const T* p, long long i);
-template <> __device__ inline float load_as_float<float>(const float* p, long long i) { return p[i]; }
-template <> __device__ inline float load_as_float<__hip_bfloat16>(const __hip_bfloat16* p, long long i) {
-  return __bfloat162float(p[i]);
-}
-template <typename T> __device__ inline void store_from_float(T* p, long long i, float v);
-template <> __device__ inline void store_from_float<float>(float* p, long long i, float v) { p[i] = v; }
-template <> __device__ inline void store_from_float<__hip_bfloat16>(__hip_bfloat16* p, long long i, float v) {
-  p[i] = __float2bfloat16(v);
 }
 
 struct BitsParams {
@@ -378,7 +368,7 @@ int run_backward(BitsParams p, float* dparams, hipStream_t st) {
 
 template <typename F32, typename BF16>
 int dispatch(int dtype, int layers, int width, const char* who, F32 f32, BF16 bf16) {
-  if (dtype != 0 && dtype != 1) return fail("%s: dtype must be 0 (float32) or 1 (bfloat16)", who);
+  if (int rc = check_dtype(who, dtype)) return rc;
   if (!((layers == 3 || layers == 4) && width == 3) && !(layers == 3 && width == 5))
     return fail("%s: built for num_filters (3, 3), (3, 3, 3) and (5, 5) (got %d layers of width %d)", who,
                 layers, width);

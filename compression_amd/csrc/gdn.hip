@@ -10,7 +10,7 @@ int gdn_forward_any(const void* x, void* y, int dtype, int64_t pixels, int64_t c
                     const float* gamma, int inverse, int rectify, int alpha_mode, int eps_mode, bool general,
                     float alpha, float epsilon, void* stream, const tfc_gdn_params* prepared = nullptr) {
   using namespace tfc;
-  if (dtype != 0 && dtype != 1) return fail("tfc_gdn_forward: dtype must be 0 (float32) or 1 (bfloat16)");
+  if (int rc = check_dtype("tfc_gdn_forward", dtype)) return rc;
   if (!general) {
     if (alpha_mode != 1 && alpha_mode != 2) return fail("tfc_gdn_forward: alpha must be 1 or 2");
     if (eps_mode != 0 && eps_mode != 1) return fail("tfc_gdn_forward: epsilon must be 1 or 0.5");
@@ -73,7 +73,7 @@ extern "C" int tfc_gdn_params_create(const float* beta, const float* gamma, int6
                                      void* stream, tfc_gdn_params** out) {
   using namespace tfc;
   *out = nullptr;
-  if (dtype != 0 && dtype != 1) return fail("tfc_gdn_params_create: dtype must be 0 (float32) or 1 (bfloat16)");
+  if (int rc = check_dtype("tfc_gdn_params_create", dtype)) return rc;
   if (channels <= 0 || channels % 32 != 0 || channels > 256 || (dtype == 0 && channels > 192))
     return fail("tfc_gdn_params_create: channels must be a multiple of 32, at most 256 (192 for float32), got %lld",
                 static_cast<long long>(channels));

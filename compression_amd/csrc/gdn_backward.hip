@@ -681,7 +681,7 @@ int launch_gdn_bwd_fused(GdnParams p, hipStream_t st) {
 template <int KT>
 int run_gdn_backward(GdnParams p, const void* g, void* dx, int dtype, float* dbeta, float* dgamma,
                      hipStream_t st) {
-  const size_t bytes = static_cast<size_t>(p.pixels) * p.C * (dtype == 1 ? 2 : 4);
+  const size_t bytes = static_cast<size_t>(p.pixels) * p.C * dtype_bytes(dtype);
   DevBuf tbuf, rbuf;
   TFC_HIP(tbuf.alloc(bytes, st));
   if constexpr (KT <= 6) {
@@ -718,7 +718,7 @@ extern "C" int tfc_gdn_backward(const void* x, const void* g, void* dx, int dtyp
                                 int rectify, int alpha_mode, int eps_mode, float* dbeta, float* dgamma,
                                 void* stream) {
   using namespace tfc;
-  if (dtype != 0 && dtype != 1) return fail("tfc_gdn_backward: dtype must be 0 (float32) or 1 (bfloat16)");
+  if (int rc = check_dtype("tfc_gdn_backward", dtype)) return rc;
   if (alpha_mode != 1 && alpha_mode != 2) return fail("tfc_gdn_backward: alpha must be 1 or 2");
   if (eps_mode != 0 && eps_mode != 1) return fail("tfc_gdn_backward: epsilon must be 1 or 0.5");
   if (channels <= 0 || channels % 32 != 0 || channels > 256)

@@ -32,8 +32,8 @@
 #include <type_traits>
 
 #include "../../include/tfc_hip.h"
+#include "bf16_io.h"
 #include "common.h"
-#include "mfma_types.h"
 
 namespace tfc {
 
@@ -93,8 +93,6 @@ __device__ inline float gdn_apply(float x, float n) {
   return x * (EPS_HALF ? __builtin_amdgcn_rsqf(n) : __builtin_amdgcn_rcpf(n));
 }
 
-__device__ inline float bf16_bits_to_float(unsigned int bits16) { return __uint_as_float(bits16 << 16); }
-
 // The kernels come in two flavours: PLAIN (alpha = 1, no rectify — the layer's defaults, where
 // |x| is a sign-bit clear on the packed words) and the general one, which folds rectify and
 // alpha into arithmetic on wave-uniform constants (no per-element branches either way).
@@ -129,19 +127,6 @@ __device__ inline float gdn_dx(float xv, float r, float a, float relu_floor, flo
   const float xe = fmaxf(xv, relu_floor);
   const float d = fmaf(a, gdn_du(xe, a2), r);
   return xv > relu_floor ? d : 0.f;
-}
-
-// v_cvt_pk_bf16_f32: two floats -> packed bf16 pair, round-to-nearest-even.
-__device__ inline unsigned int pack_bf16(float lo, float hi) {
-  return __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
-}
-
-__device__ inline unsigned int float_to_bf16_bits(float f) {
-  // round to nearest even, NaN preserved (matches __float2bfloat16)
-  unsigned int u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x40u;
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return u >> 16;
 }
 
 // ---------------------------------------------------------------------------
@@ -315,10 +300,7 @@ __global__ void __launch_bounds__(512) gdn_fwd_bf16_kernel(GdnParams p) {
             // non-temporal LOADS — still 32 bytes of a line per instruction — 57 us)
             if (on && 8 * k + (lane >> 3) < room) {
               u32x4* const dst = reinterpret_cast<u32x4*>(tbase + loff + 8 * k * C + 64 * (s >> 2));
-              // (as an instruction by hand: with __builtin_nontemporal_store in one branch and a plain store in the other the
-              // optimiser merges the two into ONE plain store)
-              if (p.nt_store) asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(dst), "v"(v) : "memory");
-              else *dst = v;
+              store_granule(dst, v, p.nt_store);
             }
 #endif
             __builtin_amdgcn_sched_barrier(0);        // (one granule at a time: registers)

@@ -20,6 +20,7 @@
 #include <cmath>
 
 #include "../../include/tfc_hip.h"
+#include "bf16_io.h"
 #include "common.h"
 #include "reduce_rows.h"
 
@@ -29,26 +30,6 @@ namespace {
 constexpr float kSnEps = 1e-12f;
 constexpr float kSlope = 0.2f;
 constexpr int kSnRows = 16;          // rows of W per workgroup of sn_wtu_kernel
-
-typedef __attribute__((ext_vector_type(2))) __bf16 hg_bf16x2;
-typedef __attribute__((ext_vector_type(2))) float hg_f32x2;
-
-__device__ inline unsigned short hg_to_bf16(float v) {
-  return static_cast<unsigned short>(
-      __builtin_bit_cast(unsigned int, __builtin_convertvector(hg_f32x2{v, 0.f}, hg_bf16x2)) & 0xFFFFu);
-}
-__device__ inline float hg_from_bf16(unsigned short v) { return __uint_as_float(static_cast<unsigned int>(v) << 16); }
-
-template <bool BF16>
-__device__ inline float hg_load(const void* base, long long at) {
-  if (BF16) return hg_from_bf16(static_cast<const unsigned short*>(base)[at]);
-  return static_cast<const float*>(base)[at];
-}
-template <bool BF16>
-__device__ inline void hg_store(void* base, long long at, float v) {
-  if (BF16) static_cast<unsigned short*>(base)[at] = hg_to_bf16(v);
-  else static_cast<float*>(base)[at] = v;
-}
 
 // max(x, 0.2 x): a positive slope keeps the sign
 __device__ inline float lrelu(float v) { return fmaxf(v, kSlope * v); }
@@ -204,15 +185,15 @@ __global__ void __launch_bounds__(256) front_forward_kernel(FrontParams p) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int c = c0 + e;
-      if (c < p.cx) v[e] = hg_load<BF16>(p.x, pix * p.cx + c);
-      else if (c < p.cx + p.cl) v[e] = lrelu(hg_load<BF16>(p.lat, src * p.cl + (c - p.cx)));
+      if (c < p.cx) v[e] = load<BF16>(p.x, pix * p.cx + c);
+      else if (c < p.cx + p.cl) v[e] = lrelu(load<BF16>(p.lat, src * p.cl + (c - p.cx)));
       else v[e] = 0.f;
     }
     const long long at = row * per_row + j;
     if (BF16) {
       uint2 o;
-      o.x = hg_to_bf16(v[0]) | (static_cast<unsigned int>(hg_to_bf16(v[1])) << 16);
-      o.y = hg_to_bf16(v[2]) | (static_cast<unsigned int>(hg_to_bf16(v[3])) << 16);
+      o.x = float_to_bf16_bits(v[0]) | (static_cast<unsigned int>(float_to_bf16_bits(v[1])) << 16);
+      o.y = float_to_bf16_bits(v[2]) | (static_cast<unsigned int>(float_to_bf16_bits(v[3])) << 16);
       static_cast<uint2*>(p.out)[at] = o;
     } else {
       static_cast<float4*>(p.out)[at] = make_float4(v[0], v[1], v[2], v[3]);
@@ -243,8 +224,8 @@ __global__ void __launch_bounds__(256) front_backward_kernel(FrontParams p) {
       const int dy = k / ww, dxx = k - dy * ww;
       const long long pix = (n * p.H + y0 + dy) * p.W + x0 + dxx;
       if (is_x || is_lat) {
-        const float gv = hg_load<BF16>(p.g, pix * p.P + c);
-        if (is_x) hg_store<BF16>(p.dx, pix * p.cx + c, gv);
+        const float gv = load<BF16>(p.g, pix * p.P + c);
+        if (is_x) store<BF16>(p.dx, pix * p.cx + c, gv);
         else acc += gv;
       }
     }
@@ -252,8 +233,8 @@ __global__ void __launch_bounds__(256) front_backward_kernel(FrontParams p) {
     acc += __shfl_xor(acc, 16);
     if (is_lat && q == 0) {
       const long long at = sp * p.cl + (c - p.cx);
-      const float lv = hg_load<BF16>(p.lat, at);
-      hg_store<BF16>(p.dlat, at, acc * (lv > 0.f ? 1.f : kSlope));
+      const float lv = load<BF16>(p.lat, at);
+      store<BF16>(p.dlat, at, acc * (lv > 0.f ? 1.f : kSlope));
     }
   }
 }
@@ -262,7 +243,7 @@ template <bool BF16>
 __global__ void __launch_bounds__(256) lrelu_forward_kernel(void* y, long long n) {
   const long long stride = static_cast<long long>(gridDim.x) * 256;
   for (long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x; i < n; i += stride)
-    hg_store<BF16>(y, i, lrelu(hg_load<BF16>(y, i)));
+    store<BF16>(y, i, lrelu(load<BF16>(y, i)));
 }
 
 // The same, 16 bytes per thread and step (y 16-byte aligned, `groups` whole groups of 4 float32 / 8 bfloat16 values).
@@ -276,7 +257,7 @@ __global__ void __launch_bounds__(256) lrelu_forward_vec_kernel(uint4* y, long l
     for (int k = 0; k < 4; ++k) {
       if (BF16) {
         const float lo = lrelu(__uint_as_float(w[k] << 16)), hi = lrelu(__uint_as_float(w[k] & 0xFFFF0000u));
-        w[k] = hg_to_bf16(lo) | (static_cast<unsigned int>(hg_to_bf16(hi)) << 16);
+        w[k] = float_to_bf16_bits(lo) | (static_cast<unsigned int>(float_to_bf16_bits(hi)) << 16);
       } else {
         w[k] = __float_as_uint(lrelu(__uint_as_float(w[k])));
       }
@@ -300,9 +281,9 @@ __global__ void __launch_bounds__(256) lrelu_backward_kernel(const void* gy, con
     if (c < C) {
       for (long long px = p0 + ty; px < p1; px += 4) {
         const long long at = px * C + c;
-        float g = hg_load<BF16>(gy, at);
-        if (masked) g = g * (hg_load<BF16>(y, at) > 0.f ? 1.f : kSlope);
-        if (gm) hg_store<BF16>(gm, at, g);
+        float g = load<BF16>(gy, at);
+        if (masked) g = g * (load<BF16>(y, at) > 0.f ? 1.f : kSlope);
+        if (gm) store<BF16>(gm, at, g);
         s += g;
       }
     }
@@ -348,7 +329,7 @@ __global__ void __launch_bounds__(256) lrelu_backward_vec_kernel(const uint4* gy
         }
         acc[2 * k] += lo;
         acc[2 * k + 1] += hi;
-        ow[k] = hg_to_bf16(lo) | (static_cast<unsigned int>(hg_to_bf16(hi)) << 16);
+        ow[k] = float_to_bf16_bits(lo) | (static_cast<unsigned int>(float_to_bf16_bits(hi)) << 16);
       } else {
         float g = __uint_as_float(gw[k]);
         if (masked) g = g * (__uint_as_float(yw[k]) > 0.f ? 1.f : kSlope);
@@ -386,7 +367,7 @@ __global__ void __launch_bounds__(1024) gan_loss_forward_kernel(const void* logi
   float a[4] = {0.f, 0.f, 0.f, 0.f};      // sce(real, 1), sce(fake, 0), sce(fake, 1), (unused)
   float pr = 0.f, pf = 0.f;
   for (long long i = threadIdx.x; i < M; i += 1024) {
-    const float r = hg_load<BF16>(logits, i), f = hg_load<BF16>(logits, M + i);
+    const float r = load<BF16>(logits, i), f = load<BF16>(logits, M + i);
     a[0] += fmaxf(r, 0.f) - r + softplus_neg_abs(r);
     a[1] += fmaxf(f, 0.f) + softplus_neg_abs(f);
     a[2] += fmaxf(f, 0.f) - f + softplus_neg_abs(f);
@@ -419,18 +400,13 @@ __global__ void __launch_bounds__(256) gan_loss_backward_kernel(const void* logi
   const float k = *scale / static_cast<float>(M);
   const long long stride = static_cast<long long>(gridDim.x) * 256;
   for (long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x; i < 2 * M; i += stride) {
-    const float x = hg_load<BF16>(logits, i);
+    const float x = load<BF16>(logits, i);
     const bool real = i < M;
     float gsc;
     if (mode == 0) gsc = real ? -sigmoid_stable(-x) : sigmoid_stable(x);
     else gsc = real ? 0.f : -sigmoid_stable(-x);
-    hg_store<BF16>(grad, i, k * gsc);
+    store<BF16>(grad, i, k * gsc);
   }
-}
-
-int hg_dtype(const char* name, int dtype) {
-  if (dtype != 0 && dtype != 1) return fail("%s: dtype must be 0 (float32) or 1 (bfloat16)", name);
-  return 0;
 }
 
 unsigned hg_blocks(long long items, long long per_block) {
@@ -487,7 +463,7 @@ namespace tfc {
 namespace {
 int front_validate(const char* name, int dtype, int64_t n, int64_t H, int64_t W, int64_t h, int64_t w, int cx, int cl,
                    int P) {
-  if (int rc = hg_dtype(name, dtype)) return rc;
+  if (int rc = check_dtype(name, dtype)) return rc;
   if (n < 0 || H < 1 || W < 1 || h < 1 || w < 1 || H > (1 << 15) || W > (1 << 15) || h > (1 << 15) || w > (1 << 15))
     return fail("%s: sizes must be positive and at most 2^15 per axis", name);
   if (cx < 1 || cl < 1 || cx + cl > 16)
@@ -546,7 +522,7 @@ extern "C" int tfc_disc_front_backward(const void* g, const void* latent, void* 
 
 extern "C" int tfc_lrelu_forward(void* y, int dtype, int64_t count, void* stream) {
   using namespace tfc;
-  if (int rc = hg_dtype("tfc_lrelu_forward", dtype)) return rc;
+  if (int rc = check_dtype("tfc_lrelu_forward", dtype)) return rc;
   if (count < 0) return fail("tfc_lrelu_forward: count must be non-negative, got %lld", static_cast<long long>(count));
   if (count == 0) return 0;
   if (!y) return fail("tfc_lrelu_forward: null tensor");
@@ -562,7 +538,7 @@ extern "C" int tfc_lrelu_forward(void* y, int dtype, int64_t count, void* stream
     done = groups * per;
   }
   if (done < count) {
-    void* const rest = static_cast<char*>(y) + done * (dtype == 1 ? 2 : 4);
+    void* const rest = static_cast<char*>(y) + done * dtype_bytes(dtype);
     const unsigned blocks = hg_blocks(count - done, 1024);
     if (dtype == 1) hipLaunchKernelGGL(lrelu_forward_kernel<true>, dim3(blocks), dim3(256), 0, st, rest, static_cast<long long>(count - done));
     else hipLaunchKernelGGL(lrelu_forward_kernel<false>, dim3(blocks), dim3(256), 0, st, rest, static_cast<long long>(count - done));
@@ -574,7 +550,7 @@ extern "C" int tfc_lrelu_forward(void* y, int dtype, int64_t count, void* stream
 extern "C" int tfc_lrelu_bias_backward(const void* gy, const void* y, void* gm, float* dbias, int dtype, int64_t pixels,
                                        int64_t channels, int masked, void* stream) {
   using namespace tfc;
-  if (int rc = hg_dtype("tfc_lrelu_bias_backward", dtype)) return rc;
+  if (int rc = check_dtype("tfc_lrelu_bias_backward", dtype)) return rc;
   if (pixels < 0) return fail("tfc_lrelu_bias_backward: pixels must be non-negative, got %lld", static_cast<long long>(pixels));
   if (channels < 1 || channels > (1 << 24))
     return fail("tfc_lrelu_bias_backward: channels must be in [1, 2^24], got %lld", static_cast<long long>(channels));
@@ -620,7 +596,7 @@ extern "C" int tfc_lrelu_bias_backward(const void* gy, const void* y, void* gm, 
 
 extern "C" int tfc_gan_loss_forward(const void* logits, int dtype, int64_t half, float* out, void* stream) {
   using namespace tfc;
-  if (int rc = hg_dtype("tfc_gan_loss_forward", dtype)) return rc;
+  if (int rc = check_dtype("tfc_gan_loss_forward", dtype)) return rc;
   if (half < 1) return fail("tfc_gan_loss_forward: at least one real and one fake logit, got half = %lld", static_cast<long long>(half));
   if (!logits || !out) return fail("tfc_gan_loss_forward: null tensor");
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -634,7 +610,7 @@ extern "C" int tfc_gan_loss_forward(const void* logits, int dtype, int64_t half,
 extern "C" int tfc_gan_loss_backward(const void* logits, const float* scale, int dtype, int64_t half, int mode,
                                      void* grad, void* stream) {
   using namespace tfc;
-  if (int rc = hg_dtype("tfc_gan_loss_backward", dtype)) return rc;
+  if (int rc = check_dtype("tfc_gan_loss_backward", dtype)) return rc;
   if (half < 1) return fail("tfc_gan_loss_backward: at least one real and one fake logit, got half = %lld", static_cast<long long>(half));
   if (mode != 0 && mode != 1) return fail("tfc_gan_loss_backward: mode must be 0 (d_loss) or 1 (g_loss), got %d", mode);
   if (!logits || !scale || !grad) return fail("tfc_gan_loss_backward: null tensor");

@@ -35,62 +35,14 @@
 #include <initializer_list>
 
 #include "../../include/tfc_hip.h"
+#include "bf16_io.h"
 #include "common.h"
 #include "unit_sum.h"
 
 namespace tfc {
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) unsigned int lp_u32x4;
-typedef __attribute__((ext_vector_type(4))) float lp_f32x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 lp_bf16x2;
-typedef __attribute__((ext_vector_type(2))) float lp_f32x2;
-
 constexpr int kLpWaves = 4;            // waves per workgroup of the distance kernels
-
-__device__ inline unsigned int lp_pack_bf16(float lo, float hi) {
-  return __builtin_bit_cast(unsigned int, __builtin_convertvector(lp_f32x2{lo, hi}, lp_bf16x2));
-}
-
-template <bool BF16>
-__device__ inline void lp_unpack(const lp_u32x4 raw, float* v) {
-  if (BF16) {
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      v[2 * w] = __uint_as_float(raw[w] << 16);
-      v[2 * w + 1] = __uint_as_float(raw[w] & 0xFFFF0000u);
-    }
-  } else {
-#pragma unroll
-    for (int w = 0; w < 4; ++w) v[w] = __uint_as_float(raw[w]);
-  }
-}
-
-// round to nearest even (gradients)
-template <bool BF16>
-__device__ inline lp_u32x4 lp_repack(const float* v) {
-  lp_u32x4 out;
-  if (BF16) {
-#pragma unroll
-    for (int w = 0; w < 4; ++w) out[w] = lp_pack_bf16(v[2 * w], v[2 * w + 1]);
-  } else {
-#pragma unroll
-    for (int w = 0; w < 4; ++w) out[w] = __float_as_uint(v[w]);
-  }
-  return out;
-}
-
-template <bool BF16>
-__device__ inline float lp_load(const void* base, long long at) {
-  if (BF16) return __uint_as_float(static_cast<unsigned int>(static_cast<const unsigned short*>(base)[at]) << 16);
-  return static_cast<const float*>(base)[at];
-}
-
-template <bool BF16>
-__device__ inline void lp_store(void* base, long long at, float v) {
-  if (BF16) static_cast<unsigned short*>(base)[at] = static_cast<unsigned short>(lp_pack_bf16(v, 0.f) & 0xFFFFu);
-  else static_cast<float*>(base)[at] = v;
-}
 
 struct LpipsParams {
   const void* f0;
@@ -141,24 +93,24 @@ __global__ void __launch_bounds__(64 * kLpWaves) lpips_vec_kernel(LpipsParams p)
     on[j] = gr < p.V;
 #pragma unroll
     for (int q = 0; q < EPG / 4; ++q) {
-      lp_f32x4 wv = {0.f, 0.f, 0.f, 0.f};
-      if (on[j]) wv = *reinterpret_cast<const lp_f32x4*>(p.w + gr * EPG + q * 4);
+      f32x4 wv = {0.f, 0.f, 0.f, 0.f};
+      if (on[j]) wv = *reinterpret_cast<const f32x4*>(p.w + gr * EPG + q * 4);
 #pragma unroll
       for (int e = 0; e < 4; ++e) wgt[j * EPG + q * 4 + e] = wv[e];
     }
   }
 
-  const lp_u32x4* const b0 = static_cast<const lp_u32x4*>(p.f0) + img * p.P * p.V;
-  const lp_u32x4* const b1 = static_cast<const lp_u32x4*>(p.f1) + img * p.P * p.V;
-  auto fetch = [&](const lp_u32x4* base, long long step, lp_u32x4* raw) {
+  const u32x4* const b0 = static_cast<const u32x4*>(p.f0) + img * p.P * p.V;
+  const u32x4* const b1 = static_cast<const u32x4*>(p.f1) + img * p.P * p.V;
+  auto fetch = [&](const u32x4* base, long long step, u32x4* raw) {
     const long long u = step * rw + grp;
 #pragma unroll
     for (int j = 0; j < NG; ++j) {
-      raw[j] = lp_u32x4{0u, 0u, 0u, 0u};
+      raw[j] = u32x4{0u, 0u, 0u, 0u};
       if (on[j] && u < p.P) raw[j] = base[u * p.V + j * lpr + l];
     }
   };
-  lp_u32x4 n0[NG], n1[NG];
+  u32x4 n0[NG], n1[NG];
   if (wave < steps) {
     fetch(b0, wave, n0);
     fetch(b1, wave, n1);
@@ -172,8 +124,8 @@ __global__ void __launch_bounds__(64 * kLpWaves) lpips_vec_kernel(LpipsParams p)
     float a[NE], b[NE];
 #pragma unroll
     for (int j = 0; j < NG; ++j) {
-      lp_unpack<BF16>(n0[j], a + j * EPG);
-      lp_unpack<BF16>(n1[j], b + j * EPG);
+      unpack<BF16>(n0[j], a + j * EPG);
+      unpack<BF16>(n1[j], b + j * EPG);
     }
     if (step + nwaves < steps) {
       fetch(b0, step + nwaves, n0);
@@ -216,12 +168,12 @@ __global__ void __launch_bounds__(64 * kLpWaves) lpips_vec_kernel(LpipsParams p)
         if (p.df0) {
 #pragma unroll
           for (int q = 0; q < EPG; ++q) o[q] = e[j * EPG + q] * ia - a[j * EPG + q] * c0;
-          if (on[j] && live) static_cast<lp_u32x4*>(p.df0)[(img * p.P + u) * p.V + j * lpr + l] = lp_repack<BF16>(o);
+          if (on[j] && live) static_cast<u32x4*>(p.df0)[(img * p.P + u) * p.V + j * lpr + l] = repack<BF16>(o);
         }
         if (p.df1) {
 #pragma unroll
           for (int q = 0; q < EPG; ++q) o[q] = b[j * EPG + q] * c1 - e[j * EPG + q] * ib;
-          if (on[j] && live) static_cast<lp_u32x4*>(p.df1)[(img * p.P + u) * p.V + j * lpr + l] = lp_repack<BF16>(o);
+          if (on[j] && live) static_cast<u32x4*>(p.df1)[(img * p.P + u) * p.V + j * lpr + l] = repack<BF16>(o);
         }
       }
     }
@@ -242,7 +194,7 @@ __global__ void __launch_bounds__(64 * kLpWaves) lpips_row_kernel(LpipsParams p)
     const long long at = (img * p.P + r) * p.C;
     float s0 = 0.f, s1 = 0.f;
     for (int c = lane; c < p.C; c += 64) {
-      const float a = lp_load<BF16>(p.f0, at + c), b = lp_load<BF16>(p.f1, at + c);
+      const float a = load<BF16>(p.f0, at + c), b = load<BF16>(p.f1, at + c);
       s0 = fmaf(a, a, s0);
       s1 = fmaf(b, b, s1);
     }
@@ -251,14 +203,14 @@ __global__ void __launch_bounds__(64 * kLpWaves) lpips_row_kernel(LpipsParams p)
     if (!BWD) {
       float t = 0.f;
       for (int c = lane; c < p.C; c += 64) {
-        const float d = lp_load<BF16>(p.f0, at + c) * ia - lp_load<BF16>(p.f1, at + c) * ib;
+        const float d = load<BF16>(p.f0, at + c) * ia - load<BF16>(p.f1, at + c) * ib;
         t = fmaf(p.w[c] * d, d, t);
       }
       acc += unit_sum(t, 6);                         // the same in all lanes; lane 0's is kept below
     } else {
       float d0 = 0.f, d1 = 0.f;
       for (int c = lane; c < p.C; c += 64) {
-        const float a = lp_load<BF16>(p.f0, at + c), b = lp_load<BF16>(p.f1, at + c);
+        const float a = load<BF16>(p.f0, at + c), b = load<BF16>(p.f1, at + c);
         const float e = ge * p.w[c] * (a * ia - b * ib);
         d0 = fmaf(a, e, d0);
         d1 = fmaf(b, e, d1);
@@ -268,10 +220,10 @@ __global__ void __launch_bounds__(64 * kLpWaves) lpips_row_kernel(LpipsParams p)
       const float c0 = nrm0 > 0.f ? d0 * ia * ia / nrm0 : 0.f;
       const float c1 = nrm1 > 0.f ? d1 * ib * ib / nrm1 : 0.f;
       for (int c = lane; c < p.C; c += 64) {
-        const float a = lp_load<BF16>(p.f0, at + c), b = lp_load<BF16>(p.f1, at + c);
+        const float a = load<BF16>(p.f0, at + c), b = load<BF16>(p.f1, at + c);
         const float e = ge * p.w[c] * (a * ia - b * ib);
-        if (p.df0) lp_store<BF16>(p.df0, at + c, e * ia - a * c0);
-        if (p.df1) lp_store<BF16>(p.df1, at + c, b * c1 - e * ib);
+        if (p.df0) store<BF16>(p.df0, at + c, e * ia - a * c0);
+        if (p.df1) store<BF16>(p.df1, at + c, b * c1 - e * ib);
       }
     }
   }
@@ -295,7 +247,7 @@ struct LpipsPlan {
 
 LpipsPlan lpips_plan(int dtype, long long C, std::initializer_list<const void*> tensors) {
   LpipsPlan plan;
-  const long long row_bytes = C * (dtype == 1 ? 2 : 4);
+  const long long row_bytes = C * dtype_bytes(dtype);
   bool aligned = true;
   for (const void* t : tensors) aligned = aligned && reinterpret_cast<uintptr_t>(t) % 16 == 0;
   if (!aligned || row_bytes % 16 != 0 || row_bytes / 16 > 128) return plan;
@@ -332,7 +284,7 @@ void lpips_launch(const LpipsPlan& plan, int dtype, long long N, hipStream_t st,
 }
 
 int lpips_validate(const char* name, int dtype, int64_t N, int64_t P, int64_t C, float eps) {
-  if (dtype != 0 && dtype != 1) return fail("%s: dtype must be 0 (float32) or 1 (bfloat16)", name);
+  if (int rc = check_dtype(name, dtype)) return rc;
   if (N < 0 || N >= (1 << 20)) return fail("%s: images must be in [0, 2^20), got %lld", name, static_cast<long long>(N));
   if (P < 1) return fail("%s: pixels must be positive, got %lld", name, static_cast<long long>(P));
   if (C < 1 || C > (1 << 24)) return fail("%s: channels must be in [1, 2^24], got %lld", name, static_cast<long long>(C));
@@ -374,14 +326,14 @@ __global__ void __launch_bounds__(256) maxpool_fwd_kernel(PoolParams p) {
       for (int j = 0; j < p.k; ++j) {
         const long long at = ((n * p.H + oh * p.s + i) * p.W + ow * p.s + j) * p.CV + cv;
         float v[EPG];
-        if (VEC) lp_unpack<BF16>(static_cast<const lp_u32x4*>(p.x)[at], v);
-        else v[0] = lp_load<BF16>(p.x, at);
+        if (VEC) unpack<BF16>(static_cast<const u32x4*>(p.x)[at], v);
+        else v[0] = load<BF16>(p.x, at);
 #pragma unroll
         for (int e = 0; e < EPG; ++e) m[e] = (i == 0 && j == 0) || pool_takes(v[e], m[e]) ? v[e] : m[e];
       }
     // (m holds input values: the conversion back is exact)
-    if (VEC) static_cast<lp_u32x4*>(p.y)[idx] = lp_repack<BF16>(m);
-    else lp_store<BF16>(p.y, idx, m[0]);
+    if (VEC) static_cast<u32x4*>(p.y)[idx] = repack<BF16>(m);
+    else store<BF16>(p.y, idx, m[0]);
   }
 }
 
@@ -414,8 +366,8 @@ __global__ void __launch_bounds__(256) maxpool_bwd_kernel(PoolParams p) {
           for (int j = 0; j < p.k; ++j) {
             const long long at = ((n * p.H + oh * p.s + i) * p.W + ow * p.s + j) * p.CV + cv;
             float v[EPG];
-            if (VEC) lp_unpack<BF16>(static_cast<const lp_u32x4*>(p.x)[at], v);
-            else v[0] = lp_load<BF16>(p.x, at);
+            if (VEC) unpack<BF16>(static_cast<const u32x4*>(p.x)[at], v);
+            else v[0] = load<BF16>(p.x, at);
 #pragma unroll
             for (int e = 0; e < EPG; ++e) {
               const bool take = (i == 0 && j == 0) || pool_takes(v[e], m[e]);
@@ -425,18 +377,18 @@ __global__ void __launch_bounds__(256) maxpool_bwd_kernel(PoolParams p) {
           }
         const long long gat = ((n * p.OH + oh) * p.OW + ow) * p.CV + cv;
         float gv[EPG];
-        if (VEC) lp_unpack<BF16>(static_cast<const lp_u32x4*>(p.g)[gat], gv);
-        else gv[0] = lp_load<BF16>(p.g, gat);
+        if (VEC) unpack<BF16>(static_cast<const u32x4*>(p.g)[gat], gv);
+        else gv[0] = load<BF16>(p.g, gat);
 #pragma unroll
         for (int e = 0; e < EPG; ++e) acc[e] += win[e] == mine ? gv[e] : 0.f;
       }
-    if (VEC) static_cast<lp_u32x4*>(p.y)[idx] = lp_repack<BF16>(acc);
-    else lp_store<BF16>(p.y, idx, acc[0]);
+    if (VEC) static_cast<u32x4*>(p.y)[idx] = repack<BF16>(acc);
+    else store<BF16>(p.y, idx, acc[0]);
   }
 }
 
 int pool_validate(const char* name, int dtype, int64_t n, int64_t h, int64_t w, int64_t c, int k, int s) {
-  if (dtype != 0 && dtype != 1) return fail("%s: dtype must be 0 (float32) or 1 (bfloat16)", name);
+  if (int rc = check_dtype(name, dtype)) return rc;
   if (n < 0 || c < 1 || c > (1 << 24)) return fail("%s: bad batch or channel count", name);
   if (k < 1 || s < 1 || k > 64) return fail("%s: window must be in [1, 64] and stride positive", name);
   if (h < k || w < k || h >= (1 << 30) || w >= (1 << 30))
@@ -453,7 +405,7 @@ int pool_launch(const void* x, const void* g, void* out, int dtype, int64_t n, i
   p.H = static_cast<int>(h); p.W = static_cast<int>(w);
   p.OH = static_cast<int>((h - k) / s + 1); p.OW = static_cast<int>((w - k) / s + 1);
   p.k = k; p.s = s;
-  const long long row_bytes = c * (dtype == 1 ? 2 : 4);
+  const long long row_bytes = c * dtype_bytes(dtype);
   bool vec = row_bytes % 16 == 0;
   for (const void* t : {x, g, static_cast<const void*>(out)}) vec = vec && reinterpret_cast<uintptr_t>(t) % 16 == 0;
   p.CV = static_cast<int>(vec ? row_bytes / 16 : c);

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/tfc_hip.h"
+#include "bf16_io.h"
 #include "common.h"
 #include "laplace_tail.h"
 
@@ -40,13 +41,6 @@ __device__ inline float log_interval_normal(float zu, float zl) {
   const float small = right ? log_ndtr(-zu) : log_ndtr(zl);
   return log1pf(-__expf(small - big)) + big;
 }
-
-template <typename T> __device__ inline float ld(const T* p, long long i);
-template <> __device__ inline float ld<float>(const float* p, long long i) { return p[i]; }
-template <> __device__ inline float ld<__hip_bfloat16>(const __hip_bfloat16* p, long long i) { return __bfloat162float(p[i]); }
-template <typename T> __device__ inline void st(T* p, long long i, float v);
-template <> __device__ inline void st<float>(float* p, long long i, float v) { p[i] = v; }
-template <> __device__ inline void st<__hip_bfloat16>(__hip_bfloat16* p, long long i, float v) { p[i] = __float2bfloat16(v); }
 
 struct NnParams {
   const void* y;
@@ -77,10 +71,10 @@ __global__ void __launch_bounds__(kThreads) noisy_normal_forward_kernel(NnParams
   float acc = 0.f;
   for (long long e = static_cast<long long>(blk) * kThreads + t; e < p.elems;
        e += static_cast<long long>(p.blocks_per_unit) * kThreads) {
-    float v = ld(y, e);
-    if (nz) v += ld(nz, e);
-    st(yh, e, v);
-    v = ld(yh, e);                                    // the value later passes see (dtype-rounded)
+    float v = load_as_float(y, e);
+    if (nz) v += load_as_float(nz, e);
+    store_from_float(yh, e, v);
+    v = load_as_float(yh, e);                         // the value later passes see (dtype-rounded)
     const float inv = 1.f / sc[e];
     float lp = log_interval_normal((v + 0.5f) * inv, (v - 0.5f) * inv);
     if (p.tail_mass > 0.f) lp = tail_mix(lp, v, p.tail_mass);
@@ -118,7 +112,7 @@ __global__ void __launch_bounds__(kThreads) noisy_normal_backward_kernel(NnParam
   const float g = p.gbits[unit] * -1.4426950408889634f;     // dL/d(sum log p) of this unit
   for (long long e = static_cast<long long>(blk) * kThreads + threadIdx.x; e < p.elems;
        e += static_cast<long long>(p.blocks_per_unit) * kThreads) {
-    const float v = ld(yh, e);
+    const float v = load_as_float(yh, e);
     const float inv = 1.f / sc[e];
     const float zu = (v + 0.5f) * inv, zl = (v - 0.5f) * inv;
     const float lp = log_interval_normal(zu, zl);
@@ -138,7 +132,7 @@ __global__ void __launch_bounds__(kThreads) noisy_normal_backward_kernel(NnParam
     ds[e] = -g * (gu * zu + gl * zl) * inv;
     if (yin) {
       // expected gradients (math_ops.py:157-216): log p(x + .5) - log p(x - .5) at the unperturbed x
-      const float x = ld(yin, e);
+      const float x = load_as_float(yin, e);
       float hi = log_interval_normal((x + 1.f) * inv, x * inv), low = log_interval_normal(x * inv, (x - 1.f) * inv);
       if (p.tail_mass > 0.f) {
         hi = tail_mix(hi, x + 0.5f, p.tail_mass);
@@ -146,7 +140,7 @@ __global__ void __launch_bounds__(kThreads) noisy_normal_backward_kernel(NnParam
       }
       dv = g * (hi - low);
     }
-    st(dy, e, dv);
+    store_from_float(dy, e, dv);
   }
 }
 
@@ -168,7 +162,7 @@ namespace {
 int nn_forward(const char* who, const void* y, const void* noise, const float* scale, void* y_hat, int dtype,
                int64_t units, int64_t elems, float tail_mass, float* bits, void* stream) {
   using namespace tfc;
-  if (dtype != 0 && dtype != 1) return fail("%s: dtype must be 0 (float32) or 1 (bfloat16)", who);
+  if (int rc = check_dtype(who, dtype)) return rc;
   if (units == 0) return 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   NnParams p{};
@@ -193,7 +187,7 @@ int nn_forward(const char* who, const void* y, const void* noise, const float* s
 int nn_backward(const char* who, const void* y_in, const void* y_hat, const float* scale, int dtype, int64_t units,
                 int64_t elems, float tail_mass, const float* gbits, void* dy, float* dscale, void* stream) {
   using namespace tfc;
-  if (dtype != 0 && dtype != 1) return fail("%s: dtype must be 0 (float32) or 1 (bfloat16)", who);
+  if (int rc = check_dtype(who, dtype)) return rc;
   if (units == 0 || elems == 0) return 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   NnParams p{};

@@ -57,6 +57,7 @@
 // LDS image (built by tfc_tables_create): row directory, 16-bit scaled cdf entries, then (decoder
 // only) the boundary bitmaps and their running counts.
 #pragma once
+#include "mfma_types.h"
 
 namespace tfc {
 
@@ -139,20 +140,19 @@ struct DecLaneJobs {
 // the kernel-argument struct by a dynamic index, so hipcc takes them for generic ("flat") pointers —
 // and a flat access counts on lgkmcnt as well: every LDS read of the steps after a memory phase would
 // wait for the phase's global loads.
-typedef unsigned int lanes_u32x4 __attribute__((ext_vector_type(4)));
 template <typename T>
 struct __attribute__((packed)) LanePacked { T v; };
 #define TFC_AS1 __attribute__((address_space(1)))
 __device__ inline uint4 lanes_gload16(const void* p) {
-  const lanes_u32x4 v = reinterpret_cast<const TFC_AS1 LanePacked<lanes_u32x4>*>((const TFC_AS1 void*)p)->v;
+  const u32x4 v = reinterpret_cast<const TFC_AS1 LanePacked<u32x4>*>((const TFC_AS1 void*)p)->v;
   return make_uint4(v.x, v.y, v.z, v.w);
 }
 __device__ inline unsigned int lanes_gload8(const void* p) {
   return *reinterpret_cast<const TFC_AS1 unsigned char*>((const TFC_AS1 void*)p);
 }
 __device__ inline void lanes_gstore16(void* p, const uint2& lo, const uint2& hi) {
-  lanes_u32x4 v = {lo.x, lo.y, hi.x, hi.y};
-  reinterpret_cast<TFC_AS1 LanePacked<lanes_u32x4>*>((TFC_AS1 void*)p)->v = v;
+  u32x4 v = {lo.x, lo.y, hi.x, hi.y};
+  reinterpret_cast<TFC_AS1 LanePacked<u32x4>*>((TFC_AS1 void*)p)->v = v;
 }
 // one element of 2 or 4 bytes, by its bits
 template <typename T>

@@ -15,12 +15,12 @@
 // from its predecessor's exit for a bounded number of rounds (rl_sync_kernel, rounds 1..R), then one wave per string repairs any chunk
 // still out of step sequentially and scans the symbol counts (rl_fix_kernel), and the chunks are decoded from
 // their true entry points (rl_decode_kernel again).  Errors are only raised from that last, true, parse.
-#include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 
 #include <cstdlib>
 #include <cstring>
 
+#include "bf16_io.h"
 #include "common.h"
 #include "../../include/tfc_hip.h"
 
@@ -59,8 +59,7 @@ template <> struct In<0> { static __device__ int32_t at(const void* p, int64_t i
 template <> struct In<1> { static __device__ int32_t at(const void* p, int64_t i) { return int32_t(rintf(static_cast<const float*>(p)[i])); } };
 template <> struct In<2> {
   static __device__ int32_t at(const void* p, int64_t i) {
-    const uint16_t b = static_cast<const uint16_t*>(p)[i];
-    return int32_t(rintf(__uint_as_float(uint32_t(b) << 16)));
+    return int32_t(rintf(bf16_bits_to_float(static_cast<const uint16_t*>(p)[i])));
   }
 };
 template <> struct In<3> { static __device__ int32_t at(const void* p, int64_t i) { return int32_t(rintf(__half2float(static_cast<const __half*>(p)[i]))); } };
@@ -443,7 +442,7 @@ __device__ __forceinline__ void store(const DecParams& p, int64_t i, int32_t v) 
   } else if (p.out_dtype == 1) {
     static_cast<float*>(p.out)[i] = float(v);
   } else {
-    static_cast<__hip_bfloat16*>(p.out)[i] = __float2bfloat16(float(v));
+    static_cast<unsigned short*>(p.out)[i] = float_to_bf16_bits(float(v));
   }
 }
 

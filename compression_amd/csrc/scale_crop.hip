@@ -104,7 +104,8 @@ __device__ __forceinline__ void scale_crop_pixel(const ScaleCropRow& r, unsigned
   }
 }
 
-// float32 -> bfloat16, round to nearest even; the values here are finite
+// float32 -> bfloat16, round to nearest even; the values here are finite.  Deliberately not bf16_io.h's hardware convert:
+// integer arithmetic, three instructions, another answer on NaN — the bits the tests pin come from this.
 __device__ __forceinline__ unsigned bf16_bits(float f) {
   const unsigned u = __float_as_uint(f);
   return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;

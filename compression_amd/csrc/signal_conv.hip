@@ -295,8 +295,8 @@ __global__ void __launch_bounds__(64 * kConvWaves) conv_kernel(const T* x, const
               v[r] = acc[t][4 * (2 * qp + half) + r] + b;
               if (c.activation == 1) v[r] = fmaxf(v[r], 0.f);
             }
-            o[2 * half] = __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{v[0], v[1]}, bf16x2));
-            o[2 * half + 1] = __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{v[2], v[3]}, bf16x2));
+            o[2 * half] = pack_bf16(v[0], v[1]);
+            o[2 * half + 1] = pack_bf16(v[2], v[3]);
           }
           const auto s0 = __builtin_amdgcn_permlane32_swap(o.x, o.z, false, false);
           const auto s1 = __builtin_amdgcn_permlane32_swap(o.y, o.w, false, false);
@@ -326,8 +326,8 @@ __global__ void __launch_bounds__(64 * kConvWaves) conv_kernel(const T* x, const
         T* dst = y + mm * c.Cout + col0;
         if constexpr (BF) {
           u32x2 o;
-          o.x = __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{v[0], v[1]}, bf16x2));
-          o.y = __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{v[2], v[3]}, bf16x2));
+          o.x = pack_bf16(v[0], v[1]);
+          o.y = pack_bf16(v[2], v[3]);
           *reinterpret_cast<u32x2*>(dst) = o;
         } else {
           *reinterpret_cast<f32x4*>(dst) = f32x4{v[0], v[1], v[2], v[3]};
@@ -639,8 +639,8 @@ __global__ void __launch_bounds__(256, TFC_CONV_WGS) conv_bf16_kernel(const __bf
               v[r] = acc[p][t][4 * (2 * qp + half) + r] + b4[r];
               if (c.activation == 1) v[r] = fmaxf(v[r], 0.f);
             }
-            o[2 * half] = __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{v[0], v[1]}, bf16x2));
-            o[2 * half + 1] = __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{v[2], v[3]}, bf16x2));
+            o[2 * half] = pack_bf16(v[0], v[1]);
+            o[2 * half + 1] = pack_bf16(v[2], v[3]);
           }
           const auto s0 = __builtin_amdgcn_permlane32_swap(o.x, o.z, false, false);
           const auto s1 = __builtin_amdgcn_permlane32_swap(o.y, o.w, false, false);
@@ -694,8 +694,8 @@ __global__ void __launch_bounds__(256, TFC_CONV_WGS) conv_bf16_kernel(const __bf
           // su == 1: phase 0, (oy, ox) = (qy, qx); else depth-to-space of the column's phase
           const int oy = qy[p] * c.su + phase / c.su, ox = qx[p] * c.su + phase % c.su;
           u32x2 o;
-          o.x = __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{v[0], v[1]}, bf16x2));
-          o.y = __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{v[2], v[3]}, bf16x2));
+          o.x = pack_bf16(v[0], v[1]);
+          o.y = pack_bf16(v[2], v[3]);
           *reinterpret_cast<u32x2*>(y + ((nn[p] * c.OH + oy) * c.OW + ox) * c.Cout + co) = o;
         } else {
 #pragma unroll
@@ -1101,8 +1101,8 @@ __global__ void __launch_bounds__(256, 2) conv_image_kernel(const __bf16* x, con
             if (g.activation == 1) v[r] = fmaxf(v[r], 0.f);
           }
           uint2 o;
-          o.x = __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{v[0], v[1]}, bf16x2));
-          o.y = __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{v[2], v[3]}, bf16x2));
+          o.x = pack_bf16(v[0], v[1]);
+          o.y = pack_bf16(v[2], v[3]);
           *reinterpret_cast<uint2*>(stg + l * ROW + (32 * tt + 8 * q + 4 * h) * 2) = o;
         }
       }
@@ -1331,10 +1331,8 @@ __global__ void __launch_bounds__(512, 1) conv_image_direct_kernel(const __bf16*
         for (int half = 0; half < 2; ++half) {
           const f32x4 b4 = *reinterpret_cast<const f32x4*>(bias_s + 32 * t0 + 8 * (q0 + half) + 4 * h);
           const int e = 4 * (q0 + half);
-          xb[s][2 * half] = __builtin_bit_cast(unsigned int, __builtin_convertvector(
-                                f32x2{acc[t0][e], acc[t0][e + 1]} + f32x2{b4[0], b4[1]}, bf16x2));
-          xb[s][2 * half + 1] = __builtin_bit_cast(unsigned int, __builtin_convertvector(
-                                    f32x2{acc[t0][e + 2], acc[t0][e + 3]} + f32x2{b4[2], b4[3]}, bf16x2));
+          xb[s][2 * half] = pack_bf16(f32x2{acc[t0][e], acc[t0][e + 1]} + f32x2{b4[0], b4[1]});
+          xb[s][2 * half + 1] = pack_bf16(f32x2{acc[t0][e + 2], acc[t0][e + 3]} + f32x2{b4[2], b4[3]});
         }
       }
       // gamma's fragments one K step ahead, each register set refilled as soon as its MFMA has read it (a second
@@ -1372,8 +1370,8 @@ __global__ void __launch_bounds__(512, 1) conv_image_direct_kernel(const __bf16*
               v[k] = yv * rn;
             }
             uint2 o;
-            o.x = __builtin_bit_cast(unsigned int, __builtin_convertvector(v[0], bf16x2));
-            o.y = __builtin_bit_cast(unsigned int, __builtin_convertvector(v[1], bf16x2));
+            o.x = pack_bf16(v[0]);
+            o.y = pack_bf16(v[1]);
             *reinterpret_cast<uint2*>(stg + l * ROW + (32 * tt + 8 * q + 4 * h) * 2) = o;
           }
         }
@@ -1403,8 +1401,8 @@ __global__ void __launch_bounds__(512, 1) conv_image_direct_kernel(const __bf16*
               if (g.activation == 1) v[k] = fmaxf(v[k], 0.f);
             }
             uint2 o;
-            o.x = __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{v[0], v[1]}, bf16x2));
-            o.y = __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{v[2], v[3]}, bf16x2));
+            o.x = pack_bf16(v[0], v[1]);
+            o.y = pack_bf16(v[2], v[3]);
             *reinterpret_cast<uint2*>(stg + l * ROW + (32 * tt + 8 * q + 4 * h) * 2) = o;
           }
         }
@@ -1634,7 +1632,7 @@ __global__ void __launch_bounds__(kUpThreads) conv_up_fused_kernel(const __bf16*
       for (int c = 0; c < (COUT ? COUT : 4); ++c) {
         float v = a[c];
         if (g.activation == 1) v = fmaxf(v, 0.f);
-        outv[k * 4 + c] = __builtin_bit_cast(unsigned short, static_cast<__bf16>(v));
+        outv[k * 4 + c] = float_to_bf16_bits(v);
       }
     }
     __bf16* dst = y + ((n * OH + oy) * OW + bx * tw + rx) * cout;
@@ -1847,8 +1845,8 @@ __global__ void __launch_bounds__(512, 2) conv_up_phase_kernel(const __bf16* x, 
         if (g.activation == 1) v[i] = fmaxf(v[i], 0.f);
       }
       unsigned int* dst = reinterpret_cast<unsigned int*>(yrow + static_cast<long long>(J) * (3 * S) + first);
-      dst[0] = __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{v[0], v[1]}, bf16x2));
-      if (count == 4) dst[1] = __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{v[2], v[3]}, bf16x2));
+      dst[0] = pack_bf16(v[0], v[1]);
+      if (count == 4) dst[1] = pack_bf16(v[2], v[3]);
     }
   }
 }
@@ -2138,7 +2136,7 @@ int route_gemm(const ConvCall& k) {
 
 int conv_entry(const ConvCall& k) {
   if (k.gdn_fused) *k.gdn_fused = 0;
-  if (k.dtype != 0 && k.dtype != 1) return fail("tfc_conv2d: dtype must be 0 (float32) or 1 (bfloat16)");
+  if (int rc = check_dtype("tfc_conv2d", k.dtype)) return rc;
   if (k.kh < 1 || k.kw < 1 || k.stride < 1 || k.cin < 1 || k.cout < 1) return fail("tfc_conv2d: bad geometry");
   if (!(k.cin % 16 == 0 || k.cin <= 4))
     return fail("tfc_conv2d: input channels must be a multiple of 16 or <= 4 (got %lld)", static_cast<long long>(k.cin));

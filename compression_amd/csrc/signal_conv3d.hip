@@ -447,7 +447,7 @@ int conv3d_bf16(const char* name, const __bf16* x, const float* w, int planes, c
 int conv3d_entry(const char* name, const void* x, const void* w, const float* bias, void* y, int dtype, int64_t n,
                  int64_t d, int64_t h, int64_t wd, int64_t cin, int64_t cout, int kd, int kh, int kw, int sd, int sh,
                  int sw, int activation, int up, void* stream) {
-  if (dtype != 0 && dtype != 1) return fail("%s: dtype must be 0 (float32) or 1 (bfloat16)", name);
+  if (int rc = check_dtype(name, dtype)) return rc;
   if (kd < 1 || kh < 1 || kw < 1) return fail("%s: kernel support must be >= 1 (got %d, %d, %d)", name, kd, kh, kw);
   if (sd < 1 || sh < 1 || sw < 1) return fail("%s: strides must be >= 1 (got %d, %d, %d)", name, sd, sh, sw);
   if (n < 0 || d < 0 || h < 0 || wd < 0) return fail("%s: negative extent", name);
@@ -512,7 +512,7 @@ extern "C" int tfc_conv3d_wgrad(const void* a, const void* b, float* dw, int dty
                                 int kw, int sd, int sh, int sw, int transpose, void* stream) {
   using namespace tfc;
   const char* name = "tfc_conv3d_wgrad";
-  if (dtype != 0 && dtype != 1) return fail("%s: dtype must be 0 (float32) or 1 (bfloat16)", name);
+  if (int rc = check_dtype(name, dtype)) return rc;
   if (kd < 1 || kh < 1 || kw < 1) return fail("%s: kernel support must be >= 1 (got %d, %d, %d)", name, kd, kh, kw);
   if (sd < 1 || sh < 1 || sw < 1) return fail("%s: strides must be >= 1 (got %d, %d, %d)", name, sd, sh, sw);
   if (n < 0 || da < 0 || ha < 0 || wa < 0 || db < 0 || hb < 0 || wb < 0) return fail("%s: negative extent", name);

@@ -431,7 +431,7 @@ extern "C" int tfc_conv2d_wgrad(const void* a, const void* b, float* dw, int dty
                                 int64_t wa, int64_t ca, int64_t hb, int64_t wb, int64_t cb, int kh, int kw,
                                 int stride, int transpose, void* stream) {
   using namespace tfc;
-  if (dtype != 0 && dtype != 1) return fail("tfc_conv2d_wgrad: dtype must be 0 (float32) or 1 (bfloat16)");
+  if (int rc = check_dtype("tfc_conv2d_wgrad", dtype)) return rc;
   if (kh < 1 || kw < 1 || stride < 1 || ca < 1 || cb < 1) return fail("tfc_conv2d_wgrad: bad geometry");
   auto ok = [](int64_t c) { return c <= 4 || (c % 32 == 0 && c <= 256); };
   if (!ok(ca) || !ok(cb))

@@ -43,6 +43,7 @@
 #include <cmath>
 
 #include "../../include/tfc_hip.h"
+#include "bf16_io.h"
 #include "common.h"
 #include "reduce_rows.h"
 
@@ -67,15 +68,6 @@ struct SsimParams {
   float c1, c2, inv_count;
   float taps[kSsimMaxTaps + 1];
 };
-
-template <typename T> __device__ inline float ssim_ld(const T* p, long long i);
-template <> __device__ inline float ssim_ld<float>(const float* p, long long i) { return p[i]; }
-template <> __device__ inline float ssim_ld<unsigned char>(const unsigned char* p, long long i) { return p[i]; }
-template <> __device__ inline float ssim_ld<_Float16>(const _Float16* p, long long i) { return static_cast<float>(p[i]); }
-// bfloat16 as its 16 bits
-template <> __device__ inline float ssim_ld<unsigned short>(const unsigned short* p, long long i) {
-  return __uint_as_float(static_cast<unsigned int>(p[i]) << 16);
-}
 
 // Which channel, tile and image a workgroup has.
 struct SsimBlock {
@@ -117,8 +109,8 @@ __device__ inline void ssim_stage(const T* gx, const T* gy, long long base, long
       const int iy = y0 + r, ix = x0 + c;
       ok[q] = c < cols && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
       const long long at = base + min(max(iy, 0), p.H - 1) * rowstride + static_cast<long long>(min(max(ix, 0), p.W - 1)) * p.C;
-      a[q] = ssim_ld<T>(gx, at);
-      b[q] = ssim_ld<T>(gy, at);
+      a[q] = load_as_float(gx, at);
+      b[q] = load_as_float(gy, at);
     }
 #pragma unroll
     for (int q = 0; q < NIT; ++q) {
@@ -135,8 +127,8 @@ __device__ inline void ssim_stage(const T* gx, const T* gy, long long base, long
       float a = 0.f, b = 0.f;
       if (c < cols && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) {
         const long long at = base + iy * rowstride + static_cast<long long>(ix) * p.C;
-        a = ssim_ld<T>(gx, at) - cen;
-        b = ssim_ld<T>(gy, at) - cen;
+        a = load_as_float(gx, at) - cen;
+        b = load_as_float(gy, at) - cen;
       }
       sx[idx] = a;
       sy[idx] = b;
@@ -172,7 +164,7 @@ __global__ void __launch_bounds__(256) ssim_fwd_kernel(SsimParams p) {
   const long long base = static_cast<long long>(blk.img) * p.H * rowstride + ch;
   const T* gx = static_cast<const T*>(p.x);
   const T* gy = static_cast<const T*>(p.y);
-  const float cen = ssim_ld<T>(gx, base + oy0 * rowstride + static_cast<long long>(ox0) * p.C);
+  const float cen = load_as_float(gx, base + oy0 * rowstride + static_cast<long long>(ox0) * p.C);
 
   constexpr int NIT = NT ? ((TILE + NT - 1) * ssim_fwd_stride<TILE, NT>(NT) + 255) / 256 : 0;
   ssim_stage<T, NIT>(gx, gy, base, rowstride, p, oy0, ox0, IW, IW, IWP, cen, sx, sy);
@@ -333,7 +325,7 @@ __global__ void __launch_bounds__(256) ssim_bwd_kernel(SsimParams p) {
   const long long plane = static_cast<long long>(blk.img) * p.C + ch;
   const T* gx = static_cast<const T*>(p.x);
   const T* gy = static_cast<const T*>(p.y);
-  const float cen = ssim_ld<T>(gx, base + i0 * rowstride + static_cast<long long>(j0) * p.C);
+  const float cen = load_as_float(gx, base + i0 * rowstride + static_cast<long long>(j0) * p.C);
   const float wa = p.gmeans[2 * plane] * p.inv_count, wb = p.gmeans[2 * plane + 1] * p.inv_count;
 
   constexpr int NIT = NT ? ((TILE + 2 * NT - 2) * (TILE + 2 * NT - 2) + 255) / 256 : 0;

@@ -25,6 +25,7 @@
 
 #include <hip/hip_fp16.h>
 
+#include "bf16_io.h"
 #include "common.h"
 
 namespace tfc {
@@ -150,7 +151,7 @@ template <> struct Elem<0> {
 template <> struct Elem<1> {
   using T = uint16_t;
   using Vec = uint2;
-  static __device__ float widen(T v) { return __uint_as_float(static_cast<uint32_t>(v) << 16); }
+  static __device__ float widen(T v) { return bf16_bits_to_float(v); }
   static __device__ void unpack(const Vec& v, float (&f)[4]) {
     f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xFFFF0000u);
     f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xFFFF0000u);

@@ -12,6 +12,7 @@
 //     neighbouring pixels.  Rows whose width is a multiple of 8 take 8/16-byte loads and stores; any other width, or an
 //     output that is not aligned, takes the same arithmetic with one access per value.
 // Byte offsets are 64-bit throughout.  No atomics, no LDS, no scratch.
+#include "bf16_io.h"
 #include "common.h"
 
 #include <cmath>
@@ -184,18 +185,6 @@ __device__ __forceinline__ float byte_of(unsigned v, int k) { return static_cast
 __device__ __forceinline__ float clamp255(float v) { return __builtin_amdgcn_fmed3f(v, 0.f, 255.f); }
 // Clamp, then round half to even: adding 2^23 leaves the integer in the low mantissa bits, rounded by the addition itself.
 __device__ __forceinline__ unsigned to_u8(float v) { return __float_as_uint(clamp255(v) + 8388608.f) & 0xffu; }
-// Two float32 -> two bfloat16, round to nearest even (one v_cvt_pk_bf16_f32 on gfx950); `a` in the low half.
-typedef float csc_float2 __attribute__((ext_vector_type(2)));
-typedef __bf16 csc_bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-  const csc_float2 f = {a, b};
-  const csc_bf16x2 h = __builtin_convertvector(f, csc_bf16x2);
-  unsigned u;
-  __builtin_memcpy(&u, &h, 4);
-  return u;
-}
-__device__ __forceinline__ unsigned to_bf16(float v) { return pack_bf16(v, v) & 0xffffu; }
-__device__ __forceinline__ float from_bf16(unsigned h) { return __uint_as_float(h << 16); }
 
 template <int MODE>
 __device__ __forceinline__ void load_chroma(const CscParams& p, unsigned n, unsigned i, int x0, float cb[CSC_PX],
@@ -360,7 +349,7 @@ __global__ void __launch_bounds__(CSC_LANES * CSC_ROWS) ycbcr_to_rgb_kernel(CscP
       } else {
 #pragma unroll
         for (int e = 0; e < 3 * CSC_PX; ++e)
-          if (e < 3 * npx) op[e] = static_cast<unsigned short>(to_bf16(o[e]));
+          if (e < 3 * npx) op[e] = float_to_bf16_bits(o[e]);
       }
     }
   }
@@ -403,11 +392,11 @@ __device__ __forceinline__ void load_rgb(const CscParams& p, long long px, int n
         const uint4 w = load16(reinterpret_cast<const u8*>(ip + 8 * d));
         const unsigned ww[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
-        for (int t = 0; t < 8; ++t) v[8 * d + t] = from_bf16((ww[t >> 1] >> (16 * (t & 1))) & 0xffffu);
+        for (int t = 0; t < 8; ++t) v[8 * d + t] = bf16_bits_to_float((ww[t >> 1] >> (16 * (t & 1))) & 0xffffu);
       }
     } else {
 #pragma unroll
-      for (int e = 0; e < 3 * CSC_PX; ++e) v[e] = e < 3 * npx ? from_bf16(ip[e]) : 0.f;
+      for (int e = 0; e < 3 * CSC_PX; ++e) v[e] = e < 3 * npx ? bf16_bits_to_float(ip[e]) : 0.f;
     }
   }
 }

@@ -17,7 +17,7 @@ from . import continuous_base
 
 __all__ = ["ContinuousBatchedEntropyModel", "EntropyBottleneck"]
 
-_DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+_DTYPE_CODE = _lib.DTYPE_CODE_F16
 
 
 class ContinuousBatchedEntropyModel(continuous_base.ContinuousEntropyModelBase):

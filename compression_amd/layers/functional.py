@@ -4,8 +4,9 @@ from __future__ import annotations
 import torch
 
 from .. import _lib
+from .._lib import ptr as _ptr
 
-_DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1}
+_DTYPE_CODE = _lib.DTYPE_CODE
 
 
 class GDNPrepared:
@@ -111,10 +112,6 @@ def _channel_norm_args(x, gamma, beta, epsilon):
                 raise ValueError(f"{name} shape {tuple(t.shape)} does not match C={C}")
         params.append(t)
     return x.contiguous(), params[0], params[1], C, float(epsilon)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def channel_norm_forward(x, gamma, beta, epsilon=1e-3, relu=False, residual=None):

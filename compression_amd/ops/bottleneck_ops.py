@@ -9,7 +9,7 @@ from .. import _lib
 
 __all__ = ["factorized_bits", "pack_factorized_params", "fused_factorized_supported", "fused_tail_mass"]
 
-_DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1}
+_DTYPE_CODE = _lib.DTYPE_CODE
 _BUILT = {(3, 3), (4, 3), (3, 5)}          # (layers, width) the library instantiates
 
 
@@ -50,7 +50,7 @@ class _FactorizedBits(torch.autograd.Function):
         y_hat = torch.empty_like(y)
         bits = torch.empty(units, dtype=torch.float32, device=y.device)
         channels = params.shape[0]
-        noise_ptr = noise.data_ptr() if noise is not None else None
+        noise_ptr = _lib.ptr(noise)
         if tail_mass:
             _lib.check(_lib.lib().tfc_factorized_bits_forward_tail(
                 y.data_ptr(), noise_ptr, y_hat.data_ptr(), _DTYPE_CODE[y.dtype], units, elems, channels,
@@ -77,7 +77,7 @@ class _FactorizedBits(torch.autograd.Function):
             # Laplace-mixture tail (continuous_base.py:298-334); the unperturbed input selects expected gradients
             y = ctx.saved_tensors[2] if len(ctx.saved_tensors) == 3 else None
             _lib.check(_lib.lib().tfc_factorized_bits_backward_tail(
-                y.data_ptr() if y is not None else None, y_hat.data_ptr(), _DTYPE_CODE[y_hat.dtype], units, elems,
+                _lib.ptr(y), y_hat.data_ptr(), _DTYPE_CODE[y_hat.dtype], units, elems,
                 params.shape[0], params.data_ptr(), layers, width, tail_mass, gb.data_ptr(), dy.data_ptr(),
                 dparams.data_ptr(), _lib.stream_ptr()))
         elif len(ctx.saved_tensors) == 3:
@@ -133,7 +133,7 @@ class _NoisyNormalBits(torch.autograd.Function):
         scale = scale.to(torch.float32).contiguous()
         y_hat = torch.empty_like(y)
         bits = torch.empty(units, dtype=torch.float32, device=y.device)
-        noise_ptr = noise.data_ptr() if noise is not None else None
+        noise_ptr = _lib.ptr(noise)
         if tail_mass:
             _lib.check(_lib.lib().tfc_noisy_normal_bits_forward_tail(
                 y.data_ptr(), noise_ptr, scale.data_ptr(), y_hat.data_ptr(), _DTYPE_CODE[y.dtype], units, elems,
@@ -154,7 +154,7 @@ class _NoisyNormalBits(torch.autograd.Function):
         dy = torch.empty_like(y_hat)
         dscale = torch.empty_like(scale)
         gb = (g_bits if g_bits is not None else torch.zeros(units, device=y_hat.device)).to(torch.float32).contiguous()
-        y_in_ptr = y_in.data_ptr() if y_in is not None else None
+        y_in_ptr = _lib.ptr(y_in)
         if tail_mass:
             _lib.check(_lib.lib().tfc_noisy_normal_bits_backward_tail(
                 y_in_ptr, y_hat.data_ptr(), scale.data_ptr(), _DTYPE_CODE[y_hat.dtype], units, elems, tail_mass,

@@ -18,8 +18,6 @@ definition as tensor ops, position by position, for any float dtype and for CPU 
 from __future__ import annotations
 
 import collections
-import os
-import re
 
 import torch
 
@@ -34,17 +32,8 @@ ContextScan = collections.namedtuple("ContextScan", ["sym", "idx", "mu", "y_hat"
 CAUSAL_TAPS = tuple((di, dj) for di in range(-2, 1) for dj in range(-2, 3) if di < 0 or dj < 0)
 
 
-def _kernel_constants():
-    """The named constants of csrc/context_params.h, read from that file."""
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc", "context_params.h")
-    with open(path) as f:
-        found = re.findall(r"constexpr\s+int\s+(CTX_[A-Z0-9_]+)\s*=\s*(\d+)\s*;", f.read())
-    if not found:
-        raise RuntimeError(f"no constants found in {path}")
-    return {name: int(value) for name, value in found}
-
-
-CONTEXT_CONSTANTS = _kernel_constants()
+# the named constants of csrc/context_params.h
+CONTEXT_CONSTANTS = _lib.kernel_constants("context_params.h", ("CTX",))
 assert CONTEXT_CONSTANTS["CTX_TAPS"] == len(CAUSAL_TAPS)
 
 

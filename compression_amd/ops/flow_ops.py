@@ -17,29 +17,19 @@ has a `*_reference` twin of plain tensor ops, which CPU tensors (and float64) ta
 from __future__ import annotations
 
 import math
-import os
-import re
 
 import torch
 
 from .. import _lib
+from .._lib import ptr as _ptr
 
 __all__ = ["gaussian_scale_space", "scale_space_warp", "scale_space_predict", "gaussian_scale_space_reference",
            "scale_space_warp_reference", "scale_space_predict_reference", "scale_space_radii",
            "SCALE_SPACE_CONSTANTS"]
 
 
-def _kernel_constants():
-    """The named constants of csrc/scale_space_params.h (tile sizes, the argument limits), read from that file."""
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc", "scale_space_params.h")
-    with open(path) as f:
-        found = re.findall(r"constexpr\s+int\s+(SS_[A-Z0-9_]+)\s*=\s*(\d+)\s*;", f.read())
-    if not found:
-        raise RuntimeError(f"no constants found in {path}")
-    return {name: int(value) for name, value in found}
-
-
-SCALE_SPACE_CONSTANTS = _kernel_constants()
+# the named constants of csrc/scale_space_params.h (tile sizes, the argument limits)
+SCALE_SPACE_CONSTANTS = _lib.kernel_constants("scale_space_params.h", ("SS",))
 
 
 def _check_levels(num_levels, sigma0):
@@ -177,10 +167,6 @@ def scale_space_predict_reference(x, flow, num_levels=5, sigma0=1.5):
 
 # -------------------------------------------------------------------------------------------------------------------
 # the kernels
-
-
-def _ptr(t):
-    return 0 if t is None else t.data_ptr()
 
 
 def _volume_kernel(x, num_levels, sigma0):

@@ -45,7 +45,7 @@ def _mode_code(mode) -> int:
         raise ValueError(f"mode must be one of 'auto', 'latency', 'throughput': {mode!r}")
     return _MODES[mode]
 
-_DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+_DTYPE_CODE = _lib.DTYPE_CODE_F16
 
 
 def _dev_i32(t, device):

@@ -18,6 +18,7 @@ import numbers
 import torch
 
 from .. import _lib
+from .._lib import ptr as _ptr
 
 __all__ = ["ssim", "ssim_multiscale", "ssim_reference", "ssim_multiscale_reference", "MSSSIM_POWER_FACTORS"]
 
@@ -139,10 +140,6 @@ def ssim_multiscale_reference(img1, img2, max_val, power_factors=MSSSIM_POWER_FA
 
 def _taps_arg(taps):
     return (C.c_float * len(taps))(*taps)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def scale_forward(x, y, taps, c1, c2, pool):

@@ -20,29 +20,19 @@ PM_MIN_C..PM_MAX_C, PM_MIN_H..PM_MAX_H take it."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import torch
 
 from .. import _lib
+from .._lib import ptr as _ptr
 
 __all__ = ["RahtTree", "PointBlocks", "raht_synthesize", "raht_synthesize_reference", "point_mlp_loss",
            "point_mlp_loss_reference", "point_mlp_eligible", "LVAC_CONSTANTS", "RGB_TO_YUV", "YUV_TO_RGB", "IDENTITY"]
 
 
-def _kernel_constants():
-    """The named constants of csrc/lvac_params.h (tile sizes, the eligibility range), read from that file."""
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc", "lvac_params.h")
-    with open(path) as f:
-        found = re.findall(r"constexpr\s+int\s+((?:RAHT|PM)_[A-Z0-9_]+)\s*=\s*(\d+)\s*;", f.read())
-    if not found:
-        raise RuntimeError(f"no constants found in {path}")
-    return {name: int(value) for name, value in found}
-
-
-LVAC_CONSTANTS = _kernel_constants()
+# the named constants of csrc/lvac_params.h (tile sizes, the eligibility range)
+LVAC_CONSTANTS = _lib.kernel_constants("lvac_params.h", ("RAHT", "PM"))
 
 # The output maps as (A row-major, o): recon = A y + o.  The notebook's coefficients (not those of rgb_to_ycbcr).
 IDENTITY = ((1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0), (0.0, 0.0, 0.0))
@@ -51,10 +41,6 @@ RGB_TO_YUV = ((0.212600, 0.715200, 0.072200, -0.114572, -0.385428, 0.5, 0.5, -0.
 # r = y + 1.57480 (v - 128) and so on: the offsets are the matrix applied to (0, -128, -128)
 YUV_TO_RGB = ((1.0, 0.0, 1.57480, 1.0, -0.18733, -0.46813, 1.0, 1.85563, 0.0),
               (-128.0 * 1.57480, 128.0 * (0.18733 + 0.46813), -128.0 * 1.85563))
-
-
-def _ptr(t):
-    return 0 if t is None else t.data_ptr()
 
 
 # ------------------------------------------------------------------------------------------------------------------

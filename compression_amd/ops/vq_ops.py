@@ -12,12 +12,11 @@ the gradients for codebook, rates and x are a gather in a fixed order (bit-ident
 from __future__ import annotations
 
 import math
-import os
-import re
 
 import torch
 
 from .. import _lib
+from .._lib import ptr as _ptr
 
 __all__ = ["ecvq_assign", "ecvq_counts", "ecvq_assign_reference", "VQ_CONSTANTS"]
 
@@ -26,21 +25,8 @@ REFERENCE_CHUNK_ROWS = 1024     # rows of the cost matrix `ecvq_assign_reference
 REFERENCE_CHUNK_ELEMENTS = 1 << 24   # and elements of the [rows, K, D] difference it is summed from, at most
 
 
-def _kernel_constants():
-    """The named constants of csrc/vecvq_params.h (tile sizes, the narrow / wide boundary), read from that file."""
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc", "vecvq_params.h")
-    with open(path) as f:
-        found = re.findall(r"constexpr\s+int\s+(VQ_[A-Z0-9_]+)\s*=\s*(\d+)\s*;", f.read())
-    if not found:
-        raise RuntimeError(f"no constants found in {path}")
-    return {name: int(value) for name, value in found}
-
-
-VQ_CONSTANTS = _kernel_constants()
-
-
-def _ptr(t):
-    return 0 if t is None else t.data_ptr()
+# the named constants of csrc/vecvq_params.h (tile sizes, the narrow / wide boundary)
+VQ_CONSTANTS = _lib.kernel_constants("vecvq_params.h", ("VQ",))
 
 
 def _check_args(x, codebook, rates, lmbda, distortion, dtypes):
