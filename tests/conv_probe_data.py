@@ -1,0 +1,287 @@
+"""Data that is exact by construction for two places where small integers are blind (tests/test_conv_probes_cpu.py
+proves its power without a device, tests/test_conv_probes_gpu.py runs it on the kernels).
+
+1. Plane probes: the float32 layers on the bfloat16 matrix cores (csrc/conv_shared.h split3, x_plane / w_plane; the
+   literal plane[6] of conv_split_w_kernel).  A float32 operand is split into three bfloat16 planes and six of the nine
+   plane products are kept, q = 0 ... 5: x planes [1 1 1 2 2 3] against w planes [1 2 3 1 2 1].  An integer below 256 is
+   one bfloat16, so five of the six products are zero in every integer test.
+
+   A probe value is  sign * sum_k d_k 2^(-9 k),  d_k in {0, 1}, k < levels, a random sign, zero with probability
+   1 - density.  The digit spacing is 9 bits: a bfloat16 keeps 8 significant bits, the next digit is below half a unit
+   of the leading one, so split3 rounds DOWN to the leading digit and leaves the rest — the i-th non-zero digit of a
+   value is its plane i (1 + 2^-9 + 2^-18 -> 1, 2^-9, 2^-18), and a value of `levels` digits has no plane beyond
+   `levels`.  (At 8 bits 1 + 2^-8 + 2^-16 rounds up, and the remainder fits one bfloat16: plane 3 stays empty.)
+
+       probe      x levels  w levels  products that are not identically zero
+       x12_w12    2         2         0, 1, 3, 4   (x1 w1, x1 w2, x2 w1, x2 w2)
+       x123_w1    3         1         0, 3, 5      (adds x3 w1)
+       x1_w123    1         3         0, 1, 2      (adds x1 w3)
+
+   The three products the scheme discards (x2 w3, x3 w2, x3 w3) are identically zero for all three.  Every kept product
+   is a multiple of 2^-18; where the sum of absolute values per output — the float64 oracle on |x|, |w| (and |bias|),
+   the way test_signal_conv_grad_gpu.check_module forms abs_y — is below ABS_SUM_BOUND = 2^4, every partial sum in any
+   order is a multiple of 2^-18 below 2^4: 22 bits, two to spare in float32.  The float32 result must then EQUAL the
+   float64 oracle.  The bound is a condition on the data, asserted for every case; it is no tolerance.
+
+   Density: 2.4 / sqrt(K), K the products an output sums (taps x Cin; behind an upsampling the taps of one phase at the
+   most, ceil(k / s) per axis) — about 5.8 non-zero candidates per output at every K.  Largest abs-sum the oracle
+   reported over the three probes of the cases below, and the smallest share of non-zero outputs (required: above a
+   half):
+
+       K      density  largest abs-sum  non-zero outputs   cases
+       80     0.268    8.0              0.88               rank 3, support (1, 1, 5), both directions
+       144    0.200    9.0              0.71               3x3 16 -> 8, transposed 5x5 x2 16 -> 8 and 16 -> 128
+       192    0.173    6.0              0.55               rank 3 transposed, support (3, 3, 3) x (1, 2, 2)
+       256    0.150    10.0             0.73               4x4 /2 16 -> 40, and its three-image batch
+       400    0.120    11.0             0.88               5x5 /2 16 -> 128
+       432    0.115    7.0              0.79               rank 3, support (3, 3, 3)
+       576    0.100    6.0              0.70               transposed 5x5 x2 64 -> 4
+
+   (The transposed cases count the taps of the fullest phase; the other phases sum fewer products, hence their lower
+   shares.)  The input-gradient cases, on |gy|, |w|: 8.0 at the most, 0.55 non-zero at the least.
+
+2. Impulse responses: the bfloat16 kernels' rounding of their float32 weights (pack_bf16 and the casts of the packing
+   kernels).  x is bfloat16 zeros with isolated ones, the weights are full-mantissa float32, the oracle runs on
+   w.bfloat16().float() (torch's CPU cast rounds to nearest, ties to even).  No output receives two impulses, so each
+   output is 0 or one rounded weight and the bfloat16 output must EQUAL the oracle; every weight element reaches some
+   output.  Planted among normal weights: exact ties (2 m + 1) 2^-8 2^e with both parities of the kept bit m, one
+   float32 unit either side of each, and the negatives of all of these."""
+import functools
+import math
+
+import numpy as np
+import torch
+
+import signal_conv_oracle as so
+
+SPACING = 9                              # bits between a probe value's digits
+ABS_SUM_BOUND = 16.0                     # per output, of |x| |w| (+ |bias|): every partial sum then fits 22 bits
+# the six kept plane products, restated (not read from the library): x plane, w plane of product q, counted from 0
+X_PLANE = (0, 0, 0, 1, 1, 2)
+W_PLANE = (0, 1, 2, 0, 1, 0)
+PROBES = {                               # name -> (x levels, w levels, products that are not identically zero)
+    "x12_w12": (2, 2, (0, 1, 3, 4)),
+    "x123_w1": (3, 1, (0, 3, 5)),
+    "x1_w123": (1, 3, (0, 1, 2)),
+}
+
+
+def case(name, up, n, extent, cin, cout, support, strides):
+    return dict(name=name, up=up, n=n, extent=tuple(extent), cin=cin, cout=cout, support=tuple(support),
+                strides=tuple(strides))
+
+
+def case_id(c):
+    return c["name"]
+
+
+def oracle_args(c):
+    """What conv2d_down / conv3d_down (correlation, `same_zeros`, strides down) and conv2d_up / conv3d_up (transposed
+    convolution, `same_zeros`, extra_pad_end) compute, in signal_conv_oracle.layer_oracle's terms."""
+    one = (1,) * len(c["extent"])
+    return dict(corr=not c["up"], strides_down=one if c["up"] else c["strides"],
+                strides_up=c["strides"] if c["up"] else one, padding="same_zeros", extra_pad_end=True)
+
+
+def oracle(c, x, w, bias=None, activation=None):
+    return so.layer_oracle(x, w, bias=bias, activation=activation, **oracle_args(c))
+
+
+def abs_sum(c, x, w, bias=None):
+    """Per output the sum of |x| |w| over its products, plus |bias|: the float64 oracle on the absolute values."""
+    return oracle(c, x.abs(), w.abs(), None if bias is None else bias.abs())
+
+
+def products_per_output(c, channels=None):
+    taps = math.prod(-(-k // s) for k, s in zip(c["support"], c["strides"])) if c["up"] else math.prod(c["support"])
+    return taps * (c["cin"] if channels is None else channels)
+
+
+def density_for(k):
+    return 2.4 / math.sqrt(k)
+
+
+def probe_values(shape, levels, density, rng):
+    digits = rng.integers(0, 2, (levels,) + tuple(shape))
+    magnitude = sum(digits[k] * 2.0 ** (-SPACING * k) for k in range(levels))
+    sign = rng.choice([-1.0, 1.0], tuple(shape))
+    keep = rng.random(tuple(shape)) < density
+    return torch.from_numpy((sign * magnitude * keep).astype(np.float32))
+
+
+def _seed(c, probe, salt=0):
+    return sum(map(ord, c["name"] + probe)) * 7 + salt
+
+
+@functools.lru_cache(maxsize=None)
+def _probe_data(key, probe):
+    c = _BY_NAME[key]
+    x_levels, w_levels, _ = PROBES[probe]
+    rng = np.random.default_rng(_seed(c, probe))
+    density = density_for(products_per_output(c))
+    x = probe_values((c["n"],) + c["extent"] + (c["cin"],), x_levels, density, rng)
+    w = probe_values(c["support"] + (c["cin"], c["cout"]), w_levels, density, rng)
+    return x, w, oracle(c, x, w)
+
+
+def probe_data(c, probe):
+    """-> (x channels-last float32, kernel [*support, Cin, Cout] float32, the float64 oracle's output), made once."""
+    return _probe_data(c["name"], probe)
+
+
+def integer_bias(c, probe):
+    """Integers in -3 ... 3: exact in every plane-1 sum, and counted in the abs-sum condition."""
+    rng = np.random.default_rng(_seed(c, probe, 1))
+    return torch.from_numpy(rng.integers(-3, 4, (c["cout"],)).astype(np.float32))
+
+
+@functools.lru_cache(maxsize=None)
+def _gradient_data(key, probe):
+    """The input gradient is the other direction's kernel on the cotangent: the cotangent from the x-side grid, the
+    kernel from the w-side grid -> (x, kernel, gy, the oracle's dx, the abs-sum of dx: the oracle's autograd on |gy|, |w|)."""
+    c = _BY_NAME[key]
+    x_levels, w_levels, _ = PROBES[probe]
+    rng = np.random.default_rng(_seed(c, probe, 2))
+    other = dict(c, up=not c["up"])
+    density = density_for(products_per_output(other, c["cout"]))
+    w = probe_values(c["support"] + (c["cin"], c["cout"]), w_levels, density, rng)
+    x = probe_values((c["n"],) + c["extent"] + (c["cin"],), 1, density, rng)
+    xd = x.double().requires_grad_(True)
+    y = oracle(c, xd, w)
+    gy = probe_values(tuple(y.shape), x_levels, density, rng)
+    y.backward(gy.double())
+    xa = x.double().requires_grad_(True)
+    oracle(c, xa, w.abs()).backward(gy.abs().double())
+    return x, w, gy, xd.grad, xa.grad
+
+
+def gradient_data(c, probe):
+    return _gradient_data(c["name"], probe)
+
+
+# ---- the cases of the float32 tier (the GPU file says per case which route's eligibility test admits it) -------------
+PLANE_CASES_2D = [
+    case("down-3x3-16-8", False, 1, (9, 11), 16, 8, (3, 3), (1, 1)),
+    case("down-4x4s2-16-40", False, 1, (10, 7), 16, 40, (4, 4), (2, 2)),
+    case("up-5x5s2-64-4", True, 1, (8, 7), 64, 4, (5, 5), (2, 2)),
+    case("up-5x5s2-16-8", True, 1, (7, 9), 16, 8, (5, 5), (2, 2)),
+    case("down-5x5s2-16-128-blocks", False, 1, (32, 128), 16, 128, (5, 5), (2, 2)),
+    case("up-5x5s2-16-128-blocks", True, 1, (16, 64), 16, 128, (5, 5), (2, 2)),
+]
+CHUNKED_CASE = case("down-4x4s2-16-40-three-images", False, 3, (20, 20), 16, 40, (4, 4), (2, 2))
+PLANE_CASES_3D = [
+    case("down3d-333-s111", False, 1, (4, 6, 9), 16, 16, (3, 3, 3), (1, 1, 1)),
+    case("down3d-115-s122", False, 2, (3, 8, 37), 16, 16, (1, 1, 5), (1, 2, 2)),
+    case("up3d-333-s122", True, 1, (3, 5, 7), 16, 16, (3, 3, 3), (1, 2, 2)),
+    case("up3d-115-s111", True, 2, (2, 3, 35), 16, 16, (1, 1, 5), (1, 1, 1)),
+]
+GRADIENT_CASES = [
+    case("grad-down-5x5s2-16-16", False, 1, (9, 12), 16, 16, (5, 5), (2, 2)),
+    case("grad-up-5x5s2-16-16", True, 1, (6, 7), 16, 16, (5, 5), (2, 2)),
+    case("grad-down3d-333-s122", False, 1, (3, 6, 9), 16, 16, (3, 3, 3), (1, 2, 2)),
+    case("grad-up3d-115-s122", True, 1, (2, 4, 19), 16, 16, (1, 1, 5), (1, 2, 2)),
+]
+BIAS_RELU_CASE = PLANE_CASES_2D[1]
+PLANE_CASES = PLANE_CASES_2D + [CHUNKED_CASE] + PLANE_CASES_3D
+
+
+# ---- impulse responses ---------------------------------------------------------------------------------------------
+def impulse_input(c):
+    """bfloat16 zeros with isolated ones on a lattice, cycling over the input channels and, in front of a stride, over
+    the positions modulo the stride (a tap t of a strided correlation only meets inputs at p = o s + t - k // 2); as
+    many images as the cycle needs.  Margins keep every tap of an impulse inside the output."""
+    k, s, extent, cin = c["support"], c["strides"], c["extent"], c["cin"]
+    rank = len(k)
+    if c["up"]:
+        pitch = [-(-k[a] // s[a]) for a in range(rank)]
+        margin = [-(-(k[a] - 1) // s[a]) for a in range(rank)]
+        residues = [(0,) * rank]
+    else:
+        pitch = [-(-(k[a] + s[a] - 1) // s[a]) * s[a] for a in range(rank)]      # a multiple of the stride: the residues stay
+        margin = [k[a] - 1 for a in range(rank)]
+        residues = list(np.ndindex(*s))
+    counts = [(extent[a] - 2 * margin[a] - (0 if c["up"] else s[a] - 1) - 1) // pitch[a] + 1 for a in range(rank)]
+    assert all(n >= 1 for n in counts), (c["name"], counts)
+    sites = list(np.ndindex(*counts))
+    needed = cin * len(residues)
+    images = -(-needed // len(sites))
+    x = torch.zeros((images,) + tuple(extent) + (cin,))
+    for j in range(images * len(sites)):
+        site, residue = sites[j % len(sites)], residues[(j // cin) % len(residues)]
+        at = tuple(margin[a] + site[a] * pitch[a] + residue[a] for a in range(rank))
+        x[(j // len(sites),) + at + (j % cin,)] = 1.0
+    return x.bfloat16()
+
+
+def _bits(a):
+    return a.numpy().view(np.uint32)
+
+
+def truncated(w):
+    return torch.from_numpy((_bits(w) & np.uint32(0xFFFF0000)).view(np.float32))
+
+
+def rounded_half_away(w):
+    return torch.from_numpy(((_bits(w) + np.uint32(0x8000)) & np.uint32(0xFFFF0000)).view(np.float32))
+
+
+def rounded_twice(w):
+    """To nearest even at 16 mantissa bits first, then at bfloat16's 8: up through a tie from one unit below it."""
+    def nearest_even(bits, drop):
+        bits = bits + np.uint32((1 << (drop - 1)) - 1) + ((bits >> np.uint32(drop)) & np.uint32(1))
+        return bits & ~np.uint32((1 << drop) - 1)
+    return torch.from_numpy(nearest_even(nearest_even(_bits(w).copy(), 8), 16).view(np.float32))
+
+
+def rounding_weights(shape, seed):
+    """-> (float32 weights, flat indices of the planted exact ties).  Normal values with full mantissas; planted at
+    random places over taps, input and output channels: ties (2 m + 1) 2^-8 2^e, m in 128 ... 255 of both parities
+    (the kept bit), one float32 unit below and above each, and the negatives of all of them."""
+    rng = np.random.default_rng(seed)
+    w = rng.standard_normal(shape).astype(np.float32)
+    ties = np.array([(2 * m + 1) * 2.0 ** (e - 8) for e in (-5, -2, 0) for m in (128, 129, 170, 171, 254, 255)],
+                    dtype=np.float32)
+    below, above = np.nextafter(ties, np.float32(0)), np.nextafter(ties, np.float32(4))
+    planted = np.concatenate([ties, -ties, below, -below, above, -above])
+    assert planted.size <= w.size // 4
+    at = rng.choice(w.size, planted.size, replace=False)
+    w.reshape(-1)[at] = planted
+    return torch.from_numpy(w), torch.from_numpy(at[:2 * ties.size])
+
+
+IMPULSE_CASES = [
+    case("gemm2-down-3x3-16-8", False, 0, (12, 20), 16, 8, (3, 3), (1, 1)),
+    case("gemm2-down-4x4s2-16-40", False, 0, (24, 32), 16, 40, (4, 4), (2, 2)),
+    case("gemm2-up-5x5s2-16-8", True, 0, (9, 13), 16, 8, (5, 5), (2, 2)),
+    case("gemm2-up-compact-5x5s2-16-192", True, 0, (9, 13), 16, 192, (5, 5), (2, 2)),
+    case("gemm3-down-5x5s2-16-128", False, 0, (32, 128), 16, 128, (5, 5), (2, 2)),
+    case("gemm3-up-5x5s2-32-128", True, 0, (16, 64), 32, 128, (5, 5), (2, 2)),
+    case("up-fused-5x5s2-64-2", True, 0, (9, 33), 64, 2, (5, 5), (2, 2)),
+    case("up-gather-5x5s2-16-3", True, 0, (9, 13), 16, 3, (5, 5), (2, 2)),
+    case("up-phase-5x5s2-64-3", True, 0, (11, 35), 64, 3, (5, 5), (2, 2)),
+    case("up-phase-9x9s4-32-3", True, 0, (11, 35), 32, 3, (9, 9), (4, 4)),
+    case("image-5x5s2-3-128", False, 0, (20, 64), 3, 128, (5, 5), (2, 2)),
+    case("image-direct-5x5s2-3-192", False, 0, (20, 64), 3, 192, (5, 5), (2, 2)),
+    case("image-direct-9x9s4-3-192", False, 0, (40, 128), 3, 192, (9, 9), (4, 4)),
+    case("gemm1-image-9x9s4-3-32", False, 0, (40, 60), 3, 32, (9, 9), (4, 4)),
+    case("down3d-335-s122", False, 0, (6, 14, 32), 16, 16, (3, 3, 5), (1, 2, 2)),
+    case("up3d-335-s122", True, 0, (5, 5, 9), 16, 16, (3, 3, 5), (1, 2, 2)),
+]
+
+
+@functools.lru_cache(maxsize=None)
+def _impulse_data(key):
+    c = _BY_NAME[key]
+    x = impulse_input(c)
+    w, ties = rounding_weights(c["support"] + (c["cin"], c["cout"]), _seed(c, "impulse"))
+    return x, w, ties, oracle(c, x.float(), w.bfloat16().float())
+
+
+def impulse_data(c):
+    """-> (x bfloat16, float32 weights, indices of the planted ties, the float64 oracle on the weights rounded to nearest
+    even), made once."""
+    return _impulse_data(c["name"])
+
+
+_BY_NAME = {c["name"]: c for c in PLANE_CASES + GRADIENT_CASES + IMPULSE_CASES}
+assert len(_BY_NAME) == len(PLANE_CASES + GRADIENT_CASES + IMPULSE_CASES)
