@@ -21,6 +21,10 @@ from .ops.flow_ops import (gaussian_scale_space, gaussian_scale_space_reference,
                            scale_space_predict_reference, scale_space_warp, scale_space_warp_reference)
 from .ops.context_ops import (ContextParams, ContextScan, context_decode, context_parameters_reference,  # noqa: F401
                               context_scan, context_scan_reference)
+from .ops.checkerboard_ops import (CHECKER_TAPS, CheckerboardParams, CheckerboardScan, anchor_mask,  # noqa: F401
+                                   checkerboard_decode, checkerboard_mask, checkerboard_merge, checkerboard_parameters,
+                                   checkerboard_parameters_reference, checkerboard_place, checkerboard_scan,
+                                   checkerboard_scan_reference, checkerboard_split)
 from .ops.round_ops import round_st, soft_round, soft_round_conditional_mean, soft_round_inverse  # noqa: F401
 from .datasets import *  # noqa: F401,F403
 from .datasets.clip_dataset import ClipDataset  # noqa: F401

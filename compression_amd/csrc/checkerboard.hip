@@ -1,0 +1,389 @@
+// The checkerboard context model of He, Zheng, Sun, Wang and Qin, "Checkerboard context model for efficient learned
+// image compression" (CVPR 2021) on gfx950: for all positions of one pass, the masked 5x5 correlation over the decoded
+// anchors, the pointwise entropy-parameter network and the quantisation, in ONE launch per pass
+// (checkerboard_params_kernel), and the decoder's store of a decoded pass (checkerboard_place_kernel).
+// include/tfc_hip.h states the definition.
+//
+// A workgroup of CKB_THREADS threads owns CKB_TILE = 32 consecutive compact positions of one image and runs the four
+// dense layers on v_mfma_f32_32x32x2_f32: the 32 positions are the rows of the A operand, 32 output columns the
+// columns of B, and a wave accumulates up to CKB_BLOCKS column blocks side by side (16 accumulator registers each)
+// while it walks K.  That instruction is bit for bit D = fmaf(a[k+1], b[k+1], fmaf(a[k], b[k], C)), so every output
+// element is ONE chain: its bias, then one fmaf per input row in ascending k (for the correlation: taps in row-major
+// order, the channels of a tap ascending, a neighbour outside the latent contributing fmaf(0, w, acc); for the first
+// layer: the 2M context features, then the P hyperprior features).  Rows and columns of an MFMA do not interact,
+// so the chain depends on (M, P, H1, H2) alone: not on the batch, the tile, the slot in the tile or the neighbours
+// that exist.  Encoder and decoder run this kernel.
+//
+// Activations stay in LDS between the layers, k-major: row k holds the 32 positions' values of feature k, so the A
+// operand of k-step s is the 64 consecutive floats at row 2 s, one ds_read_b32 without a bank conflict, and an
+// accumulator column goes back as four 16-byte stores.  Buffer A holds ctx, then h2; buffer B holds h1, then the
+// output; a third region stages the gathered inputs (a tap's y_hat rows, psi) CKB_STAGE_K rows at a time, the next
+// chunk's global loads in flight while the current one is multiplied.  [ctx, psi] are two K ranges of the first layer.
+// With the model's widths A is 64 KiB and B 80 KiB: the kernel declares gfx950's whole 160 KiB of LDS, on purpose
+// (one workgroup of four waves per CU, one wave per SIMD, which is what the f32 MFMA needs to reach its rate).
+//
+// Weights: no two waves of a workgroup use the same weight element (a wave owns its columns for all 32 positions),
+// so a trip through LDS would add traffic and save none; each lane loads its B operand, one float of the packed
+// buffer, straight into a register, 128 contiguous bytes per half wave, eight k-steps ahead.  The whole packed buffer
+// is read once per tile of 32 positions.
+//
+// Nothing waits on another workgroup; every loop bound comes from the shapes.  In pass 1 the kernel reads y_hat at
+// anchors only and writes it at the other positions only, so concurrent workgroups never touch the same element.
+#include "common.h"
+#include "context_params.h"
+#include "mfma_types.h"
+
+#include "../../include/tfc_hip.h"
+
+namespace tfc {
+namespace {
+
+struct CkbArgs {
+  ContextLayout L;
+  int pass, hl, wl, num_scales;
+  int64_t positions;        // of this pass, per image
+  int64_t tiles;            // per image
+  const float* packed;
+  const float* psi;         // [B, Hl, Wl, P]
+  const float* y;           // [B, Hl, Wl, M] or null
+  float* y_hat;             // [B, Hl, Wl, M]
+  float* mu;                // [B, positions, M]
+  float* index_float;
+  int32_t* idx;
+  int32_t* sym;
+};
+
+__device__ __forceinline__ float ckb_lrelu(float v) { return v > 0.f ? v : 0.2f * v; }
+
+// tfc_index_prepare's value (csrc/elementwise.hip)
+__device__ __forceinline__ int32_t ckb_index(float v, float hi) { return static_cast<int32_t>(fminf(fmaxf(v, 0.f), hi)); }
+
+// Compact slot -> raster index i * Wl + j of the position
+__device__ __forceinline__ void ckb_position(int64_t slot, int pass, int wl, int* i, int* j) {
+  if (wl & 1) {
+    const int64_t n = 2 * slot + pass;
+    *i = static_cast<int>(n / wl);
+    *j = static_cast<int>(n - static_cast<int64_t>(*i) * wl);
+  } else {
+    const int half = wl >> 1;
+    *i = static_cast<int>(slot / half);
+    const int c = static_cast<int>(slot - static_cast<int64_t>(*i) * half);
+    *j = 2 * c + ((*i + pass) & 1);
+  }
+}
+
+// acc[q] += in[0 .. Kp) x w[0 .. Kp)[col q], k ascending.  `in` is LDS, k-major rows of CKB_TILE floats; `wq[q]` points
+// at w[lane >> 5][column of block q for this lane]; Kp is a multiple of CTX_KPAD, so it is even.
+template <int NQ>
+__device__ __forceinline__ void ckb_mma(f32x16 (&acc)[NQ], const float* in, int Kp, const float* (&wq)[NQ], int O) {
+  constexpr int G = CKB_GROUP;
+  const int lane = threadIdx.x & 63;
+  const float* a = in + lane;
+  const size_t step = 2 * static_cast<size_t>(O);
+  const int steps = Kp >> 1, groups = steps / G;
+  // whole groups of G k-steps: the next group's weights are on their way while this one is multiplied
+  float next[G][NQ];
+  auto load = [&](int g) {
+#pragma unroll
+    for (int u = 0; u < G; ++u)
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) next[u][q] = wq[q][static_cast<size_t>(g * G + u) * step];
+  };
+  if (groups > 0) load(0);
+  for (int g = 0; g < groups; ++g) {
+    float av[G], bv[G][NQ];
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      av[u] = a[static_cast<size_t>(g * G + u) * (2 * CKB_TILE)];
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) bv[u][q] = next[u][q];
+    }
+    if (g + 1 < groups) load(g + 1);
+#pragma unroll
+    for (int u = 0; u < G; ++u)
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u][q], acc[q], 0, 0, 0);
+  }
+  for (int s = groups * G; s < steps; ++s) {
+    const float av = a[static_cast<size_t>(s) * (2 * CKB_TILE)];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+      acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, wq[q][static_cast<size_t>(s) * step], acc[q], 0, 0, 0);
+  }
+}
+static_assert(CTX_KPAD % 2 == 0, "a k-step of the MFMA is two input rows");
+
+// What a thread fetches of one staged chunk: position (tid & 31) of the tile, 8 consecutive input rows.
+constexpr int CKB_STAGE_PER_THREAD = CKB_STAGE_K * CKB_TILE / CKB_THREADS;
+static_assert(CKB_STAGE_PER_THREAD * (CKB_THREADS / CKB_TILE) == CKB_STAGE_K, "a chunk is 8 row groups of 32 positions");
+
+struct CkbTile {
+  int b, np;                // image, live positions of the tile
+  int pi, pj;               // this thread's staged position (tid & 31), or pi < 0 when it is beyond the pass
+};
+
+// One layer for the tile: out (k-major, LDS) = act(bias + chain).  The chain takes the LDS-resident rows [0, Kl) of
+// `in` against wl first, then `taps` staged segments: rows [0, Cp) of src[the position, moved by the tap when
+// `shifted`][C channels] against wseg + tap * Cp * O.  A wave accumulates NQ column blocks side by side (blocks
+// wave, wave + 4, ...); NQ is the same for the whole workgroup, and a block beyond the layer's width computes a
+// live column again and drops it.  All threads of the workgroup call it together.  `store` receives (column, first
+// of four positions, the four values).
+template <int NQ, typename Store>
+__device__ __forceinline__ void ckb_layer(const CkbArgs& a, const CkbTile& t, float* stage, const float* in, int Kl,
+                                          const float* wl, const float* src, int C, int Cp, int taps, bool shifted,
+                                          const float* wseg, const float* bias, int O, int Op, Store store) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  const int col = lane & 31, kk = lane >> 5;
+  const int nblk = (Op + 31) >> 5;
+  const int spos = threadIdx.x & (CKB_TILE - 1), sk = (threadIdx.x / CKB_TILE) * CKB_STAGE_PER_THREAD;
+  const int per_tap = (Cp + CKB_STAGE_K - 1) / CKB_STAGE_K;
+  const int chunks = taps * per_tap;
+
+  for (int base = 0; base < nblk; base += (CKB_THREADS / 64) * NQ) {
+    f32x16 acc[NQ];
+    const float* wq[NQ];
+    int cq[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      cq[q] = (base + wave + 4 * q) * 32 + col;
+      const int c = min(cq[q], O - 1);
+      const float bv = bias[c];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[q][r] = bv;
+      wq[q] = wl + static_cast<size_t>(kk) * O + c;
+    }
+    if (Kl > 0) ckb_mma<NQ>(acc, in, Kl, wq, O);
+    if (chunks > 0) {
+      float r[CKB_STAGE_PER_THREAD];
+      auto fetch = [&](int c) {
+        const int tap = c / per_tap, k0 = (c - tap * per_tap) * CKB_STAGE_K + sk;
+        int ii = t.pi, jj = t.pj;
+        if (shifted) {
+          ii += ckb_tap_di(tap);
+          jj += ckb_tap_dj(tap);
+        }
+        const bool live = t.pi >= 0 && ii >= 0 && ii < a.hl && jj >= 0 && jj < a.wl;
+        const float* row = src + ((static_cast<int64_t>(t.b) * a.hl + (live ? ii : 0)) * a.wl + (live ? jj : 0)) * C;
+#pragma unroll
+        for (int e = 0; e < CKB_STAGE_PER_THREAD; ++e) r[e] = (live && k0 + e < C) ? row[k0 + e] : 0.f;
+      };
+      fetch(0);
+      for (int c = 0; c < chunks; ++c) {
+        const int tap = c / per_tap, k0 = (c - tap * per_tap) * CKB_STAGE_K;
+        const int kn = min(CKB_STAGE_K, Cp - k0);
+#pragma unroll
+        for (int e = 0; e < CKB_STAGE_PER_THREAD; ++e) stage[(sk + e) * CKB_TILE + spos] = r[e];
+        __syncthreads();
+        if (c + 1 < chunks) fetch(c + 1);
+        const float* wb = wseg + (static_cast<size_t>(tap) * Cp + k0 + kk) * O;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) wq[q] = wb + min(cq[q], O - 1);
+        ckb_mma<NQ>(acc, stage, kn, wq, O);
+        __syncthreads();
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      if (cq[q] < Op) {
+        const bool live = cq[q] < O;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          f32x4 v;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = live ? acc[q][4 * g + e] : 0.f;
+          store(cq[q], 8 * g + 4 * kk, v);
+        }
+      }
+    }
+  }
+}
+
+// ckb_layer with the block count of the layer's width: ceil(blocks / 4), at most CKB_BLOCKS (wider layers take turns)
+template <typename Store>
+__device__ __forceinline__ void ckb_layer_n(const CkbArgs& a, const CkbTile& t, float* stage, const float* in, int Kl,
+                                            const float* wl, const float* src, int C, int Cp, int taps, bool shifted,
+                                            const float* wseg, const float* bias, int O, int Op, Store store) {
+  const int per_wave = (((Op + 31) >> 5) + 3) >> 2;
+  switch (per_wave) {                 // the same for every thread of the grid
+    case 1: ckb_layer<1>(a, t, stage, in, Kl, wl, src, C, Cp, taps, shifted, wseg, bias, O, Op, store); break;
+    case 2: ckb_layer<2>(a, t, stage, in, Kl, wl, src, C, Cp, taps, shifted, wseg, bias, O, Op, store); break;
+    case 3: ckb_layer<3>(a, t, stage, in, Kl, wl, src, C, Cp, taps, shifted, wseg, bias, O, Op, store); break;
+    case 4: ckb_layer<4>(a, t, stage, in, Kl, wl, src, C, Cp, taps, shifted, wseg, bias, O, Op, store); break;
+    default: ckb_layer<CKB_BLOCKS>(a, t, stage, in, Kl, wl, src, C, Cp, taps, shifted, wseg, bias, O, Op, store); break;
+  }
+}
+static_assert(CKB_BLOCKS == 5, "ckb_layer_n lists the block counts");
+
+template <int PASS>
+__global__ void __launch_bounds__(CKB_THREADS) checkerboard_params_kernel(const CkbArgs a) {
+  __shared__ __attribute__((aligned(16))) float lds[CKB_LDS_FLOATS];
+  const ContextLayout& L = a.L;
+  const int M = L.m;
+  const int b = static_cast<int>(blockIdx.x / a.tiles);
+  const int64_t slot0 = (blockIdx.x - static_cast<int64_t>(b) * a.tiles) * CKB_TILE;
+  float* bufA = lds;
+  float* bufB = bufA + static_cast<size_t>(L.a_floats) * CKB_TILE;
+  float* stage = bufB + static_cast<size_t>(L.b_floats) * CKB_TILE;
+
+  CkbTile t;
+  t.b = b;
+  t.np = static_cast<int>(min<int64_t>(CKB_TILE, a.positions - slot0));
+  {
+    const int sp = threadIdx.x & (CKB_TILE - 1);
+    t.pi = -1;
+    t.pj = 0;
+    if (sp < t.np) ckb_position(slot0 + sp, PASS, a.wl, &t.pi, &t.pj);
+  }
+  auto to = [](float* buf, bool lrelu) {
+    return [buf, lrelu](int col, int pos, f32x4 v) {
+      if (lrelu) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = ckb_lrelu(v[e]);
+      }
+      *reinterpret_cast<f32x4*>(buf + static_cast<size_t>(col) * CKB_TILE + pos) = v;
+    };
+  };
+
+  // ctx -> A: the bias alone for the anchors, the bias and the 12 taps' chain for the rest
+  if (PASS == 0) {
+    const float* bc = a.packed + L.bc;
+    for (int e = threadIdx.x; e < L.c2p * CKB_TILE; e += CKB_THREADS) {
+      const int k = e / CKB_TILE;
+      bufA[e] = k < L.c2 ? bc[k] : 0.f;
+    }
+  } else {
+    ckb_layer_n(a, t, stage, nullptr, 0, a.packed, a.y_hat, M, L.mp, CTX_TAPS, true, a.packed + L.wc, a.packed + L.bc,
+              L.c2, L.c2p, to(bufA, false));
+  }
+  __syncthreads();
+  // h1 -> B: the context rows from A, then the hyperprior rows staged from psi
+  ckb_layer_n(a, t, stage, bufA, L.c2p, a.packed + L.w1c, a.psi, L.p, L.pp, 1, false, a.packed + L.w1p, a.packed + L.b1,
+            L.h1, L.h1p, to(bufB, true));
+  __syncthreads();
+  ckb_layer_n(a, t, stage, bufB, L.h1p, a.packed + L.w2, nullptr, 0, 0, 0, false, nullptr, a.packed + L.b2, L.h2, L.h2p,
+            to(bufA, true));
+  __syncthreads();
+  ckb_layer_n(a, t, stage, bufA, L.h2p, a.packed + L.w3, nullptr, 0, 0, 0, false, nullptr, a.packed + L.b3, L.c2, L.c2,
+            to(bufB, false));
+  __syncthreads();
+
+  // the outputs of the tile, channels innermost
+  const float hi = static_cast<float>(a.num_scales - 1);
+  for (int e = threadIdx.x; e < t.np * M; e += CKB_THREADS) {
+    const int p = e / M, m = e - p * M;
+    const float mu = bufB[static_cast<size_t>(m) * CKB_TILE + p];
+    const float fi = bufB[static_cast<size_t>(M + m) * CKB_TILE + p];
+    const int64_t at = (static_cast<int64_t>(b) * a.positions + slot0 + p) * M + m;
+    a.mu[at] = mu;
+    a.index_float[at] = fi;
+    a.idx[at] = ckb_index(fi, hi);
+    if (a.y) {
+      int i, j;
+      ckb_position(slot0 + p, PASS, a.wl, &i, &j);
+      const int64_t full = ((static_cast<int64_t>(b) * a.hl + i) * a.wl + j) * M + m;
+      const int32_t s = static_cast<int32_t>(rintf(a.y[full] - mu));
+      a.sym[at] = s;
+      a.y_hat[full] = static_cast<float>(s) + mu;
+    }
+  }
+}
+
+struct CkbPlace {
+  int pass, hl, wl, m;
+  int64_t positions, total;     // per image; batch * positions * M
+  const float* sym;
+  const float* mu;
+  float* y_hat;
+};
+
+__global__ void __launch_bounds__(256) checkerboard_place_kernel(const CkbPlace a) {
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < a.total; e += stride) {
+    const int64_t s = e / a.m;
+    const int m = static_cast<int>(e - s * a.m);
+    const int64_t b = s / a.positions;
+    int i, j;
+    ckb_position(s - b * a.positions, a.pass, a.wl, &i, &j);
+    a.y_hat[((b * a.hl + i) * a.wl + j) * a.m + m] = a.sym[e] + a.mu[e];
+  }
+}
+
+}  // namespace
+}  // namespace tfc
+
+extern "C" int tfc_checkerboard_params(int pass, const float* y, float* y_hat, const float* psi, const float* packed,
+                                       int64_t packed_floats, int64_t batch, int64_t hl, int64_t wl, int m, int p,
+                                       int h1, int h2, int num_scales, float* mu, float* index_float, int32_t* idx,
+                                       int32_t* sym, void* stream) {
+  using namespace tfc;
+  const char* name = "tfc_checkerboard_params";
+  CkbArgs a = {};
+  if (const char* e = ctx_layout(m, p, h1, h2, &a.L)) return fail("%s: %s (M %d, P %d, H1 %d, H2 %d)", name, e, m, p, h1, h2);
+  if (const char* e = ctx_check_shape(batch, hl, wl, num_scales, packed_floats, a.L))
+    return fail("%s: %s (batch %lld, Hl %lld, Wl %lld, num_scales %d, %lld packed floats)", name, e,
+                static_cast<long long>(batch), static_cast<long long>(hl), static_cast<long long>(wl), num_scales,
+                static_cast<long long>(packed_floats));
+  if (const char* e = ckb_check(pass, batch, hl, wl, a.L))
+    return fail("%s: %s (pass %d, batch %lld, Hl %lld, Wl %lld, M %d, P %d, H1 %d, H2 %d)", name, e, pass,
+                static_cast<long long>(batch), static_cast<long long>(hl), static_cast<long long>(wl), m, p, h1, h2);
+  a.positions = ckb_positions(hl, wl, pass);
+  if (batch == 0 || a.positions == 0) return 0;
+  if (!y_hat || !psi || !packed || !mu || !index_float || !idx)
+    return fail("%s: y_hat, psi, packed, mu, index_float and idx must not be null", name);
+  if (y && !sym) return fail("%s: sym must not be null when y is given", name);
+  a.pass = pass;
+  a.hl = static_cast<int>(hl);
+  a.wl = static_cast<int>(wl);
+  a.num_scales = num_scales;
+  a.tiles = (a.positions + CKB_TILE - 1) / CKB_TILE;
+  a.packed = packed;
+  a.psi = psi;
+  a.y = y;
+  a.y_hat = y_hat;
+  a.mu = mu;
+  a.index_float = index_float;
+  a.idx = idx;
+  a.sym = sym;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  KernelTimer timer("checkerboard_params", st);
+  const dim3 grid(static_cast<unsigned>(a.tiles * batch));
+  if (pass == 0)
+    hipLaunchKernelGGL(checkerboard_params_kernel<0>, grid, dim3(CKB_THREADS), 0, st, a);
+  else
+    hipLaunchKernelGGL(checkerboard_params_kernel<1>, grid, dim3(CKB_THREADS), 0, st, a);
+  TFC_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int tfc_checkerboard_place(int pass, const float* sym, const float* mu, float* y_hat, int64_t batch,
+                                      int64_t hl, int64_t wl, int m, void* stream) {
+  using namespace tfc;
+  const char* name = "tfc_checkerboard_place";
+  if (pass != 0 && pass != 1) return fail("%s: pass must be 0 or 1, got %d", name, pass);
+  if (m < 1 || m > CTX_MAX_DIM) return fail("%s: M must be in [1, 65536], got %d", name, m);
+  if (batch < 0) return fail("%s: the batch size must not be negative", name);
+  if (hl < 1 || wl < 1 || hl > (1 << 24) || wl > (1 << 24))
+    return fail("%s: Hl and Wl must be in [1, 2^24] (Hl %lld, Wl %lld)", name, static_cast<long long>(hl),
+                static_cast<long long>(wl));
+  if (batch > 0 && hl * wl > (1ll << 40) / batch) return fail("%s: batch * Hl * Wl must be at most 2^40", name);
+  CkbPlace a = {};
+  a.positions = ckb_positions(hl, wl, pass);
+  a.total = batch * a.positions * m;
+  if (a.total == 0) return 0;
+  if (!sym || !mu || !y_hat) return fail("%s: sym, mu and y_hat must not be null", name);
+  a.pass = pass;
+  a.hl = static_cast<int>(hl);
+  a.wl = static_cast<int>(wl);
+  a.m = m;
+  a.sym = sym;
+  a.mu = mu;
+  a.y_hat = y_hat;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  KernelTimer timer("checkerboard_place", st);
+  const int64_t blocks = (a.total + 255) / 256;
+  hipLaunchKernelGGL(checkerboard_place_kernel, dim3(static_cast<unsigned>(blocks < 65536 ? blocks : 65536)), dim3(256),
+                     0, st, a);
+  TFC_HIP(hipGetLastError());
+  return 0;
+}

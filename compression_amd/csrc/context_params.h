@@ -99,4 +99,39 @@ inline int64_t ctx_workspace_bytes(int64_t batch, int64_t hl, int64_t wl, int64_
   return (pre + 15) / 16 * 16 + batch * hl * 16;
 }
 
+// ---- the checkerboard context model (checkerboard.hip) -------------------------------------------------------------
+// Same packed buffer (ctx_layout), the same CTX_TAPS x Mp rows of wc; only the tap list differs: the 12 offsets of the
+// 5x5 window with di + dj odd, row-major.  Those are the odd elements of the window counted row-major, so packed tap k
+// is element 2 k + 1: (di, dj) = (ckb_tap_di(k), ckb_tap_dj(k)) = (-2,-1) (-2,1) (-1,-2) (-1,0) (-1,2) (0,-1) (0,1) ...
+
+constexpr int CKB_TILE = 32;            // positions of one workgroup: the 32 rows of v_mfma_f32_32x32x2_f32
+constexpr int CKB_THREADS = 256;        // four waves, each owns 32-column blocks of a layer's output
+constexpr int CKB_BLOCKS = 5;           // column blocks a wave accumulates side by side (5 x 16 registers)
+constexpr int CKB_GROUP = 8;            // k-steps (of two input rows) whose weights a wave loads ahead
+constexpr int CKB_STAGE_K = 64;         // input rows of one staged chunk of gathered y_hat or psi
+constexpr int CKB_LDS_FLOATS = 40960;   // 160 KiB: gfx950's whole LDS, declared on purpose
+
+constexpr int ckb_tap_di(int k) { return (2 * k + 1) / 5 - 2; }
+constexpr int ckb_tap_dj(int k) { return (2 * k + 1) % 5 - 2; }
+static_assert(ckb_tap_di(0) == -2 && ckb_tap_dj(0) == -1 && ckb_tap_di(CTX_TAPS - 1) == 2 && ckb_tap_dj(CTX_TAPS - 1) == 1,
+              "the checkerboard taps are the odd elements of the 5x5 window");
+
+// Positions of a pass: anchors (i + j even) are pass 0
+inline int64_t ckb_positions(int64_t hl, int64_t wl, int pass) { return (hl * wl + (pass == 0 ? 1 : 0)) / 2; }
+
+// LDS rows (of CKB_TILE floats) of the two activation buffers: A holds ctx then h2, B holds h1 then the output
+inline int ckb_rows_a(const ContextLayout& L) { return L.a_floats; }
+inline int ckb_rows_b(const ContextLayout& L) { return L.b_floats; }
+
+// The checks of tfc_checkerboard_params beyond ctx_layout / ctx_check_shape; null, or the text.
+inline const char* ckb_check(int pass, int64_t batch, int64_t hl, int64_t wl, const ContextLayout& L) {
+  if (pass != 0 && pass != 1) return "pass must be 0 or 1";
+  const int64_t rows = static_cast<int64_t>(ckb_rows_a(L)) + ckb_rows_b(L);
+  if (rows * CKB_TILE + CKB_STAGE_K * CKB_TILE > CKB_LDS_FLOATS)
+    return "the activations of one tile of 32 positions do not fit 160 KiB of LDS";
+  const int64_t tiles = (ckb_positions(hl, wl, pass) + CKB_TILE - 1) / CKB_TILE;
+  if (batch > 0 && tiles > 0x7fffffffll / batch) return "batch * tiles of 32 positions must be below 2^31";
+  return nullptr;
+}
+
 }  // namespace tfc

@@ -77,7 +77,20 @@ class ContextParams:
 
     kernel [5, 5, M, 2M] (HWIO, as `MaskedConv2D.kernel`; the causal mask is applied here whatever the non-causal
     taps hold), kernel_bias [2M], w1 [2M + P, H1], b1 [H1], w2 [H1, H2], b2 [H2], w3 [H2, 2M], b3 [2M]: rows are
-    inputs, as a 1x1 `SignalConv2D` kernel [1, 1, in, out] reshaped.  Holds detached copies."""
+    inputs, as a 1x1 `SignalConv2D` kernel [1, 1, in, out] reshaped.  Holds detached copies.
+
+    `TAPS` is the tap list, in the order of the packed rows; a subclass with another list of CTX_TAPS taps
+    (ops/checkerboard_ops.py) gets the same checks, cache and packed layout with its own mask."""
+
+    TAPS = CAUSAL_TAPS
+
+    @classmethod
+    def mask(cls, dtype=torch.float32, device=None):
+        """[5, 5, 1, 1]: 1 on `TAPS`, 0 elsewhere."""
+        mask = torch.zeros(5, 5, 1, 1, dtype=dtype, device=device)
+        for di, dj in cls.TAPS:
+            mask[di + 2, dj + 2] = 1
+        return mask
 
     def __init__(self, kernel, kernel_bias, w1, b1, w2, b2, w3, b3, num_scales):
         t = [torch.as_tensor(v).detach() for v in (kernel, kernel_bias, w1, b1, w2, b2, w3, b3)]
@@ -108,7 +121,7 @@ class ContextParams:
         if max(m, p, h1, h2) > limit:
             raise ValueError(f"M, P, H1 and H2 must be at most {limit}")
         self.m, self.p, self.h1, self.h2, self.num_scales = m, p, h1, h2, int(num_scales)
-        self.kernel = kernel * causal_mask(kernel.dtype, kernel.device)
+        self.kernel = kernel * self.mask(kernel.dtype, kernel.device)
         self.kernel_bias, self.w1, self.b1, self.w2, self.b2, self.w3, self.b3 = kernel_bias, w1, b1, w2, b2, w3, b3
         self._cache = {}
 
@@ -147,8 +160,8 @@ class ContextParams:
                 assert tuple(value.shape) == (rows, cols), (name, tuple(value.shape), rows, cols)
                 buf[at:at + rows * cols] = value.reshape(-1)
 
-            taps = torch.zeros(len(CAUSAL_TAPS), _pad(m), 2 * m)
-            for k, (di, dj) in enumerate(CAUSAL_TAPS):
+            taps = torch.zeros(len(self.TAPS), _pad(m), 2 * m)
+            for k, (di, dj) in enumerate(self.TAPS):
                 taps[k, :m] = kernel[di + 2, dj + 2]
             at = sections["wc"][0]
             buf[at:at + taps.numel()] = taps.reshape(-1)
@@ -159,9 +172,10 @@ class ContextParams:
         return self._cache[key]
 
 
-def _check_inputs(y, psi, params, what="y"):
-    if not isinstance(params, ContextParams):
-        raise TypeError("params must be a ContextParams")
+def _check_inputs(y, psi, params, what="y", kind=None):
+    kind = kind or ContextParams
+    if not isinstance(params, kind) or params.TAPS != kind.TAPS:
+        raise TypeError(f"params must be a {kind.__name__}")
     if psi.dim() != 4 or psi.shape[-1] != params.p:
         raise ValueError(f"psi must be [B, Hl, Wl, {params.p}], received shape {tuple(psi.shape)}")
     if y is not None:

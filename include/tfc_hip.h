@@ -1068,6 +1068,49 @@ int tfc_context_decode(const tfc_tables* tables, const uint8_t* blob, const int6
                        int64_t hl, int64_t wl, int m, int p, int h1, int h2, int num_scales, void* workspace,
                        float* y_hat, uint8_t* ok, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Checkerboard context model (He, Zheng, Sun, Wang, Qin 2021)              */
+/* ------------------------------------------------------------------------ */
+
+/* The two-pass context model of "Checkerboard context model for efficient learned image compression" (CVPR 2021).
+ * The reference tree carries no program text for it: the definition, the stream format and the layer shapes are this
+ * project's own, and parity with anyone's checkpoints is unpinned.  With y [batch, Hl, Wl, M] the latent, psi [batch,
+ * Hl, Wl, P] the hyper-synthesis output and y_hat = 0 outside the latent, position (i, j) is an ANCHOR when i + j is
+ * even; pass 0 is the anchors, pass 1 the rest:
+ *   taps       = (di, dj) in [-2, 2]^2 with di + dj odd, row-major: 12 taps (every such neighbour of a pass-1
+ *                position is an anchor)
+ *   ctx[i, j]  = bc                                                            pass 0
+ *              = bc + sum over the taps of y_hat[i + di, j + dj] . Wc[di + 2, dj + 2]     pass 1           M -> 2M
+ *   h1 = lrelu(b1 + [ctx, psi] W1)   h2 = lrelu(b2 + h1 W2)   out = b3 + h2 W3                 lrelu slope 0.2
+ *   mu = out[:M]     index_float = out[M:]     idx = tfc_index_prepare(index_float, num_scales)
+ *   sym = int32(rint(y - mu))  (half to even)        y_hat = float32(sym) + mu
+ * all float32.  COMPACT ORDER: the positions of one pass in raster order, channels innermost, [batch, N_p, M] with
+ * N_0 = ceil(Hl Wl / 2), N_1 = floor(Hl Wl / 2); the slot of (i, j) is (i Wl + j) >> 1 when Wl is odd and
+ * i (Wl / 2) + (j >> 1) when Wl is even.
+ * Every output element is one chain of float32 fused multiply-adds that starts from its bias and takes the inputs in
+ * ascending k (taps in row-major order and a tap's channels ascending; a neighbour outside the latent enters as
+ * zeros; the 2M context features before the P hyperprior features): the order depends on (M, P, H1, H2) alone, not on
+ * the batch, the tile of 32 positions a position falls in or its place there, so an image coded in a batch decodes
+ * alone, bit for bit, on the same build and device kind.
+ * `packed` DEV float32 [packed_floats]: the layout of csrc/context_params.h (ctx_layout), whose 12 x Mp rows of wc
+ * hold these taps in row-major order (tap k is element 2 k + 1 of the 5x5 window).
+ * Checked on the host before any launch: pass, sizes (as tfc_context_scan, and the activations of 32 positions within
+ * 160 KiB of LDS, which the kernel declares in full), Hl, Wl, batch, num_scales, packed_floats, null pointers.
+ * batch == 0, or a pass without positions (pass 1 of a 1x1 latent), launches nothing. */
+
+/* The parameters of one pass for all its positions, ONE launch (a workgroup per 32 positions of an image).  y_hat
+ * DEV [batch, Hl, Wl, M] is read at the anchors (pass 1) and, when `y` is given, written at the pass's positions.
+ * mu, index_float DEV float32 and idx DEV int32 [batch, N_pass, M] in compact order.  `y` DEV [batch, Hl, Wl, M] or
+ * NULL (the decoder): when given, sym DEV int32 [batch, N_pass, M] is written as well.  Replaces a masked convolution
+ * (python/layers/signal_conv.py:663-690 with a masked kernel), three 1x1 convolutions, tf.round and two gathers. */
+int tfc_checkerboard_params(int pass, const float* y, float* y_hat, const float* psi, const float* packed,
+                            int64_t packed_floats, int64_t batch, int64_t hl, int64_t wl, int m, int p, int h1, int h2,
+                            int num_scales, float* mu, float* index_float, int32_t* idx, int32_t* sym, void* stream);
+/* The decoder's store of a decoded pass: y_hat[position] = sym + mu, the same single float32 add, from compact sym
+ * (float32, as the entropy model's decoder returns it) and mu [batch, N_pass, M] into y_hat [batch, Hl, Wl, M]. */
+int tfc_checkerboard_place(int pass, const float* sym, const float* mu, float* y_hat, int64_t batch, int64_t hl,
+                           int64_t wl, int m, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
