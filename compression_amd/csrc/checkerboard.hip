@@ -29,8 +29,7 @@
 //
 // Nothing waits on another workgroup; every loop bound comes from the shapes.  In pass 1 the kernel reads y_hat at
 // anchors only and writes it at the other positions only, so concurrent workgroups never touch the same element.
-#include "common.h"
-#include "context_params.h"
+#include "context_shared.h"
 #include "mfma_types.h"
 
 #include "../../include/tfc_hip.h"
@@ -52,11 +51,6 @@ struct CkbArgs {
   int32_t* idx;
   int32_t* sym;
 };
-
-__device__ __forceinline__ float ckb_lrelu(float v) { return v > 0.f ? v : 0.2f * v; }
-
-// tfc_index_prepare's value (csrc/elementwise.hip)
-__device__ __forceinline__ int32_t ckb_index(float v, float hi) { return static_cast<int32_t>(fminf(fmaxf(v, 0.f), hi)); }
 
 // Compact slot -> raster index i * Wl + j of the position
 __device__ __forceinline__ void ckb_position(int64_t slot, int pass, int wl, int* i, int* j) {
@@ -239,7 +233,7 @@ __global__ void __launch_bounds__(CKB_THREADS) checkerboard_params_kernel(const 
     return [buf, lrelu](int col, int pos, f32x4 v) {
       if (lrelu) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = ckb_lrelu(v[e]);
+        for (int e = 0; e < 4; ++e) v[e] = ctx_lrelu(v[e]);
       }
       *reinterpret_cast<f32x4*>(buf + static_cast<size_t>(col) * CKB_TILE + pos) = v;
     };
@@ -277,7 +271,7 @@ __global__ void __launch_bounds__(CKB_THREADS) checkerboard_params_kernel(const 
     const int64_t at = (static_cast<int64_t>(b) * a.positions + slot0 + p) * M + m;
     a.mu[at] = mu;
     a.index_float[at] = fi;
-    a.idx[at] = ckb_index(fi, hi);
+    a.idx[at] = ctx_index(fi, hi);
     if (a.y) {
       int i, j;
       ckb_position(slot0 + p, PASS, a.wl, &i, &j);
@@ -319,11 +313,7 @@ extern "C" int tfc_checkerboard_params(int pass, const float* y, float* y_hat, c
   using namespace tfc;
   const char* name = "tfc_checkerboard_params";
   CkbArgs a = {};
-  if (const char* e = ctx_layout(m, p, h1, h2, &a.L)) return fail("%s: %s (M %d, P %d, H1 %d, H2 %d)", name, e, m, p, h1, h2);
-  if (const char* e = ctx_check_shape(batch, hl, wl, num_scales, packed_floats, a.L))
-    return fail("%s: %s (batch %lld, Hl %lld, Wl %lld, num_scales %d, %lld packed floats)", name, e,
-                static_cast<long long>(batch), static_cast<long long>(hl), static_cast<long long>(wl), num_scales,
-                static_cast<long long>(packed_floats));
+  if (int rc = ctx_check_args(name, m, p, h1, h2, batch, hl, wl, true, num_scales, packed_floats, &a.L)) return rc;
   if (const char* e = ckb_check(pass, batch, hl, wl, a.L))
     return fail("%s: %s (pass %d, batch %lld, Hl %lld, Wl %lld, M %d, P %d, H1 %d, H2 %d)", name, e, pass,
                 static_cast<long long>(batch), static_cast<long long>(hl), static_cast<long long>(wl), m, p, h1, h2);

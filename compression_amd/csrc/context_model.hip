@@ -19,8 +19,7 @@
 // positions to the left that earlier steps of the SAME workgroup stored, ordered by __syncthreads().  Nothing waits
 // on another workgroup.  Every loop bound comes from the shapes; the unary part of an escape is bounded by
 // dec_escape() and reads past a string's end yield zeros (window_load), so damaged input ends the kernel as any other.
-#include "common.h"
-#include "context_params.h"
+#include "context_shared.h"
 #include "range_tables.h"
 #include "range_wave.h"
 
@@ -50,8 +49,6 @@ struct CtxArgs {
   const int32_t* cdf_offset;
   uint8_t* ok;
 };
-
-__device__ __forceinline__ float ctx_lrelu(float v) { return v > 0.f ? v : 0.2f * v; }
 
 // out(p, o) = act(init(p, o) + sum_k in[p][k] w[k][o]) for p < np, o < O; out(p, o) = 0 for O <= o < Op (the next
 // layer's K padding).  `in` is LDS, [np][ldin], Kp a multiple of CTX_KPAD, w [Kp][O] with zero rows behind K.
@@ -239,9 +236,6 @@ __device__ __forceinline__ void ctx_network(const CtxArgs& a, int b, int t, int 
   __syncthreads();
 }
 
-// tfc_index_prepare's value (csrc/elementwise.hip)
-__device__ __forceinline__ int32_t ctx_index(float v, float hi) { return static_cast<int32_t>(fminf(fmaxf(v, 0.f), hi)); }
-
 // Rows of step t: i0 .. i0 + n - 1 (n <= 0: none)
 __device__ __forceinline__ void ctx_step_rows(int t, int hl, int wl, int* i0, int* n) {
   const int hi = min(t / 3, hl - 1);
@@ -263,14 +257,10 @@ __global__ void __launch_bounds__(CTX_THREADS) context_kernel(const CtxArgs a) {
   float* bufB = lds + static_cast<size_t>(L.waves) * L.a_floats;
 
   if (DECODE) {
-    // RangeDecoder's constructor for every row stream of the image (range_coder.h:79-83)
+    // every row stream of the image opens
     for (int i = threadIdx.x; i < a.hl; i += CTX_THREADS) {
       const int64_t s = static_cast<int64_t>(b) * a.hl + i;
-      const uint8_t* src = a.blob + a.off[s];
-      const long long len = a.off[s + 1] - a.off[s];
-      unsigned int w = 0;
-      for (int k = 0; k < 4; ++k) w = (w << 8) | (k < len ? src[k] : 0u);
-      a.state[s] = make_uint4(0u, 0xFFFFFFFFu, w, 2u);
+      a.state[s] = dec_open_state(a.blob + a.off[s], a.off[s + 1] - a.off[s]);
     }
   }
   ctx_precompute(a, b, lds);        // ends with __syncthreads()
@@ -338,23 +328,7 @@ __global__ void __launch_bounds__(CTX_THREADS) context_kernel(const CtxArgs a) {
           }
           if (lane == 0) {
             a.state[s] = make_uint4(st.base, st.span_m1, st.window, w.pulls);
-            if (j == a.wl - 1) {
-              // RangeDecoder::Finalize (range_coder.h:144-169), as dec_close_one of range_coder.hip
-              bool good;
-              if (2ll * w.pulls < w.len) {
-                good = false;
-              } else {
-                const unsigned int top = st.base + st.span_m1;
-                if (st.base == 0 || top < st.base) {
-                  good = st.window == 0;
-                } else {
-                  const int sh = (((st.base - 1) >> 24) < (top >> 24)) ? 24 : 16;
-                  const unsigned int r = ((st.base - 1) >> sh) + 1;
-                  good = (r << sh) == st.window;
-                }
-              }
-              a.ok[s] = good ? 1 : 0;
-            }
+            if (j == a.wl - 1) a.ok[s] = dec_finalize_ok(st.base, st.span_m1, st.window, w.pulls, w.len) ? 1 : 0;
           }
         }
       }
@@ -368,11 +342,7 @@ bool ctx_aligned(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 
 int ctx_prepare(const char* name, const float* psi, const float* packed, int64_t packed_floats, int64_t batch,
                 int64_t hl, int64_t wl, int m, int p, int h1, int h2, int num_scales, void* workspace, float* y_hat,
                 CtxArgs* a) {
-  if (const char* e = ctx_layout(m, p, h1, h2, &a->L)) return fail("%s: %s (M %d, P %d, H1 %d, H2 %d)", name, e, m, p, h1, h2);
-  if (const char* e = ctx_check_shape(batch, hl, wl, num_scales, packed_floats, a->L))
-    return fail("%s: %s (batch %lld, Hl %lld, Wl %lld, num_scales %d, %lld packed floats)", name, e,
-                static_cast<long long>(batch), static_cast<long long>(hl), static_cast<long long>(wl), num_scales,
-                static_cast<long long>(packed_floats));
+  if (int rc = ctx_check_args(name, m, p, h1, h2, batch, hl, wl, true, num_scales, packed_floats, &a->L)) return rc;
   if (batch == 0) return 0;
   if (!psi || !packed || !workspace || !y_hat) return fail("%s: psi, packed, workspace and y_hat must not be null", name);
   if (!ctx_aligned(packed) || !ctx_aligned(workspace)) return fail("%s: packed and workspace must be 16-byte aligned", name);
@@ -395,15 +365,7 @@ int ctx_prepare(const char* name, const float* psi, const float* packed, int64_t
 extern "C" int64_t tfc_context_workspace(int64_t batch, int64_t hl, int64_t wl, int m, int p, int h1, int h2) {
   using namespace tfc;
   ContextLayout L;
-  if (const char* e = ctx_layout(m, p, h1, h2, &L)) {
-    fail("tfc_context_workspace: %s (M %d, P %d, H1 %d, H2 %d)", e, m, p, h1, h2);
-    return -1;
-  }
-  if (const char* e = ctx_check_shape(batch, hl, wl, 1, L.total, L)) {
-    fail("tfc_context_workspace: %s (batch %lld, Hl %lld, Wl %lld)", e, static_cast<long long>(batch),
-         static_cast<long long>(hl), static_cast<long long>(wl));
-    return -1;
-  }
+  if (ctx_check_args("tfc_context_workspace", m, p, h1, h2, batch, hl, wl, false, 0, 0, &L)) return -1;
   return ctx_workspace_bytes(batch, hl, wl, h1);
 }
 

@@ -540,18 +540,13 @@ __global__ void __launch_bounds__(kBlock) dec_kernel(DecParams p, Dst dst) {
 #include "range_pipe.h"
 namespace tfc {
 
-// Reads the first four bytes of every stream (RangeDecoder ctor,
-// range_coder.h:79-83).
+// Opens every stream (dec_open_state, range_wave.h).
 __device__ inline void dec_open_one(const uint8_t* blob, const long long* off, int64_t streams,
                                     uint4* state, unsigned long long* status) {
   const int64_t s = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
   if (s == 0) *status = ~0ull;       // no index error met yet
   if (s >= streams) return;
-  const uint8_t* src = blob + off[s];
-  const long long len = off[s + 1] - off[s];
-  unsigned int w = 0;
-  for (int i = 0; i < 4; ++i) w = (w << 8) | (i < len ? src[i] : 0u);
-  state[s] = make_uint4(0u, 0xFFFFFFFFu, w, 2u);
+  state[s] = dec_open_state(blob + off[s], off[s + 1] - off[s]);
 }
 __global__ void dec_open_kernel(const uint8_t* blob, const long long* off, int64_t streams,
                                 uint4* state, unsigned long long* status) {
@@ -574,27 +569,13 @@ __global__ void dec_open_many_kernel(const DecoderJobs f) {
                reinterpret_cast<unsigned long long*>(ctl));
 }
 
-// RangeDecoder::Finalize (range_coder.h:144-169).
+// The Finalize verdict of every stream (dec_finalize_ok, range_wave.h).
 __device__ inline void dec_close_one(const uint4* state, const long long* off, int64_t streams,
                                      uint8_t* ok) {
   const int64_t s = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
   if (s >= streams) return;
   const uint4 st = state[s];
-  const long long len = off[s + 1] - off[s];
-  bool good;
-  if (2ll * st.w < len) {
-    good = false;
-  } else {
-    const unsigned int top = st.x + st.y;
-    if (st.x == 0 || top < st.x) {
-      good = st.z == 0;
-    } else {
-      const int sh = (((st.x - 1) >> 24) < (top >> 24)) ? 24 : 16;
-      const unsigned int r = ((st.x - 1) >> sh) + 1;
-      good = (r << sh) == st.z;
-    }
-  }
-  ok[s] = good ? 1 : 0;
+  ok[s] = dec_finalize_ok(st.x, st.y, st.z, st.w, off[s + 1] - off[s]) ? 1 : 0;
 }
 __global__ void dec_close_kernel(const uint4* state, const long long* off, int64_t streams,
                                  uint8_t* ok) {

@@ -268,6 +268,37 @@ struct DecoderState {
   unsigned int base, span_m1, window;
 };
 
+// The two rules of the stream format at a decoder's ends, as (base, span_m1, window, pulls).  A stream opens on the
+// whole interval with its first four bytes in the window, zeros behind its end (RangeDecoder's constructor,
+// range_coder.h:79-83) ...
+__host__ __device__ __forceinline__ uint4 dec_open_state(const uint8_t* const& src, const long long& len) {
+  unsigned int w = 0;
+  for (int i = 0; i < 4; ++i) w = (w << 8) | (i < len ? src[i] : 0u);
+  return make_uint4(0u, 0xFFFFFFFFu, w, 2u);
+}
+
+// ... and closes well when no byte is left over and the window holds what the encoder's last flush wrote for this
+// interval (RangeDecoder::Finalize, range_coder.h:144-169).
+// (The arguments are references so that the callers' code comes out as it did with the rule written in place.)
+__host__ __device__ __forceinline__ bool dec_finalize_ok(const unsigned int& base, const unsigned int& span_m1,
+                                                         const unsigned int& window, const unsigned int& pulls,
+                                                         const long long& len) {
+  bool good;
+  if (2ll * pulls < len) {
+    good = false;
+  } else {
+    const unsigned int top = base + span_m1;
+    if (base == 0 || top < base) {
+      good = window == 0;
+    } else {
+      const int sh = (((base - 1) >> 24) < (top >> 24)) ? 24 : 16;
+      const unsigned int r = ((base - 1) >> sh) + 1;
+      good = (r << sh) == window;
+    }
+  }
+  return good;
+}
+
 __device__ inline void dec_narrow(DecoderState& st, unsigned int lo, unsigned int hi, int prec,
                                   DigitWindow& w, int lane) {
   const unsigned long long span = static_cast<unsigned long long>(st.span_m1) + 1;

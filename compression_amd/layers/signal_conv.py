@@ -266,10 +266,9 @@ class SignalConv(torch.nn.Module):
                          for d in range(rank)))
         return _spatial(self._up(self._pad(x, pads), kernel, None, ks), sl)
 
-    def _forward_model(self, x, kernel):
+    def _forward_model(self, x, kernel, bias):
         act = self.activation
         fused = _fused_relu(act)
-        bias = self._bias_value()
         if bias is not None:
             bias = bias.to(x.device)
         corr = self.corr
@@ -285,6 +284,10 @@ class SignalConv(torch.nn.Module):
         return y if act is None or fused else act(y)
 
     def forward(self, inputs):
+        return self._forward(inputs)
+
+    def _forward(self, inputs, with_bias=True):
+        """`forward`, or with `with_bias=False` the same computation without the bias term."""
         if inputs.dim() != self._rank + 2:
             raise ValueError(f"Input tensor must have rank {self._rank + 2}, received shape {tuple(inputs.shape)}.")
         x = inputs.movedim(1, -1) if self.data_format == "channels_first" else inputs
@@ -295,11 +298,11 @@ class SignalConv(torch.nn.Module):
             x, kernel = x[(slice(None),) + (None,) * unit], kernel[(None,) * unit]
         if self._pads_channels_in_forward and not self.channel_separable:
             x, kernel = self._pad_channels(x, kernel)
+        bias = self._bias_value() if with_bias else None
         if self._is_model_configuration():
-            y = self._forward_model(x, kernel)
+            y = self._forward_model(x, kernel, bias)
         else:
             y = self._forward_general(x, kernel)
-            bias = self._bias_value()
             if bias is not None:
                 y = y + bias.to(y.device, y.dtype)
             if self.activation is not None:
@@ -416,7 +419,7 @@ class SignalConv2D(cached.CachedValues, SignalConv):
         if hit is not None:
             cached.drop_weights_key(hit[1])
 
-    def _forward_model(self, x, kernel):
+    def _forward_model(self, x, kernel, bias):
         act = self.activation
         fused = _fused_relu(act)
         corr, up, down = self.corr, self.strides_up[0], self.strides_down[0]
@@ -430,15 +433,15 @@ class SignalConv2D(cached.CachedValues, SignalConv):
             # GDN / IGDN as the activation (signal_conv.py:948-950 applying gdn.py:371-421): one kernel where the
             # convolution kernel that takes the layer can (functional.conv2d_gdn), else the GDN kernel on its output
             prepared = act._prepared_params(gdn[0], gdn[1], x.dtype)
-            y, done = functional.conv2d_gdn(x, kernel, self._bias_value(), down if corr else up, not corr, prepared,
+            y, done = functional.conv2d_gdn(x, kernel, bias, down if corr else up, not corr, prepared,
                                             act.inverse, weights_key=wkey)
             if not done:
                 y = functional.gdn_forward(y, gdn[0], gdn[1], act.inverse, False, 1.0, 1.0, prepared=prepared)
             return y
         if corr:
-            y = functional.conv2d_down(x, kernel, self._bias_value(), down, fused, weights_key=wkey)
+            y = functional.conv2d_down(x, kernel, bias, down, fused, weights_key=wkey)
         else:
-            y = functional.conv2d_up(x, kernel, self._bias_value(), up, fused, weights_key=wkey)
+            y = functional.conv2d_up(x, kernel, bias, up, fused, weights_key=wkey)
             if down != 1:
                 y = y[:, ::down, ::down]
         return y if act is None or fused else act(y)

@@ -82,9 +82,13 @@ class EntropyParameters(torch.nn.Module):
         return self.layer_2(_lrelu(self.layer_1(_lrelu(self.layer_0(features)))))
 
 
-class MBT2018Model(torch.nn.Module):
-    """compress() returns (x_shape, y_shape, z_shape, z_string [B], y_strings); with the context model y_strings holds
-    one string per latent row, [B * Hl], image after image; without it one per image, [B]."""
+class HyperpriorContextModel(torch.nn.Module):
+    """A mean-scale hyperprior whose entropy parameters come from psi and a context model over decoded values: what
+    `MBT2018Model` and `Checkerboard2021Model` share.  A subclass names its context layer and packed-parameter class and
+    supplies `_scan`, `_write_strings` and `_read_strings` (and `_check_latent` where a latent can be too small); with
+    `context=False` the class is the hyperprior alone."""
+
+    context_layer = params_class = None
 
     def __init__(self, lmbda=0.01, num_filters=192, latent_depth=192, context=True, num_scales=64, scale_min=0.11,
                  scale_max=256.0, compute_dtype=torch.float32):
@@ -101,7 +105,7 @@ class MBT2018Model(torch.nn.Module):
         self.hyper_synthesis_transform = HyperSynthesisTransform(num_filters, M)
         self.hyperprior = distributions.NoisyDeepFactorized(batch_shape=(num_filters,))
         if self.context:
-            self.context_prediction = layers.MaskedConv2D(2 * M, M)
+            self.context_prediction = self.context_layer(2 * M, M)
             self.entropy_parameters = EntropyParameters(M)
         self.em_y = self.em_z = None
         self._packed = None
@@ -134,14 +138,31 @@ class MBT2018Model(torch.nn.Module):
         key = tuple((t.data_ptr(), t._version, str(t.device)) for t in sources)
         if self._packed is None or self._packed[0] != key:
             ep = self.entropy_parameters
-            params = context_ops.ContextParams.from_layers(self.context_prediction, (ep.layer_0, ep.layer_1, ep.layer_2),
-                                                           self.num_scales)
+            params = self.params_class.from_layers(self.context_prediction, (ep.layer_0, ep.layer_1, ep.layer_2),
+                                                   self.num_scales)
             self._packed = (key, params)
         return self._packed[1]
 
     def _psi(self, z_hat, y_shape):
         return self.hyper_synthesis_transform(z_hat)[:, :y_shape[0], :y_shape[1], :].contiguous()
 
+    # --- what a context scheme supplies -------------------------------------------------------------------------------
+    def _check_latent(self, y_shape):
+        """Raises for a latent the scheme cannot code."""
+
+    def _scan(self, y, psi, params):
+        """float32 y and psi -> the scheme's scan tuple (mu, index_float, y_hat, ...), full layout."""
+        raise NotImplementedError
+
+    def _write_strings(self, y, scan):
+        """The y strings of `compress` from the float32 latent and its scan."""
+        raise NotImplementedError
+
+    def _read_strings(self, y_strings, psi, batch, y_shape):
+        """The flat y strings of `decompress` -> y_hat; raises when their count is not the scheme's."""
+        raise NotImplementedError
+
+    # ------------------------------------------------------------------------------------------------------------------
     def forward(self, x, training=True, return_y_hat=False):
         """x [B, H, W, 3] on the 0...255 scale -> (loss, bpp, mse) (and y_hat on request)."""
         em_y, em_z = self._models(False)
@@ -149,6 +170,7 @@ class MBT2018Model(torch.nn.Module):
         M = self.latent_depth
         y = self.analysis_transform(x)
         y_shape = tuple(y.shape[1:-1])
+        self._check_latent(y_shape)
         z = self.hyper_analysis_transform(y)
         num_pixels = x.shape[0] * x.shape[1] * x.shape[2]
         _, z_bits = em_z(z, training=training)
@@ -167,7 +189,7 @@ class MBT2018Model(torch.nn.Module):
             _, y_bits = em_y(y.float(), indexes.float(), loc=mu.float(), training=True, noise=u.float())
             y_hat = y_tilde
         else:
-            scan = context_ops.context_scan(y.float(), psi.float(), self.context_params())
+            scan = self._scan(y.float(), psi.float(), self.context_params())
             _, y_bits = em_y(y.float(), scan.index_float, loc=scan.mu, training=False)
             y_hat = scan.y_hat.to(self.compute_dtype)
         x_hat = self.synthesis_transform(y_hat)[:, :x.shape[1], :x.shape[2], :]
@@ -193,13 +215,15 @@ class MBT2018Model(torch.nn.Module):
         y = self.analysis_transform(x)
         z = self.hyper_analysis_transform(y)
         x_shape, y_shape, z_shape = tuple(x.shape[1:-1]), tuple(y.shape[1:-1]), tuple(z.shape[1:-1])
+        self._check_latent(y_shape)
         z_string = self.em_z.compress(z)
         # the closed loop uses quantize() in place of a decode of the string (as ms2020's compress does)
         z_hat = self.em_z.quantize(z).to(self.compute_dtype)
         psi = self._psi(z_hat, y_shape)
         if self.context:
-            scan = context_ops.context_scan(y.float().contiguous(), psi.float(), self.context_params())
-            y_strings = self.em_y.compress((y.float() - scan.mu).contiguous(), scan.index_float).reshape(-1)
+            y = y.float().contiguous()
+            scan = self._scan(y, psi.float(), self.context_params())
+            y_strings = self._write_strings(y, scan)
             y_hat = scan.y_hat
         else:
             means, indexes = psi[..., :M].contiguous(), psi[..., M:].contiguous()
@@ -214,6 +238,7 @@ class MBT2018Model(torch.nn.Module):
         if self.em_y is None:
             raise RuntimeError("decompress needs init_compression()")
         x_shape, y_shape, z_shape = (tuple(int(v) for v in s) for s in (x_shape, y_shape, z_shape))
+        self._check_latent(y_shape)
         M = self.latent_depth
         z_string = np.asarray(z_string, dtype=object).reshape(-1)
         z_hat = self.em_z.decompress(z_string, z_shape).to(self.compute_dtype)
@@ -221,17 +246,34 @@ class MBT2018Model(torch.nn.Module):
         psi = self._psi(z_hat, y_shape)
         y_strings = np.asarray(y_strings, dtype=object).reshape(-1)
         if self.context:
-            if y_strings.shape[0] != batch * y_shape[0]:
-                raise ValueError(f"{batch * y_shape[0]} row strings are needed for {batch} image(s) of {y_shape[0]} "
-                                 f"latent rows, received {y_strings.shape[0]}")
-            y_hat, ok = context_ops.context_decode(y_strings.reshape(batch, y_shape[0]), psi.float(),
-                                                   self.context_params(), self.em_y.cdf, self.em_y.cdf_offset)
-            if self.em_y.decode_sanity_check and not bool(ok.all()):
-                raise RuntimeError("Sanity check failed.")
+            y_hat = self._read_strings(y_strings, psi.float(), batch, y_shape)
         else:
             means, indexes = psi[..., :M].contiguous(), psi[..., M:].contiguous()
             y_hat = self.em_y.decompress(y_strings, indexes, loc=means)
         return self._reconstruct(y_hat, x_shape)
+
+
+class MBT2018Model(HyperpriorContextModel):
+    """compress() returns (x_shape, y_shape, z_shape, z_string [B], y_strings); with the context model y_strings holds
+    one string per latent row, [B * Hl], image after image; without it one per image, [B]."""
+
+    context_layer, params_class = layers.MaskedConv2D, context_ops.ContextParams
+
+    def _scan(self, y, psi, params):
+        return context_ops.context_scan(y, psi, params)
+
+    def _write_strings(self, y, scan):
+        return self.em_y.compress((y - scan.mu).contiguous(), scan.index_float).reshape(-1)
+
+    def _read_strings(self, y_strings, psi, batch, y_shape):
+        if y_strings.shape[0] != batch * y_shape[0]:
+            raise ValueError(f"{batch * y_shape[0]} row strings are needed for {batch} image(s) of {y_shape[0]} "
+                             f"latent rows, received {y_strings.shape[0]}")
+        y_hat, ok = context_ops.context_decode(y_strings.reshape(batch, y_shape[0]), psi, self.context_params(),
+                                               self.em_y.cdf, self.em_y.cdf_offset)
+        if self.em_y.decode_sanity_check and not bool(ok.all()):
+            raise RuntimeError("Sanity check failed.")
+        return y_hat
 
 
 if __name__ == "__main__":      # python -m compression_amd.models.mbt2018 compress in.png out.tfci

@@ -31,7 +31,7 @@ import torch
 
 from .. import _lib
 from . import context_ops
-from .context_ops import ContextParams, _check_inputs, _index_prepare, _network
+from .context_ops import ContextParams, _check_inputs, _index_prepare, _network, tap_sum
 
 __all__ = ["CHECKER_TAPS", "CHECKERBOARD_CONSTANTS", "CheckerboardParams", "CheckerboardScan", "anchor_mask",
            "checkerboard_mask", "checkerboard_split", "checkerboard_merge", "checkerboard_parameters",
@@ -58,15 +58,13 @@ class CheckerboardParams(ContextParams):
 
     def fits_kernel(self):
         """Whether the activations of one tile of positions fit the kernel's LDS (csrc/context_params.h, ckb_check)."""
-        pad = context_ops._pad
-        rows = max(pad(2 * self.m), pad(self.h2)) + max(pad(self.h1), pad(2 * self.m))
         c = CHECKERBOARD_CONSTANTS
-        return super().fits_kernel() and (rows + c["CKB_STAGE_K"]) * c["CKB_TILE"] <= c["CKB_LDS_FLOATS"]
+        return super().fits_kernel() and (self._ab_rows() + c["CKB_STAGE_K"]) * c["CKB_TILE"] <= c["CKB_LDS_FLOATS"]
 
 
 def checkerboard_mask(dtype=torch.float32, device=None):
     """[5, 5, 1, 1]: 1 on the 12 taps with di + dj odd, 0 on the centre and the other 12."""
-    return CheckerboardParams.mask(dtype, device)
+    return context_ops.tap_mask(CHECKER_TAPS, dtype, device)
 
 
 def anchor_mask(hl, wl, device=None):
@@ -122,10 +120,7 @@ def checkerboard_parameters_reference(y_hat, psi, params):
     _check(y_hat, psi, params, "y_hat")
     w = params.tensors(y_hat.dtype, y_hat.device)
     b, hl, wl, m = y_hat.shape
-    padded = torch.nn.functional.pad(y_hat, (0, 0, 2, 2, 2, 2))
-    conv = torch.zeros(b, hl, wl, 2 * m, dtype=y_hat.dtype, device=y_hat.device)
-    for di, dj in CHECKER_TAPS:
-        conv = conv + padded[:, 2 + di:2 + di + hl, 2 + dj:2 + dj + wl] @ w[0][di + 2, dj + 2]
+    conv = tap_sum(torch.zeros(b, hl, wl, 2 * m, dtype=y_hat.dtype, device=y_hat.device), y_hat, w[0], CHECKER_TAPS)
     others = (~anchor_mask(hl, wl, y_hat.device)).to(y_hat.dtype)[None, :, :, None]
     out = _network(w[1] + conv * others, psi, w)
     return out[..., :m], out[..., m:]

@@ -37,12 +37,27 @@ CONTEXT_CONSTANTS = _lib.kernel_constants("context_params.h", ("CTX",))
 assert CONTEXT_CONSTANTS["CTX_TAPS"] == len(CAUSAL_TAPS)
 
 
-def causal_mask(dtype=torch.float32, device=None):
-    """[5, 5, 1, 1]: 1 on the 12 causal taps, 0 on the centre and everything after it in raster order."""
+def tap_mask(taps, dtype=torch.float32, device=None):
+    """[5, 5, 1, 1]: 1 on the taps (di, dj) of the list, 0 elsewhere."""
     mask = torch.zeros(5, 5, 1, 1, dtype=dtype, device=device)
-    for di, dj in CAUSAL_TAPS:
+    for di, dj in taps:
         mask[di + 2, dj + 2] = 1
     return mask
+
+
+def causal_mask(dtype=torch.float32, device=None):
+    """[5, 5, 1, 1]: 1 on the 12 causal taps, 0 on the centre and everything after it in raster order."""
+    return tap_mask(CAUSAL_TAPS, dtype, device)
+
+
+def tap_sum(start, y_hat, kernel, taps):
+    """start + the sum over `taps`, in the list's order, of y_hat [B, Hl, Wl, M] moved by the tap @ kernel[tap], with
+    y_hat zero outside the latent.  Rows below the latent are padded only when a tap reads them."""
+    hl, wl = y_hat.shape[1:3]
+    padded = torch.nn.functional.pad(y_hat, (0, 0, 2, 2, 2, max(di for di, _ in taps)))
+    for di, dj in taps:
+        start = start + padded[:, 2 + di:2 + di + hl, 2 + dj:2 + dj + wl] @ kernel[di + 2, dj + 2]
+    return start
 
 
 def wavefront_steps(hl, wl):
@@ -87,10 +102,7 @@ class ContextParams:
     @classmethod
     def mask(cls, dtype=torch.float32, device=None):
         """[5, 5, 1, 1]: 1 on `TAPS`, 0 elsewhere."""
-        mask = torch.zeros(5, 5, 1, 1, dtype=dtype, device=device)
-        for di, dj in cls.TAPS:
-            mask[di + 2, dj + 2] = 1
-        return mask
+        return tap_mask(cls.TAPS, dtype, device)
 
     def __init__(self, kernel, kernel_bias, w1, b1, w2, b2, w3, b3, num_scales):
         t = [torch.as_tensor(v).detach() for v in (kernel, kernel_bias, w1, b1, w2, b2, w3, b3)]
@@ -140,11 +152,13 @@ class ContextParams:
                 self.kernel, self.kernel_bias, self.w1, self.b1, self.w2, self.b2, self.w3, self.b3))
         return self._cache[key]
 
+    def _ab_rows(self):
+        """Floats per position of the kernels' two activation buffers: A holds ctx then h2, B holds h1 then the output."""
+        return max(_pad(2 * self.m), _pad(self.h2)) + max(_pad(self.h1), _pad(2 * self.m))
+
     def fits_kernel(self):
         """Whether one position's activations fit the kernels' LDS (csrc/context_params.h, ctx_layout)."""
-        a = max(_pad(2 * self.m), _pad(self.h2))
-        b = max(_pad(self.h1), _pad(2 * self.m))
-        return max(a + b, _pad(self.p)) <= CONTEXT_CONSTANTS["CTX_LDS_FLOATS"]
+        return max(self._ab_rows(), _pad(self.p)) <= CONTEXT_CONSTANTS["CTX_LDS_FLOATS"]
 
     def packed(self, device):
         """The float32 buffer the kernels read (layout: csrc/context_params.h)."""
@@ -211,11 +225,7 @@ def context_parameters_reference(y_hat, psi, params):
     _check_inputs(y_hat, psi, params, "y_hat")
     w = params.tensors(y_hat.dtype, y_hat.device)
     b, hl, wl, m = y_hat.shape
-    padded = torch.nn.functional.pad(y_hat, (0, 0, 2, 2, 2, 0))
-    ctx = w[1].expand(b, hl, wl, 2 * m)
-    for di, dj in CAUSAL_TAPS:
-        ctx = ctx + padded[:, 2 + di:2 + di + hl, 2 + dj:2 + dj + wl] @ w[0][di + 2, dj + 2]
-    out = _network(ctx, psi, w)
+    out = _network(tap_sum(w[1].expand(b, hl, wl, 2 * m), y_hat, w[0], CAUSAL_TAPS), psi, w)
     return out[..., :m], out[..., m:]
 
 

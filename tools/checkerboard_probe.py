@@ -10,29 +10,12 @@ ends in a device synchronise.  `checkerboard_decode` includes the entropy model'
 and `tflops` its float32 rate (2 flops per multiply-add of the definition).  Needs a GPU: there is no fallback."""
 import argparse
 import json
-import math
-import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-
-def _median_ms(fn, repeats, warmup=2):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(repeats):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        times.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(times), min(times), max(times)
+from context_probe import _median_ms, probe_inputs          # (puts the repository on sys.path as well)
 
 
 def main(argv=None):
@@ -46,28 +29,13 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("checkerboard_probe needs a GPU")
 
-    from compression_amd import distributions, entropy_models
     from compression_amd.ops import checkerboard_ops, context_ops, gen_ops
 
     hl, wl, m = args.latent
     h1, h2, p, num_scales = 10 * m // 3, 8 * m // 3, 2 * m, 64
-    rng = np.random.Generator(np.random.PCG64(0))
-
-    def normal(scale, *shape):
-        return torch.from_numpy(rng.normal(0.0, scale, shape).astype(np.float32))
-
-    w3 = normal(1 / math.sqrt(h2), h2, 2 * m)
-    w3[:, m:] *= 8.0                                              # indexes that spread over the tables
-    b3 = torch.cat([torch.zeros(m), torch.full((m,), 20.0)])
-    weights = (normal(1 / math.sqrt(12 * m), 5, 5, m, 2 * m), normal(0.1, 2 * m),
-               normal(1 / math.sqrt(2 * m + p), 2 * m + p, h1), normal(0.1, h1), normal(1 / math.sqrt(h1), h1, h2),
-               normal(0.1, h2), w3, b3)
+    normal, weights, model = probe_inputs(args.latent, num_scales)
     checker = checkerboard_ops.CheckerboardParams(*weights, num_scales)
     causal = context_ops.ContextParams(*weights, num_scales)
-    offset = math.log(0.11)
-    factor = (math.log(256.0) - offset) / (num_scales - 1.0)
-    model = entropy_models.LocationScaleIndexedEntropyModel(
-        distributions.NoisyNormal, num_scales, lambda i: torch.exp(offset + factor * i), coding_rank=2, compression=True)
     macs = 2 * m * (12 * m) + (2 * m + p) * h1 + h1 * h2 + h2 * 2 * m            # per pass-1 position
     results = []
     for images in args.images:

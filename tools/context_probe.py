@@ -35,6 +35,35 @@ def _median_ms(fn, repeats, warmup=2):
     return statistics.median(times), min(times), max(times)
 
 
+def probe_inputs(latent, num_scales=64):
+    """What the probes of both context models share: (normal, weights, model): the seeded float32 normal sampler
+    `normal(scale, *shape)`, the eight weight tensors of a model with latent [Hl, Wl, M] drawn from it, and the
+    coding_rank 2 entropy model of the y strings."""
+    m = latent[2]
+    h1, h2, p = 10 * m // 3, 8 * m // 3, 2 * m
+    rng = np.random.Generator(np.random.PCG64(0))
+
+    def normal(scale, *shape):
+        return torch.from_numpy(rng.normal(0.0, scale, shape).astype(np.float32))
+
+    w3 = normal(1 / math.sqrt(h2), h2, 2 * m)
+    w3[:, m:] *= 8.0                                              # indexes that spread over the tables
+    b3 = torch.cat([torch.zeros(m), torch.full((m,), 20.0)])
+    weights = (normal(1 / math.sqrt(12 * m), 5, 5, m, 2 * m), normal(0.1, 2 * m),
+               normal(1 / math.sqrt(2 * m + p), 2 * m + p, h1), normal(0.1, h1), normal(1 / math.sqrt(h1), h1, h2),
+               normal(0.1, h2), w3, b3)
+    return normal, weights, scale_model(num_scales, 2)
+
+
+def scale_model(num_scales, coding_rank):
+    from compression_amd import distributions, entropy_models
+    offset = math.log(0.11)
+    factor = (math.log(256.0) - offset) / (num_scales - 1.0)
+    return entropy_models.LocationScaleIndexedEntropyModel(
+        distributions.NoisyNormal, num_scales, lambda i: torch.exp(offset + factor * i), coding_rank=coding_rank,
+        compression=True)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, nargs="+", default=[1, 16])
@@ -48,28 +77,13 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("context_probe needs a GPU")
 
-    from compression_amd import distributions, entropy_models
     from compression_amd.ops import context_ops, gen_ops
 
     hl, wl, m = args.latent
-    h1, h2, p, num_scales = 10 * m // 3, 8 * m // 3, 2 * m, 64
-    rng = np.random.Generator(np.random.PCG64(0))
-
-    def normal(scale, *shape):
-        return torch.from_numpy(rng.normal(0.0, scale, shape).astype(np.float32))
-
-    w3 = normal(1 / math.sqrt(h2), h2, 2 * m)
-    w3[:, m:] *= 8.0                                              # indexes that spread over the tables
-    b3 = torch.cat([torch.zeros(m), torch.full((m,), 20.0)])
-    params = context_ops.ContextParams(
-        normal(1 / math.sqrt(12 * m), 5, 5, m, 2 * m), normal(0.1, 2 * m), normal(1 / math.sqrt(2 * m + p), 2 * m + p, h1),
-        normal(0.1, h1), normal(1 / math.sqrt(h1), h1, h2), normal(0.1, h2), w3, b3, num_scales)
-    offset = math.log(0.11)
-    factor = (math.log(256.0) - offset) / (num_scales - 1.0)
-    model = entropy_models.LocationScaleIndexedEntropyModel(
-        distributions.NoisyNormal, num_scales, lambda i: torch.exp(offset + factor * i), coding_rank=2, compression=True)
-    per_image = entropy_models.LocationScaleIndexedEntropyModel(
-        distributions.NoisyNormal, num_scales, lambda i: torch.exp(offset + factor * i), coding_rank=3, compression=True)
+    p, num_scales = 2 * m, 64
+    normal, weights, model = probe_inputs(args.latent, num_scales)
+    params = context_ops.ContextParams(*weights, num_scales)
+    per_image = scale_model(num_scales, 3)
     steps = (wl - 1) + 3 * (hl - 1) + 1
     clock_hz = args.clock_mhz * 1e6
     results = []
