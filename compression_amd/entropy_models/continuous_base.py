@@ -37,6 +37,31 @@ class ContinuousEntropyModelBase(torch.nn.Module, metaclass=abc.ABCMeta):
             raise RuntimeError(
                 "For range coding, the entropy model must be instantiated with `compression=True`.")
 
+    # how compress() / decompress() and their `*_many` forms end in every model that codes through gen_ops handles
+    @staticmethod
+    def _compressed(handle, device_result):
+        """A coded handle's strings; with `device_result` the handle itself, finalized without a read-back."""
+        if device_result:
+            return gen_ops.entropy_encode_finalize_device(handle)
+        return gen_ops.entropy_encode_finalize(handle)
+
+    def _decompressed(self, decoder, values, defer_sanity):
+        """`values` once EntropyDecodeFinalize has passed; with `defer_sanity` (values, ok), nothing read back."""
+        if defer_sanity:
+            ok = gen_ops.entropy_decode_finalize_device(decoder)
+            ok._tfc_handle = decoder         # the decoder (and what it borrows) lives as long as its verdict
+            return values, ok
+        sanity = gen_ops.entropy_decode_finalize(decoder)
+        if self.decode_sanity_check and not bool(sanity.all()):
+            raise RuntimeError("Sanity check failed.")
+        return values
+
+    @staticmethod
+    def _decompressed_many(decoders, values):
+        ok = gen_ops.entropy_decode_finalize_device_many(decoders)
+        ok._tfc_handle = decoders
+        return values, ok
+
     @property
     def prior(self):
         if self._prior is None:

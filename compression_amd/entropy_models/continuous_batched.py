@@ -4,7 +4,6 @@ coding with per-channel tables.  compress()/decompress() run on the HIP coder; t
 quantise prologue / dequantise epilogue are fused into the coder's load/store."""
 from __future__ import annotations
 
-import ctypes as C
 import functools
 
 import numpy as np
@@ -134,6 +133,53 @@ class ContinuousBatchedEntropyModel(continuous_base.ContinuousEntropyModelBase):
             cache = self._dev_cache
         return cache[1], cache[2], cache[3]
 
+    def _batches(self, bottlenecks):
+        """compress() inputs on the device -> (contiguous batches of one shape, the shape of their handles)."""
+        self._check_compression()
+        device = _lib.require_device()
+        bottlenecks = [torch.as_tensor(b).to(device, self.bottleneck_dtype).contiguous() for b in bottlenecks]
+        if not bottlenecks:
+            return [], None
+        shape = tuple(bottlenecks[0].shape)
+        if any(tuple(b.shape) != shape for b in bottlenecks):
+            raise ValueError("compress_many: all bottlenecks must have the same shape")
+        return bottlenecks, shape[:len(shape) - self.coding_rank] if self.coding_rank else shape
+
+    def _encode(self, handles, bottlenecks):
+        """continuous_batched.py:370-383 for one batch per handle, ONE coder launch for all of them -> the handles, not
+        finalized."""
+        cdf_offset, qoff, qn = self._device_tables(handles[0].device)
+        channels = int(self.prior_shape.numel())
+        if self.fused and bottlenecks[0].dtype in _DTYPE_CODE:
+            gen_ops.encode_values(handles, bottlenecks, cdf_offset, qoffset=qoff, channels=channels)
+        else:
+            symbols = []
+            for b in bottlenecks:
+                sym = torch.round(b if qn is None else b - qn).to(torch.int32)
+                iid = b.shape[:b.dim() - len(self.prior_shape)]
+                symbols.append((sym.reshape(tuple(iid) + (channels,)) - cdf_offset).reshape(b.shape).contiguous())
+            gen_ops.encode_symbols(handles, symbols)
+        for h, b in zip(handles, bottlenecks):
+            h.coder_inputs = (b, None)           # what the coder read (values, table indexes): for checkers
+        return handles
+
+    def _decode(self, decoders, broadcast_shape):
+        """continuous_batched.py:408-422 for a list of decoders, ONE coder launch for all of them -> values per decoder
+        shaped decoder.shape + broadcast_shape + prior_shape."""
+        broadcast_shape = tuple(int(s) for s in broadcast_shape)
+        cdf_offset, qoff, qn = self._device_tables(decoders[0].device)
+        channels = int(self.prior_shape.numel())
+        if self.fused and self.bottleneck_dtype in _DTYPE_CODE:
+            return gen_ops.decode_values(decoders, broadcast_shape + tuple(self.prior_shape), self.bottleneck_dtype,
+                                         cdf_offset, qoffset=qoff, channels=channels)
+        _, symbols = gen_ops.decode_symbols(decoders, broadcast_shape + (channels,))
+        outs = []
+        for d, sym in zip(decoders, symbols):
+            out = (sym + cdf_offset).reshape(d.shape + broadcast_shape + tuple(self.prior_shape))
+            out = out.to(self.bottleneck_dtype)
+            outs.append(out if qn is None else out + qn)
+        return outs
+
     def compress(self, bottleneck, device_result=False):
         """continuous_batched.py:347-383.  Returns a numpy object array of `bytes`
         shaped like `bottleneck` minus the `coding_rank` innermost dimensions.
@@ -146,34 +192,9 @@ class ContinuousBatchedEntropyModel(continuous_base.ContinuousEntropyModelBase):
         escape rows — i.e. more than ~16-20 bits per symbol on average over a whole stream, which only data far off
         the model's tables produces): "a stream outgrew its output slab".  The plain call (`device_result=False`)
         repeats itself with the bound that cannot be exceeded instead; call it for such data."""
-        self._check_compression()
-        device = _lib.require_device()
-        bottleneck = torch.as_tensor(bottleneck).to(device, self.bottleneck_dtype).contiguous()
-        shape = tuple(bottleneck.shape)
-        batch_shape = shape[:len(shape) - self.coding_rank] if self.coding_rank else shape
+        bottlenecks, batch_shape = self._batches([bottleneck])
         handle = gen_ops.create_range_encoder(batch_shape, self.cdf, deferred_errors=device_result)
-        if handle.streams == 0:
-            raise ValueError(f"`handle` is empty: handle.shape={list(batch_shape)}")
-        channels = int(self.prior_shape.numel())
-        elems = bottleneck.numel() // handle.streams
-        cdf_offset, qoff, _ = self._device_tables(device)
-        if self.fused and bottleneck.dtype in _DTYPE_CODE:
-            handle._keep += [bottleneck, cdf_offset, qoff]
-            quantized = self._quantized_call(bottleneck, qoff, cdf_offset, channels, elems)
-            handle.record(quantized)
-            quantized(handle)
-        else:
-            offset = self.quantization_offset
-            if offset is not None:
-                bottleneck = bottleneck - offset.to(device)
-            symbols = torch.round(bottleneck).to(torch.int32)
-            iid = shape[:len(shape) - len(self.prior_shape)] if len(self.prior_shape) else shape
-            symbols = symbols.reshape(tuple(iid) + (-1,)) - cdf_offset
-            handle = gen_ops.entropy_encode_channel(handle, symbols.contiguous())
-        if device_result:
-            handle.coder_inputs = (bottleneck, None)     # what the coder read (values, table indexes): for checkers
-            return gen_ops.entropy_encode_finalize_device(handle)
-        return gen_ops.entropy_encode_finalize(handle)
+        return self._compressed(self._encode([handle], bottlenecks)[0], device_result)
 
     def decompress(self, strings, broadcast_shape, defer_sanity=False):
         """continuous_batched.py:385-422: output shape = strings.shape + broadcast_shape +
@@ -183,57 +204,8 @@ class ContinuousBatchedEntropyModel(continuous_base.ContinuousEntropyModelBase):
         uint8 result of EntropyDecodeFinalize (1 = the end-of-stream check passed) for the caller to test
         once the stream has run."""
         self._check_compression()
-        device = _lib.require_device()
-        broadcast_shape = tuple(int(s) for s in broadcast_shape)
-        handle = gen_ops.create_range_decoder(strings, self.cdf)
-        channels = int(self.prior_shape.numel())
-        out_shape = tuple(handle.shape) + broadcast_shape + tuple(self.prior_shape)
-        elems = int(np.prod(broadcast_shape, dtype=np.int64)) * channels
-        cdf_offset, qoff, _ = self._device_tables(device)
-        if self.fused and self.bottleneck_dtype in _DTYPE_CODE:
-            out = torch.empty(out_shape, dtype=self.bottleneck_dtype, device=device)
-            _lib.check(_lib.lib().tfc_decoder_decode_dequantized(
-                handle.ptr, None, out.data_ptr(), _DTYPE_CODE[self.bottleneck_dtype],
-                None if qoff is None else qoff.data_ptr(), cdf_offset.data_ptr(), channels, elems,
-                _lib.stream_ptr()))
-            handle._keep.append(out)
-        else:
-            handle, symbols = gen_ops.entropy_decode_channel(
-                handle, broadcast_shape + (channels,), torch.int32)
-            out = (symbols + cdf_offset).reshape(out_shape).to(self.bottleneck_dtype)
-            offset = self.quantization_offset
-            if offset is not None:
-                out = out + offset.to(device)
-        if defer_sanity:
-            ok = gen_ops.entropy_decode_finalize_device(handle)
-            ok._tfc_handle = handle          # the decoder (and what it borrows) lives as long as its verdict
-            return out, ok
-        sanity = gen_ops.entropy_decode_finalize(handle)
-        if self.decode_sanity_check and not bool(sanity.all()):
-            raise RuntimeError("Sanity check failed.")
-        return out
-
-    @staticmethod
-    def _quantized_call(bottleneck, qoff, cdf_offset, channels, elems):
-        """The fused quantise + encode call of one handle as a closure over its inputs (what a deferred handle keeps to be
-        coded again: gen_ops._retry_outgrown)."""
-        def call(handle):
-            handle._keep += [bottleneck, cdf_offset, qoff]
-            _lib.check(_lib.lib().tfc_encoder_encode_quantized(
-                handle.ptr, bottleneck.data_ptr(), _DTYPE_CODE[bottleneck.dtype],
-                None if qoff is None else qoff.data_ptr(), cdf_offset.data_ptr(), channels, elems,
-                _lib.stream_ptr()))
-        return call
-
-    # ------------------------------------------------------------------ several batches per launch
-    def _symbols(self, bottleneck, cdf_offset, qoff_native):
-        """int32 symbols of continuous_batched.py:370-380 as tensor ops (the `*_many` path hands the coder
-        plain symbols: the lane-per-stream kernels' hand-scheduled blocks take int32 in channel mode)."""
-        if qoff_native is not None:
-            bottleneck = bottleneck - qoff_native
-        symbols = torch.round(bottleneck.float()).to(torch.int32)
-        iid = bottleneck.shape[:bottleneck.dim() - len(self.prior_shape)] if len(self.prior_shape) else bottleneck.shape
-        return (symbols.reshape(tuple(iid) + (-1,)) - cdf_offset).reshape(bottleneck.shape).contiguous()
+        decoder = gen_ops.create_range_decoder(strings, self.cdf)
+        return self._decompressed(decoder, self._decode([decoder], broadcast_shape)[0], defer_sanity)
 
     def compress_many(self, bottlenecks):
         """compress() of several independent batches (same shape) with ONE coder launch: the batches'
@@ -243,76 +215,22 @@ class ContinuousBatchedEntropyModel(continuous_base.ContinuousEntropyModelBase):
         finalized encoder handle per batch (`gen_ops.fetch_strings`, `decompress_many`).  Same strings as
         compress() batch by batch.  (Like `compress(device_result=True)`: a stream of more than ~16-20 bits per
         symbol outgrows the speculative slab; `fetch_strings` then codes that handle again, synchronously.)"""
-        self._check_compression()
-        device = _lib.require_device()
-        bottlenecks = [torch.as_tensor(b).to(device, self.bottleneck_dtype).contiguous() for b in bottlenecks]
+        bottlenecks, batch_shape = self._batches(bottlenecks)
         if not bottlenecks:
             return []
-        shape = tuple(bottlenecks[0].shape)
-        if any(tuple(b.shape) != shape for b in bottlenecks):
-            raise ValueError("compress_many: all bottlenecks must have the same shape")
-        batch_shape = shape[:len(shape) - self.coding_rank] if self.coding_rank else shape
-        cdf_offset, qoff, qn = self._device_tables(device)
-        n = len(bottlenecks)
-        handles = gen_ops.create_range_encoders(n, batch_shape, self.cdf, mode="throughput", deferred_errors=True)
-        if self.fused and bottlenecks[0].dtype in _DTYPE_CODE:
-            # quantise prologue inside the library: one elementwise pass per batch, then ONE coding launch
-            channels = int(self.prior_shape.numel())
-            elems = bottlenecks[0].numel() // handles[0].streams
-            hp = (C.c_void_p * n)(*[h.ptr for h in handles])
-            yp = (C.c_void_p * n)(*[b.data_ptr() for b in bottlenecks])
-            _lib.check(_lib.lib().tfc_encoder_encode_quantized_many(
-                n, hp, yp, _DTYPE_CODE[bottlenecks[0].dtype], None if qoff is None else qoff.data_ptr(),
-                cdf_offset.data_ptr(), channels, elems, _lib.stream_ptr()))
-            keep = [[b, cdf_offset, qoff] for b in bottlenecks]
-            for h, b in zip(handles, bottlenecks):
-                h.record(self._quantized_call(b, qoff, cdf_offset, channels, elems))
-        else:
-            symbols = [self._symbols(b, cdf_offset, qn) for b in bottlenecks]
-            handles = gen_ops.entropy_encode_channel_many(handles, symbols)
-            keep = [[b, s] for b, s in zip(bottlenecks, symbols)]
-        handles = gen_ops.entropy_encode_finalize_device_many(handles)
-        for h, b, k in zip(handles, bottlenecks, keep):
-            h.coder_inputs = (b, None)
-            h._keep += k
-        return handles
+        handles = gen_ops.create_range_encoders(len(bottlenecks), batch_shape, self.cdf, mode="throughput",
+                                                deferred_errors=True)
+        return gen_ops.entropy_encode_finalize_device_many(self._encode(handles, bottlenecks))
 
     def decompress_many(self, handles, broadcast_shape):
         """decompress() for the handles of compress_many (or any finalized encoder handles of one shape): one
         decoder launch for all of them; returns ([values per batch], ok) with `ok` the device-resident
         EntropyDecodeFinalize flags [len(handles), *batch_shape] — nothing is read back."""
         self._check_compression()
-        device = _lib.require_device()
-        handles = list(handles)
-        if not handles:
-            return [], None
-        broadcast_shape = tuple(int(s) for s in broadcast_shape)
-        channels = int(self.prior_shape.numel())
-        cdf_offset, qoff, qn = self._device_tables(device)
         decoders = gen_ops.create_range_decoders(handles, self.cdf, mode="throughput")
-        n = len(decoders)
-        out_shape = tuple(handles[0].shape) + broadcast_shape + tuple(self.prior_shape)
-        if self.fused and self.bottleneck_dtype in _DTYPE_CODE:
-            outs = [torch.empty(out_shape, dtype=self.bottleneck_dtype, device=device) for _ in range(n)]
-            elems = int(np.prod(broadcast_shape, dtype=np.int64)) * channels
-            dp = (C.c_void_p * n)(*[d.ptr for d in decoders])
-            yp = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
-            _lib.check(_lib.lib().tfc_decoder_decode_dequantized_many(
-                n, dp, yp, _DTYPE_CODE[self.bottleneck_dtype], None if qoff is None else qoff.data_ptr(),
-                cdf_offset.data_ptr(), channels, elems, _lib.stream_ptr()))
-            for d, o in zip(decoders, outs):
-                d._keep += [o, cdf_offset, qoff]
-        else:
-            decoders, symbols = gen_ops.entropy_decode_channel_many(decoders, broadcast_shape + (channels,), torch.int32)
-            outs = []
-            for sym in symbols:
-                out = (sym + cdf_offset).reshape(out_shape).to(self.bottleneck_dtype)
-                if qn is not None:
-                    out = out + qn
-                outs.append(out)
-        ok = gen_ops.entropy_decode_finalize_device_many(decoders)
-        ok._tfc_handle = decoders
-        return outs, ok
+        if not decoders:
+            return [], None
+        return self._decompressed_many(decoders, self._decode(decoders, broadcast_shape))
 
     def get_config(self):
         config = super().get_config()

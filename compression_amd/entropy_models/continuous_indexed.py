@@ -2,8 +2,6 @@
 (python/entropy_models/continuous_indexed.py:30-633)."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -159,77 +157,66 @@ class ContinuousIndexedEntropyModel(continuous_base.ContinuousEntropyModelBase):
             cache = self._dev_offsets
         return cache[1]
 
+    def _flats(self, indexes):
+        device = _lib.require_device()
+        return [self._table_indexes(torch.as_tensor(i).to(device)) for i in indexes]
+
+    def _batches(self, bottlenecks, indexes):
+        """compress() inputs on the device -> (contiguous batches of one shape, their table indexes, the shape of their
+        handles)."""
+        self._check_compression()
+        device = _lib.require_device()
+        bottlenecks = [torch.as_tensor(b).to(device, self.bottleneck_dtype).contiguous() for b in bottlenecks]
+        flats = self._flats(indexes)
+        if not bottlenecks:
+            return [], [], None
+        if len(flats) != len(bottlenecks):
+            raise ValueError("compress_many: one index tensor per bottleneck")
+        shape = tuple(flats[0].shape)
+        if any(tuple(f.shape) != shape for f in flats) or any(b.shape != bottlenecks[0].shape for b in bottlenecks):
+            raise ValueError("compress_many: all batches must have the same shape")
+        return bottlenecks, flats, shape[:len(shape) - self.coding_rank] if self.coding_rank else shape
+
+    def _encode(self, handles, bottlenecks, flats):
+        """continuous_indexed.py:374-386 for one batch per handle, ONE coder launch per stage for all of them -> the
+        handles, not finalized."""
+        cdf_offset = self._device_offsets(handles[0].device)
+        if self.fused and bottlenecks[0].dtype in _DTYPE_CODE:
+            gen_ops.encode_values(handles, bottlenecks, cdf_offset, indexes=flats)
+        else:
+            symbols = [(torch.round(b).to(torch.int32) - cdf_offset[f.long()]).contiguous()
+                       for b, f in zip(bottlenecks, flats)]
+            gen_ops.encode_symbols(handles, symbols, flats)
+        for h, b, f in zip(handles, bottlenecks, flats):
+            h.coder_inputs = (b, f)              # what the coder read (values, table indexes): for checkers
+        return handles
+
+    def _decode(self, decoders, flats):
+        """continuous_indexed.py:405-417 for a list of decoders, ONE coder launch per stage for all of them -> values
+        per decoder, shaped like its table indexes."""
+        shape = tuple(flats[0].shape)
+        decode_shape = shape[len(shape) - self.coding_rank:] if self.coding_rank else ()
+        cdf_offset = self._device_offsets(decoders[0].device)
+        if self.fused and self.bottleneck_dtype in _DTYPE_CODE:
+            return gen_ops.decode_values(decoders, decode_shape, self.bottleneck_dtype, cdf_offset, indexes=flats)
+        _, symbols = gen_ops.decode_symbols(decoders, decode_shape, flats)
+        return [(sym + cdf_offset[f.long()]).to(self.bottleneck_dtype) for sym, f in zip(symbols, flats)]
+
     def compress(self, bottleneck, indexes, device_result=False):
         """continuous_indexed.py:355-386.  `device_result=True`: see
         `ContinuousBatchedEntropyModel.compress` (nothing read back, returns the finalized handle)."""
-        self._check_compression()
-        device = _lib.require_device()
-        bottleneck = torch.as_tensor(bottleneck).to(device, self.bottleneck_dtype).contiguous()
-        flat = self._table_indexes(torch.as_tensor(indexes).to(device))
-        shape = tuple(flat.shape)
-        batch_shape = shape[:len(shape) - self.coding_rank] if self.coding_rank else shape
-        cdf_offset = self._device_offsets(device)
+        bottlenecks, flats, batch_shape = self._batches([bottleneck], [indexes])
         handle = gen_ops.create_range_encoder(batch_shape, self.cdf, deferred_errors=device_result)
-        if handle.streams == 0:
-            raise ValueError(f"`handle` is empty: handle.shape={list(batch_shape)}")
-        if self.fused and bottleneck.dtype in _DTYPE_CODE:
-            elems = flat.numel() // handle.streams
-            handle._keep += [bottleneck, flat, cdf_offset]
-            quantized = self._quantized_call(bottleneck, flat, cdf_offset, elems)
-            handle.record(quantized)
-            quantized(handle)
-        else:
-            symbols = torch.round(bottleneck).to(torch.int32) - cdf_offset[flat.long()]
-            handle = gen_ops.entropy_encode_index(handle, flat, symbols.contiguous())
-        if device_result:
-            handle.coder_inputs = (bottleneck, flat)     # what the coder read (values, table indexes): for checkers
-            return gen_ops.entropy_encode_finalize_device(handle)
-        return gen_ops.entropy_encode_finalize(handle)
+        return self._compressed(self._encode([handle], bottlenecks, flats)[0], device_result)
 
     def decompress(self, strings, indexes, defer_sanity=False):
         """continuous_indexed.py:388-417.  `strings` may be a handle from `compress(device_result=True)`;
         `defer_sanity=True` returns (values, ok) without reading anything back (see
         `ContinuousBatchedEntropyModel.decompress`)."""
         self._check_compression()
-        device = _lib.require_device()
-        flat = self._table_indexes(torch.as_tensor(indexes).to(device))
-        shape = tuple(flat.shape)
-        decode_shape = shape[len(shape) - self.coding_rank:] if self.coding_rank else ()
-        cdf_offset = self._device_offsets(device)
-        handle = gen_ops.create_range_decoder(strings, self.cdf)
-        if tuple(handle.shape) + tuple(decode_shape) != shape:
-            raise ValueError(
-                "'index' shape should match 'handle' shape + 'shape': "
-                f"index.shape={list(shape)}, handle.shape={list(handle.shape)}, shape={list(decode_shape)}")
-        if self.fused and self.bottleneck_dtype in _DTYPE_CODE:
-            out = torch.empty(shape, dtype=self.bottleneck_dtype, device=device)
-            elems = flat.numel() // handle.streams
-            handle._keep += [flat, out, cdf_offset]
-            _lib.check(_lib.lib().tfc_decoder_decode_dequantized(
-                handle.ptr, flat.data_ptr(), out.data_ptr(), _DTYPE_CODE[self.bottleneck_dtype],
-                None, cdf_offset.data_ptr(), 0, elems, _lib.stream_ptr()))
-        else:
-            handle, symbols = gen_ops.entropy_decode_index(handle, flat, decode_shape, torch.int32)
-            out = (symbols + cdf_offset[flat.long()]).to(self.bottleneck_dtype)
-        if defer_sanity:
-            ok = gen_ops.entropy_decode_finalize_device(handle)
-            ok._tfc_handle = handle
-            return out, ok
-        sanity = gen_ops.entropy_decode_finalize(handle)
-        if self.decode_sanity_check and not bool(sanity.all()):
-            raise RuntimeError("Sanity check failed.")
-        return out
-
-    @staticmethod
-    def _quantized_call(bottleneck, flat, cdf_offset, elems):
-        """The fused quantise + indexed encode call of one handle as a closure over its inputs (what a deferred handle
-        keeps to be coded again: gen_ops._retry_outgrown)."""
-        def call(handle):
-            handle._keep += [bottleneck, flat, cdf_offset]
-            _lib.check(_lib.lib().tfc_encoder_encode_quantized_indexed(
-                handle.ptr, bottleneck.data_ptr(), _DTYPE_CODE[bottleneck.dtype], flat.data_ptr(),
-                cdf_offset.data_ptr(), elems, _lib.stream_ptr()))
-        return call
+        flats = self._flats([indexes])
+        decoder = gen_ops.create_range_decoder(strings, self.cdf)
+        return self._decompressed(decoder, self._decode([decoder], flats)[0], defer_sanity)
 
     def compress_many(self, bottlenecks, indexes):
         """compress() of several independent batches (same shapes) with ONE coder launch per stage
@@ -237,85 +224,27 @@ class ContinuousIndexedEntropyModel(continuous_base.ContinuousEntropyModelBase):
         their parallel expansion pass; the serial chain of all batches' streams is one small grid).  Nothing is read
         back: one finalized encoder handle per batch (`gen_ops.fetch_strings`, `decompress_many`); same strings as
         compress() batch by batch.  `indexes`: one tensor per batch (continuous_indexed.py:355-386)."""
-        self._check_compression()
-        device = _lib.require_device()
-        bottlenecks = [torch.as_tensor(b).to(device, self.bottleneck_dtype).contiguous() for b in bottlenecks]
-        flats = [self._table_indexes(torch.as_tensor(i).to(device)) for i in indexes]
+        bottlenecks, flats, batch_shape = self._batches(bottlenecks, indexes)
         if not bottlenecks:
             return []
-        if len(flats) != len(bottlenecks):
-            raise ValueError("compress_many: one index tensor per bottleneck")
-        shape = tuple(flats[0].shape)
-        if any(tuple(f.shape) != shape for f in flats) or any(tuple(b.shape) != tuple(bottlenecks[0].shape) for b in bottlenecks):
-            raise ValueError("compress_many: all batches must have the same shape")
-        batch_shape = shape[:len(shape) - self.coding_rank] if self.coding_rank else shape
-        cdf_offset = self._device_offsets(device)
-        n = len(bottlenecks)
-        handles = gen_ops.create_range_encoders(n, batch_shape, self.cdf, mode="throughput", deferred_errors=True)
-        if handles[0].streams == 0:
-            raise ValueError(f"`handle` is empty: handle.shape={list(batch_shape)}")
-        if self.fused and bottlenecks[0].dtype in _DTYPE_CODE:
-            elems = flats[0].numel() // handles[0].streams
-            hp = (C.c_void_p * n)(*[h.ptr for h in handles])
-            yp = (C.c_void_p * n)(*[b.data_ptr() for b in bottlenecks])
-            ip = (C.c_void_p * n)(*[f.data_ptr() for f in flats])
-            _lib.check(_lib.lib().tfc_encoder_encode_quantized_indexed_many(
-                n, hp, yp, _DTYPE_CODE[bottlenecks[0].dtype], ip, cdf_offset.data_ptr(), elems, _lib.stream_ptr()))
-            for h, b, f in zip(handles, bottlenecks, flats):
-                h.record(self._quantized_call(b, f, cdf_offset, elems))
-        else:
-            for k in range(n):
-                symbols = torch.round(bottlenecks[k]).to(torch.int32) - cdf_offset[flats[k].long()]
-                handles[k] = gen_ops.entropy_encode_index(handles[k], flats[k], symbols.contiguous())
-        handles = gen_ops.entropy_encode_finalize_device_many(handles)
-        for h, b, f in zip(handles, bottlenecks, flats):
-            h.coder_inputs = (b, f)
-            h._keep += [b, f, cdf_offset]
-        return handles
+        handles = gen_ops.create_range_encoders(len(bottlenecks), batch_shape, self.cdf, mode="throughput",
+                                                deferred_errors=True)
+        return gen_ops.entropy_encode_finalize_device_many(self._encode(handles, bottlenecks, flats))
 
     def decompress_many(self, handles, indexes):
         """decompress() for the handles of compress_many: one decoder launch per stage for all of them; returns
         ([values per batch], ok) with `ok` the device-resident EntropyDecodeFinalize flags — nothing is read back."""
         self._check_compression()
-        device = _lib.require_device()
         handles = list(handles)
         if not handles:
             return [], None
-        flats = [self._table_indexes(torch.as_tensor(i).to(device)) for i in indexes]
+        flats = self._flats(indexes)
         if len(flats) != len(handles):
             raise ValueError(f"decompress_many: one index tensor per handle ({len(flats)} index tensors, {len(handles)} handles)")
-        shape = tuple(flats[0].shape)
-        if any(tuple(f.shape) != shape for f in flats):
+        if any(f.shape != flats[0].shape for f in flats):
             raise ValueError("decompress_many: all index tensors must have the same shape")
-        decode_shape = shape[len(shape) - self.coding_rank:] if self.coding_rank else ()
-        cdf_offset = self._device_offsets(device)
         decoders = gen_ops.create_range_decoders(handles, self.cdf, mode="throughput")
-        n = len(decoders)
-        for d in decoders:
-            if d.streams == 0:
-                raise ValueError(f"`handle` is empty: handle.shape={list(d.shape)}")
-            if tuple(d.shape) + tuple(decode_shape) != shape:
-                raise ValueError(
-                    "'index' shape should match 'handle' shape + 'shape': "
-                    f"index.shape={list(shape)}, handle.shape={list(d.shape)}, shape={list(decode_shape)}")
-        if self.fused and self.bottleneck_dtype in _DTYPE_CODE:
-            outs = [torch.empty(shape, dtype=self.bottleneck_dtype, device=device) for _ in range(n)]
-            elems = flats[0].numel() // decoders[0].streams
-            dp = (C.c_void_p * n)(*[d.ptr for d in decoders])
-            ip = (C.c_void_p * n)(*[f.data_ptr() for f in flats])
-            yp = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
-            _lib.check(_lib.lib().tfc_decoder_decode_dequantized_indexed_many(
-                n, dp, ip, yp, _DTYPE_CODE[self.bottleneck_dtype], cdf_offset.data_ptr(), elems, _lib.stream_ptr()))
-            for d, f, o in zip(decoders, flats, outs):
-                d._keep += [f, o, cdf_offset]
-        else:
-            outs = []
-            for k in range(n):
-                decoders[k], symbols = gen_ops.entropy_decode_index(decoders[k], flats[k], decode_shape, torch.int32)
-                outs.append((symbols + cdf_offset[flats[k].long()]).to(self.bottleneck_dtype))
-        ok = gen_ops.entropy_decode_finalize_device_many(decoders)
-        ok._tfc_handle = decoders
-        return outs, ok
+        return self._decompressed_many(decoders, self._decode(decoders, flats))
 
     def get_config(self):
         raise NotImplementedError("Serializing indexed entropy models is not yet implemented.")

@@ -95,21 +95,31 @@ class BLS2017Model(torch.nn.Module):
             self.prior, coding_rank=3, compression=True, bottleneck_dtype=self.compute_dtype)
         return self
 
+    def _latent(self, x):
+        """(y, (x_shape, y_shape)) of one batch of images: what compress() hands the coder."""
+        if x.dim() == 3:
+            x = x[None]
+        y = self.analysis_transform.unit(functional.image_to_unit(x, self.compute_dtype))
+        return y, (tuple(x.shape[1:-1]), tuple(y.shape[1:-1]))
+
+    def _reconstruction(self, y_hat, x_shape):
+        x_hat = functional.unit_to_image(self.synthesis_transform.unit(y_hat)[:, :x_shape[0], :x_shape[1], :])
+        x_hat._tfc_keep = (y_hat,)          # produced on the coder stream, read on the transform stream
+        return x_hat
+
     @torch.no_grad()
     def compress(self, x, device_result=False, lane=None):
         """x: uint8 [B, H, W, 3] (or [H, W, 3]) -> (strings[B], x_shape, y_shape) — bls2017.py:164-176.
         `device_result` / `lane`: see BMSHJ2018Model.compress (strings stay in HBM, nothing read back;
         transforms and coder on the lane's two streams)."""
         lane = lane or inline_lane()
-        if x.dim() == 3:
-            x = x[None]
         with lane.on("transform"):
-            y = self.analysis_transform.unit(functional.image_to_unit(x, self.compute_dtype))
+            y, shapes = self._latent(x)
         with lane.on("coder"):
             string = self.entropy_model.compress(y, device_result=device_result)
         if device_result:
             string._keep.append(y)          # produced on the transform stream, read by the coder stream
-        return string, tuple(x.shape[1:-1]), tuple(y.shape[1:-1])
+        return (string,) + shapes
 
     @torch.no_grad()
     def decompress(self, string, x_shape, y_shape, defer_sanity=False, lane=None):
@@ -123,31 +133,23 @@ class BLS2017Model(torch.nn.Module):
             y_hat, oky = y_hat
             ok.append(oky)
         with lane.on("transform"):
-            x_hat = functional.unit_to_image(self.synthesis_transform.unit(y_hat)[:, :x_shape[0], :x_shape[1], :])
-            x_hat._tfc_keep = (y_hat,)      # produced on the coder stream, read here on the transform stream
+            x_hat = self._reconstruction(y_hat, x_shape)
         return (x_hat, ok) if defer_sanity else x_hat
 
     @torch.no_grad()
     def compress_many(self, xs):
         """compress() of several batches with one coder launch (ContinuousBatchedEntropyModel.compress_many):
         [(handle, x_shape, y_shape)] — the handles keep the strings in HBM."""
-        ys = [self.analysis_transform.unit(functional.image_to_unit(x if x.dim() == 4 else x[None], self.compute_dtype))
-              for x in xs]
-        handles = self.entropy_model.compress_many(ys)
-        return [(h, tuple(x.shape[-3:-1]), tuple(y.shape[1:-1])) for h, x, y in zip(handles, xs, ys)]
+        latents = [self._latent(x) for x in xs]
+        handles = self.entropy_model.compress_many([y for y, _ in latents])
+        return [(h,) + shapes for h, (_, shapes) in zip(handles, latents)]
 
     @torch.no_grad()
     def decompress_many(self, packed):
         """decompress() for the results of compress_many: ([x_hat per batch], ok flags on the device)."""
         packed = list(packed)
-        handles = [p[0] for p in packed]
-        y_hats, ok = self.entropy_model.decompress_many(handles, packed[0][2])
-        outs = []
-        for (h, x_shape, y_shape), y_hat in zip(packed, y_hats):
-            x_hat = functional.unit_to_image(self.synthesis_transform.unit(y_hat)[:, :x_shape[0], :x_shape[1], :])
-            x_hat._tfc_keep = (y_hat,)
-            outs.append(x_hat)
-        return outs, ok
+        y_hats, ok = self.entropy_model.decompress_many([p[0] for p in packed], packed[0][2])
+        return [self._reconstruction(y_hat, p[1]) for p, y_hat in zip(packed, y_hats)], ok
 
 
 if __name__ == "__main__":      # python -m compression_amd.models.bls2017 compress in.png out.tfci

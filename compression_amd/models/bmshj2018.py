@@ -136,6 +136,24 @@ class BMSHJ2018Model(torch.nn.Module):
         self.entropy_model, self.side_entropy_model = self._models(True)
         return self
 
+    def _latents(self, x):
+        """(y, z, indexes, (x_shape, y_shape, z_shape)) of one batch of images: what compress() hands the coder."""
+        if x.dim() == 3:
+            x = x[None]
+        y = self.analysis_transform.unit(functional.image_to_unit(x, self.compute_dtype))
+        z = self.hyper_analysis_transform(torch.abs(y))
+        shapes = tuple(x.shape[1:-1]), tuple(y.shape[1:-1]), tuple(z.shape[1:-1])
+        z_hat = self.side_entropy_model.quantize(z)
+        indexes = self.hyper_synthesis_transform(z_hat)[:, :y.shape[1], :y.shape[2], :]
+        return y, z, indexes, shapes
+
+    def _reconstruction(self, z_hat, indexes, y_hat, x_shape):
+        x_hat = functional.unit_to_image(self.synthesis_transform.unit(y_hat)[:, :x_shape[0], :x_shape[1], :])
+        # produced on one stream, read on the other: alive until the caller drops x_hat (a tensor freed behind a
+        # kernel of ANOTHER stream goes back to its own stream's pool while that kernel may still read it)
+        x_hat._tfc_keep = (z_hat, indexes, y_hat)
+        return x_hat
+
     @torch.no_grad()
     def compress(self, x, device_result=False, lane=None):
         """uint8 [B, H, W, 3] -> (string[B], side_string[B], x_shape, y_shape, z_shape) —
@@ -146,14 +164,8 @@ class BMSHJ2018Model(torch.nn.Module):
         enqueues work; `lane` (compression_amd.pipeline.Lane) puts the transforms and the coder on their
         own streams / compute units."""
         lane = lane or inline_lane()
-        if x.dim() == 3:
-            x = x[None]
         with lane.on("transform"):
-            y = self.analysis_transform.unit(functional.image_to_unit(x, self.compute_dtype))
-            z = self.hyper_analysis_transform(torch.abs(y))
-            x_shape, y_shape, z_shape = tuple(x.shape[1:-1]), tuple(y.shape[1:-1]), tuple(z.shape[1:-1])
-            z_hat = self.side_entropy_model.quantize(z)
-            indexes = self.hyper_synthesis_transform(z_hat)[:, :y_shape[0], :y_shape[1], :]
+            y, z, indexes, shapes = self._latents(x)
         with lane.on("coder"):
             side_string = self.side_entropy_model.compress(z, device_result=device_result)
             string = self.entropy_model.compress(y, indexes, device_result=device_result)
@@ -161,7 +173,7 @@ class BMSHJ2018Model(torch.nn.Module):
             # produced on the transform stream, read by the coder stream: alive as long as the strings
             string._keep += [y, indexes]
             side_string._keep += [z]
-        return string, side_string, x_shape, y_shape, z_shape
+        return (string, side_string) + shapes
 
     @torch.no_grad()
     def decompress(self, string, side_string, x_shape, y_shape, z_shape, defer_sanity=False, lane=None):
@@ -184,10 +196,7 @@ class BMSHJ2018Model(torch.nn.Module):
             y_hat, oky = y_hat
             ok.append(oky)
         with lane.on("transform"):
-            x_hat = functional.unit_to_image(self.synthesis_transform.unit(y_hat)[:, :x_shape[0], :x_shape[1], :])
-            # produced on one stream, read on the other: alive until the caller drops x_hat (a tensor freed behind a
-            # kernel of ANOTHER stream goes back to its own stream's pool while that kernel may still read it)
-            x_hat._tfc_keep = (z_hat, indexes, y_hat)
+            x_hat = self._reconstruction(z_hat, indexes, y_hat, x_shape)
         return (x_hat, ok) if defer_sanity else x_hat
 
     @torch.no_grad()
@@ -196,19 +205,10 @@ class BMSHJ2018Model(torch.nn.Module):
         the pipelined lane kernels, whose serial chain is a few waves however many batches share the launch — the
         convolutions of other batches keep the rest of the chip): [(string handle, side handle, x_shape, y_shape,
         z_shape)], strings in HBM.  Same strings as compress() batch by batch."""
-        ys, zs, idxs, shapes = [], [], [], []
-        for x in xs:
-            x = x if x.dim() == 4 else x[None]
-            y = self.analysis_transform.unit(functional.image_to_unit(x, self.compute_dtype))
-            z = self.hyper_analysis_transform(torch.abs(y))
-            shapes.append((tuple(x.shape[1:-1]), tuple(y.shape[1:-1]), tuple(z.shape[1:-1])))
-            z_hat = self.side_entropy_model.quantize(z)
-            idxs.append(self.hyper_synthesis_transform(z_hat)[:, :y.shape[1], :y.shape[2], :])
-            ys.append(y)
-            zs.append(z)
-        side = self.side_entropy_model.compress_many(zs)
-        main = self.entropy_model.compress_many(ys, idxs)
-        return [(h, sh) + shp for h, sh, shp in zip(main, side, shapes)]
+        latents = [self._latents(x) for x in xs]
+        side = self.side_entropy_model.compress_many([z for _, z, _, _ in latents])
+        main = self.entropy_model.compress_many([y for y, _, _, _ in latents], [i for _, _, i, _ in latents])
+        return [(h, sh) + shapes for h, sh, (_, _, _, shapes) in zip(main, side, latents)]
 
     @torch.no_grad()
     def decompress_many(self, packed):
@@ -220,12 +220,8 @@ class BMSHJ2018Model(torch.nn.Module):
         z_hats, okz = self.side_entropy_model.decompress_many([p[1] for p in packed], packed[0][4])
         idxs = [self.hyper_synthesis_transform(z_hat)[:, :p[3][0], :p[3][1], :] for z_hat, p in zip(z_hats, packed)]
         y_hats, oky = self.entropy_model.decompress_many([p[0] for p in packed], idxs)
-        outs = []
-        for p, z_hat, ix, y_hat in zip(packed, z_hats, idxs, y_hats):
-            x_hat = functional.unit_to_image(self.synthesis_transform.unit(y_hat)[:, :p[2][0], :p[2][1], :])
-            x_hat._tfc_keep = (z_hat, ix, y_hat)
-            outs.append(x_hat)
-        return outs, [okz, oky]
+        return [self._reconstruction(z_hat, ix, y_hat, p[2])
+                for p, z_hat, ix, y_hat in zip(packed, z_hats, idxs, y_hats)], [okz, oky]
 
 
 if __name__ == "__main__":      # python -m compression_amd.models.bmshj2018 compress in.png out.tfci

@@ -262,62 +262,102 @@ def _check_prefix(handle_shape, value_shape, what="value"):
             f"does not start with handle.shape={list(handle_shape)}")
 
 
-def entropy_encode_channel(handle: EncoderHandle, value) -> EncoderHandle:
-    """EntropyEncodeChannel(handle, value) -> aliased handle."""
-    if handle.streams == 0:
-        raise ValueError(f"`handle` is empty: handle.shape={list(handle.shape)}")
-    value = _dev_i32(value, handle.device)
-    _check_prefix(handle.shape, value.shape)
-    elems = value.numel() // handle.streams
-    handle._keep.append(value)
-    handle.record(lambda h, v=value: entropy_encode_channel(h, v))
-    _lib.check(_lib.lib().tfc_encoder_encode(handle.ptr, value.data_ptr(), None, elems,
-                                             _lib.stream_ptr()))
-    return handle
+def _ptrs(pointers):
+    """The pointer array argument of a list entry of the C ABI."""
+    return (C.c_void_p * len(pointers))(*pointers)
 
 
-def entropy_encode_channel_many(handles, values):
-    """EntropyEncodeChannel for several independent handles (same lookup, same shape) as ONE launch
-    (include/tfc_hip.h tfc_encoder_encode_many): same results as calling entropy_encode_channel on each."""
+def _check_values(handles, values, indexes):
+    """What EntropyEncodeChannel / EntropyEncodeIndex check, for every job of a list call -> the elements per stream
+    (one count for the whole call)."""
+    if len(values) != len(handles) or (indexes is not None and len(indexes) != len(handles)):
+        raise ValueError("one value tensor (and, in index mode, one index tensor) per handle")
+    elems = set()
+    for k, (h, v) in enumerate(zip(handles, values)):
+        if h.streams == 0:
+            raise ValueError(f"`handle` is empty: handle.shape={list(h.shape)}")
+        _check_prefix(h.shape, v.shape)
+        if indexes is not None and indexes[k].dtype != torch.int32:
+            raise TypeError(f"expected int32 tensor, got {indexes[k].dtype}")
+        if indexes is not None and indexes[k].shape != v.shape:
+            raise ValueError(
+                f"'index' shape should match 'value' shape: index.shape={list(indexes[k].shape)} "
+                f"!= value.shape={list(v.shape)}")
+        elems.add(v.numel() // h.streams)
+    if len(elems) != 1:
+        raise ValueError("all values of one call must have the same shape")
+    return elems.pop()
+
+
+def encode_symbols(handles, values, indexes=None):
+    """EntropyEncodeChannel (`indexes` None) or EntropyEncodeIndex for a list of independent handles (same lookup, same
+    shape) as ONE launch (include/tfc_hip.h tfc_encoder_encode_many).  Every encode op below is a call of this."""
     handles = list(handles)
     if not handles:
         return handles
-    vals = []
-    for h, v in zip(handles, values):
-        if h.streams == 0:
-            raise ValueError(f"`handle` is empty: handle.shape={list(h.shape)}")
-        v = _dev_i32(v, h.device)
-        _check_prefix(h.shape, v.shape)
-        vals.append(v)
-        h._keep.append(v)
-        h.record(lambda hh, vv=v: entropy_encode_channel(hh, vv))
-    elems = {v.numel() // h.streams for h, v in zip(handles, vals)}
-    if len(elems) != 1:
-        raise ValueError("entropy_encode_channel_many: all values must have the same shape")
-    n = len(handles)
-    hp = (C.c_void_p * n)(*[h.ptr for h in handles])
-    vp = (C.c_void_p * n)(*[v.data_ptr() for v in vals])
-    _lib.check(_lib.lib().tfc_encoder_encode_many(n, hp, vp, None, elems.pop(), _lib.stream_ptr()))
+    values = [_dev_i32(v, h.device) for h, v in zip(handles, values)]
+    if indexes is not None:
+        indexes = [_dev_i32(i, h.device) for h, i in zip(handles, indexes)]
+    elems = _check_values(handles, values, indexes)
+    for k, (h, v) in enumerate(zip(handles, values)):
+        if indexes is None:
+            h._keep.append(v)
+            h.record(lambda hh, vv=v: encode_symbols([hh], [vv]))
+        else:
+            h._keep += [v, indexes[k]]
+            h.record(lambda hh, vv=v, ii=indexes[k]: encode_symbols([hh], [vv], [ii]))
+    _lib.check(_lib.lib().tfc_encoder_encode_many(
+        len(handles), _ptrs([h.ptr for h in handles]), _ptrs([v.data_ptr() for v in values]),
+        None if indexes is None else _ptrs([i.data_ptr() for i in indexes]), elems, _lib.stream_ptr()))
     return handles
+
+
+def encode_values(handles, ys, cdf_offset, *, qoffset=None, channels=0, indexes=None):
+    """encode_symbols with the quantise prologue of compress() inside the coder (tfc_encoder_encode_quantized_many /
+    tfc_encoder_encode_quantized_indexed_many): `ys` are contiguous device tensors of one floating-point dtype.  Channel
+    mode (`indexes` None) codes round(y - qoffset[c]) - cdf_offset[c] with table c of `channels`, the innermost
+    dimension's; index mode codes round(y) - cdf_offset[index] with table `index`.  `cdf_offset` (int32), `qoffset`
+    (float32 or None) and the int32 `indexes` are device tensors."""
+    handles = list(handles)
+    if not handles:
+        return handles
+    elems = _check_values(handles, ys, indexes)
+    dtype = ys[0].dtype
+    if dtype not in _DTYPE_CODE:
+        raise TypeError(f"values must be bfloat16, float16 or float32: {dtype}")
+    for k, (h, y) in enumerate(zip(handles, ys)):
+        if y.dtype != dtype or not y.is_contiguous():
+            raise TypeError(f"all values of one call must be contiguous and have the same dtype: {y.dtype}, {dtype}")
+        i = None if indexes is None else indexes[k]
+        h._keep += [y, cdf_offset, qoffset if i is None else i]
+        h.record(lambda hh, yy=y, ii=i: encode_values([hh], [yy], cdf_offset, qoffset=qoffset, channels=channels,
+                                                      indexes=None if ii is None else [ii]))
+    hp, yp = _ptrs([h.ptr for h in handles]), _ptrs([y.data_ptr() for y in ys])
+    if indexes is None:
+        _lib.check(_lib.lib().tfc_encoder_encode_quantized_many(
+            len(handles), hp, yp, _DTYPE_CODE[dtype], _lib.ptr(qoffset), cdf_offset.data_ptr(), channels, elems,
+            _lib.stream_ptr()))
+    else:
+        _lib.check(_lib.lib().tfc_encoder_encode_quantized_indexed_many(
+            len(handles), hp, yp, _DTYPE_CODE[dtype], _ptrs([i.data_ptr() for i in indexes]), cdf_offset.data_ptr(),
+            elems, _lib.stream_ptr()))
+    return handles
+
+
+def entropy_encode_channel(handle: EncoderHandle, value) -> EncoderHandle:
+    """EntropyEncodeChannel(handle, value) -> aliased handle."""
+    return encode_symbols([handle], [value])[0]
+
+
+def entropy_encode_channel_many(handles, values):
+    """EntropyEncodeChannel for several independent handles (same lookup, same shape) as ONE launch: same results as
+    calling entropy_encode_channel on each."""
+    return encode_symbols(handles, values)
 
 
 def entropy_encode_index(handle: EncoderHandle, index, value) -> EncoderHandle:
     """EntropyEncodeIndex(handle, index, value) -> aliased handle."""
-    if handle.streams == 0:
-        raise ValueError(f"`handle` is empty: handle.shape={list(handle.shape)}")
-    value = _dev_i32(value, handle.device)
-    index = _dev_i32(index, handle.device)
-    _check_prefix(handle.shape, value.shape)
-    if index.shape != value.shape:
-        raise ValueError(
-            f"'index' shape should match 'value' shape: index.shape={list(index.shape)} "
-            f"!= value.shape={list(value.shape)}")
-    elems = value.numel() // handle.streams
-    handle._keep += [value, index]
-    handle.record(lambda h, i=index, v=value: entropy_encode_index(h, i, v))
-    _lib.check(_lib.lib().tfc_encoder_encode(handle.ptr, value.data_ptr(), index.data_ptr(),
-                                             elems, _lib.stream_ptr()))
-    return handle
+    return encode_symbols([handle], [value], [index])[0]
 
 
 def _finalize_device(handle: EncoderHandle):
@@ -512,60 +552,86 @@ def _create_range_decoder(encoded, lookup) -> DecoderHandle:
     return DecoderHandle(shape, tables, device, out)
 
 
-def _decode(handle: DecoderHandle, index, shape, Tdecoded):
-    if Tdecoded not in (torch.int32, None):
-        raise TypeError("Tdecoded must be int32")
-    if handle.streams == 0:
-        raise ValueError(f"`handle` is empty: {list(handle.shape)}")
-    suffix = _shape_list(shape)
-    out_shape = tuple(handle.shape) + tuple(suffix)
-    elems = int(np.prod(suffix, dtype=np.int64))
-    out = torch.empty(out_shape, dtype=torch.int32, device=handle.device)
-    iptr = None
-    if index is not None:
-        index = _dev_i32(index, handle.device)
-        if tuple(index.shape) != out_shape:
+def _decode_targets(handles, shape, indexes, dtype):
+    """What EntropyDecodeChannel / EntropyDecodeIndex check, for every job of a list call -> (the output tensors
+    handle.shape + shape, the elements per stream)."""
+    suffix = tuple(_shape_list(shape))
+    if indexes is not None and len(indexes) != len(handles):
+        raise ValueError("one index tensor per handle")
+    outs = []
+    for k, h in enumerate(handles):
+        if h.streams == 0:
+            raise ValueError(f"`handle` is empty: {list(h.shape)}")
+        out_shape = h.shape + suffix
+        if indexes is not None and indexes[k].dtype != torch.int32:
+            raise TypeError(f"expected int32 tensor, got {indexes[k].dtype}")
+        if indexes is not None and tuple(indexes[k].shape) != out_shape:
             raise ValueError(
                 "'index' shape should match 'handle' shape + 'shape': "
-                f"index.shape={list(index.shape)}, handle.shape={list(handle.shape)}, "
-                f"shape={suffix}")
-        handle._keep.append(index)
-        iptr = index.data_ptr()
-    _lib.check(_lib.lib().tfc_decoder_decode(handle.ptr, iptr, out.data_ptr(), elems,
-                                             _lib.stream_ptr()))
-    return handle, out
+                f"index.shape={list(indexes[k].shape)}, handle.shape={list(h.shape)}, shape={list(suffix)}")
+        outs.append(torch.empty(out_shape, dtype=dtype, device=h.device))
+    return outs, int(np.prod(suffix, dtype=np.int64))
 
 
-def entropy_decode_channel(handle: DecoderHandle, shape, Tdecoded=torch.int32):
-    """EntropyDecodeChannel(handle, shape, Tdecoded) -> (aliased handle, decoded)."""
-    return _decode(handle, None, shape, Tdecoded)
-
-
-def entropy_decode_channel_many(handles, shape, Tdecoded=torch.int32):
-    """EntropyDecodeChannel for several independent handles as ONE launch
-    (tfc_decoder_decode_many) -> (handles, list of decoded tensors)."""
+def decode_symbols(handles, shape, indexes=None, Tdecoded=torch.int32):
+    """EntropyDecodeChannel (`indexes` None) or EntropyDecodeIndex for a list of independent handles as ONE launch
+    (tfc_decoder_decode_many) -> (handles, list of decoded tensors).  Every decode op below is a call of this."""
     if Tdecoded not in (torch.int32, None):
         raise TypeError("Tdecoded must be int32")
     handles = list(handles)
     if not handles:
         return handles, []
-    suffix = _shape_list(shape)
-    elems = int(np.prod(suffix, dtype=np.int64))
-    outs = []
-    for h in handles:
-        if h.streams == 0:
-            raise ValueError(f"`handle` is empty: {list(h.shape)}")
-        outs.append(torch.empty(tuple(h.shape) + tuple(suffix), dtype=torch.int32, device=h.device))
-    n = len(handles)
-    hp = (C.c_void_p * n)(*[h.ptr for h in handles])
-    op = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
-    _lib.check(_lib.lib().tfc_decoder_decode_many(n, hp, None, op, elems, _lib.stream_ptr()))
+    if indexes is not None:
+        indexes = [_dev_i32(i, h.device) for h, i in zip(handles, indexes)]
+    outs, elems = _decode_targets(handles, shape, indexes, torch.int32)
+    if indexes is not None:
+        for h, i in zip(handles, indexes):
+            h._keep.append(i)
+    _lib.check(_lib.lib().tfc_decoder_decode_many(
+        len(handles), _ptrs([h.ptr for h in handles]),
+        None if indexes is None else _ptrs([i.data_ptr() for i in indexes]), _ptrs([o.data_ptr() for o in outs]),
+        elems, _lib.stream_ptr()))
     return handles, outs
+
+
+def decode_values(handles, shape, dtype, cdf_offset, *, qoffset=None, channels=0, indexes=None):
+    """decode_symbols with the dequantise epilogue of decompress() inside the coder
+    (tfc_decoder_decode_dequantized_many / tfc_decoder_decode_dequantized_indexed_many) -> list of tensors of `dtype`
+    shaped handle.shape + shape: symbol + cdf_offset[c] + qoffset[c] in channel mode, symbol + cdf_offset[index] in
+    index mode (see encode_values)."""
+    handles = list(handles)
+    if not handles:
+        return []
+    if dtype not in _DTYPE_CODE:
+        raise TypeError(f"values must be bfloat16, float16 or float32: {dtype}")
+    outs, elems = _decode_targets(handles, shape, indexes, dtype)
+    for k, (h, o) in enumerate(zip(handles, outs)):
+        h._keep += [o, cdf_offset, qoffset if indexes is None else indexes[k]]
+    hp, yp = _ptrs([h.ptr for h in handles]), _ptrs([o.data_ptr() for o in outs])
+    if indexes is None:
+        _lib.check(_lib.lib().tfc_decoder_decode_dequantized_many(
+            len(handles), hp, yp, _DTYPE_CODE[dtype], _lib.ptr(qoffset), cdf_offset.data_ptr(), channels, elems,
+            _lib.stream_ptr()))
+    else:
+        _lib.check(_lib.lib().tfc_decoder_decode_dequantized_indexed_many(
+            len(handles), hp, _ptrs([i.data_ptr() for i in indexes]), yp, _DTYPE_CODE[dtype], cdf_offset.data_ptr(),
+            elems, _lib.stream_ptr()))
+    return outs
+
+
+def entropy_decode_channel(handle: DecoderHandle, shape, Tdecoded=torch.int32):
+    """EntropyDecodeChannel(handle, shape, Tdecoded) -> (aliased handle, decoded)."""
+    return handle, decode_symbols([handle], shape, None, Tdecoded)[1][0]
+
+
+def entropy_decode_channel_many(handles, shape, Tdecoded=torch.int32):
+    """EntropyDecodeChannel for several independent handles as ONE launch -> (handles, list of decoded tensors)."""
+    return decode_symbols(handles, shape, None, Tdecoded)
 
 
 def entropy_decode_index(handle: DecoderHandle, index, shape, Tdecoded=torch.int32):
     """EntropyDecodeIndex(handle, index, shape, Tdecoded) -> (aliased handle, decoded)."""
-    return _decode(handle, index, shape, Tdecoded)
+    return handle, decode_symbols([handle], shape, [index], Tdecoded)[1][0]
 
 
 def entropy_decode_finalize(handle: DecoderHandle) -> torch.Tensor:

@@ -4,6 +4,7 @@ What must hold: a deferred-error handle of the wave-per-stream family codes with
 still produces the oracle's bytes; range errors and an outgrown speculative slab surface at status /
 fetch; `compress(device_result=True)` + `decompress(defer_sanity=True)` on a lane of pipeline.StepLanes give
 the strings and images of the plain calls; several steps in flight do not disturb each other."""
+import math
 import os
 
 import numpy as np
@@ -279,3 +280,67 @@ def test_fused_quantise_on_the_lane_kernels(dtype):
         assert [bytes(s) for s in tfc.fetch_strings(handles[k])] == [bytes(s) for s in want[k]]
         assert torch.equal(got_hat[k], want_hat[k]) and torch.equal(many_hat[k], want_hat[k])
         assert torch.equal(want_hat[k], em.quantize(ys[k]))
+
+
+def _scale_fn(i):
+    return torch.exp(math.log(0.11) + (math.log(256.0) - math.log(0.11)) / 63 * i)
+
+
+@pytest.mark.parametrize("which,fused,n,dtype", [
+    pytest.param(which, fused, n, dtype, id=f"{which}-{'fused' if fused else 'unfused'}-{n}-{str(dtype)[6:]}")
+    for which in ("batched", "indexed") for fused in (True, False) for n in (1, 3)
+    for dtype in ((torch.float32, torch.bfloat16) if fused else (torch.float32,))])
+def test_every_coding_route_of_a_model_gives_the_reference_strings_and_the_quantised_values(which, fused, n, dtype):
+    """compress(), compress(device_result=True) and compress_many() are one coding routine per model, fused into the
+    coder's load or through tensor ops and int32 symbols: all give the strings of the CPU reference coder on the symbols
+    computed here with tensor ops, and decompress() of the strings, decompress(defer_sanity=True) of the handle and
+    decompress_many() of the handles give the quantised latent bit for bit.  70 streams: one past a wave of lanes."""
+    from oracle import oracle
+    port = oracle.port()
+    torch.manual_seed(3)
+    if which == "batched":
+        C = 24
+        prior = tfc.NoisyNormal(loc=torch.linspace(-0.7, 0.7, C), scale=torch.linspace(0.3, 7.0, C))
+        em = tfc.ContinuousBatchedEntropyModel(prior, coding_rank=3, compression=True, bottleneck_dtype=dtype,
+                                               quantization_offset=torch.linspace(-0.4, 0.4, C))
+        ys = [(torch.randn(70, 9, 13, C) * torch.linspace(0.3, 7.0, C) * 1.3).to(dtype) for _ in range(n)]
+        args = [(y.cuda(),) for y in ys]
+        sizes = [(9, 13)] * n
+        many_sizes = sizes[0]
+        wants = []
+        for y in ys:
+            sym = torch.round(y - em.quantization_offset).to(torch.int32).reshape(70, -1) - em.cdf_offset.repeat(9 * 13)
+            wants.append(port.encode(em.cdf.numpy(), sym.numpy())[0])
+        values = [em.quantize(y) for y in ys]
+    else:
+        em = tfc.LocationScaleIndexedEntropyModel(tfc.NoisyNormal, num_scales=64, scale_fn=_scale_fn, coding_rank=3,
+                                                  compression=True, bottleneck_dtype=dtype)
+        idxs = [torch.randint(0, 64, (70, 6, 8, 16)).float() for _ in range(n)]
+        ys = [(torch.randn(70, 6, 8, 16) * _scale_fn(idx) * 1.3).to(dtype) for idx in idxs]
+        args = [(y.cuda(), idx.cuda()) for y, idx in zip(ys, idxs)]
+        sizes = many_sizes = [idx.cuda() for idx in idxs]
+        wants = []
+        for y, idx in zip(ys, idxs):
+            flat = idx.to(torch.int32)
+            sym = torch.round(y).to(torch.int32) - em.cdf_offset[flat.long()]
+            wants.append(port.encode(em.cdf.numpy(), sym.reshape(70, -1).numpy(), index=flat.reshape(70, -1).numpy())[0])
+        values = [torch.round(y) for y in ys]
+    em.fused = fused
+
+    def strings(s):
+        return [bytes(b) for b in np.asarray(s, dtype=object).reshape(-1)]
+
+    plain = [em.compress(*a) for a in args]
+    single = [em.compress(*a, device_result=True) for a in args]
+    many = em.compress_many(*[list(column) for column in zip(*args)])
+    assert len(many) == n
+    from_strings = [em.decompress(s, size) for s, size in zip(plain, sizes)]
+    from_handle = [em.decompress(h, size, defer_sanity=True) for h, size in zip(single, sizes)]
+    from_many, ok = em.decompress_many(many, many_sizes)
+    assert tuple(ok.shape) == (n, 70) and bool(ok.cpu().all())
+    for k in range(n):
+        assert plain[k].shape == (70,) and strings(plain[k]) == wants[k]
+        assert strings(tfc.fetch_strings(single[k])) == wants[k] and strings(tfc.fetch_strings(many[k])) == wants[k]
+        assert bool(from_handle[k][1].cpu().all())
+        for got in (from_strings[k], from_handle[k][0], from_many[k]):
+            assert got.dtype == dtype and torch.equal(got.cpu(), values[k])
