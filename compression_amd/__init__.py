@@ -25,6 +25,9 @@ from .ops.checkerboard_ops import (CHECKER_TAPS, CheckerboardParams, Checkerboar
                                    checkerboard_decode, checkerboard_mask, checkerboard_merge, checkerboard_parameters,
                                    checkerboard_parameters_reference, checkerboard_place, checkerboard_scan,
                                    checkerboard_scan_reference, checkerboard_split)
+from .ops.scctx_ops import (SpaceChannelParams, SpaceChannelScan, scctx_decode, scctx_encode,  # noqa: F401
+                            scctx_parameters, scctx_parameters_reference, scctx_place, scctx_scan,
+                            scctx_scan_reference)
 from .ops.round_ops import round_st, soft_round, soft_round_conditional_mean, soft_round_inverse  # noqa: F401
 from .datasets import *  # noqa: F401,F403
 from .datasets.clip_dataset import ClipDataset  # noqa: F401

@@ -173,6 +173,9 @@ SIGNATURES = {
     "tfc_checkerboard_params": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int,
                                        _vp, _vp, _vp, _vp, _vp]),
     "tfc_checkerboard_place": (_int, [_int, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp]),
+    "tfc_scctx_params": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int,
+                                _int, _vp, _vp, _vp, _vp, _vp]),
+    "tfc_scctx_place": (_int, [_int, _vp, _vp, _vp, _i64, _i64, _i64, _int, _int, _int, _vp]),
 }
 
 # the dtype argument of the C ABI: entries on float32 / bfloat16 tensors, and those that take float16 as well

@@ -2,7 +2,8 @@
 // image compression" (CVPR 2021) on gfx950: for all positions of one pass, the masked 5x5 correlation over the decoded
 // anchors, the pointwise entropy-parameter network and the quantisation, in ONE launch per pass
 // (checkerboard_params_kernel), and the decoder's store of a decoded pass (checkerboard_place_kernel).
-// include/tfc_hip.h states the definition.
+// include/tfc_hip.h states the definition.  The MFMA walk and the layer driver described below live in ckb_engine.h,
+// which space_channel.hip shares.
 //
 // A workgroup of CKB_THREADS threads owns CKB_TILE = 32 consecutive compact positions of one image and runs the four
 // dense layers on v_mfma_f32_32x32x2_f32: the 32 positions are the rows of the A operand, 32 output columns the
@@ -29,8 +30,7 @@
 //
 // Nothing waits on another workgroup; every loop bound comes from the shapes.  In pass 1 the kernel reads y_hat at
 // anchors only and writes it at the other positions only, so concurrent workgroups never touch the same element.
-#include "context_shared.h"
-#include "mfma_types.h"
+#include "ckb_engine.h"
 
 #include "../../include/tfc_hip.h"
 
@@ -52,163 +52,6 @@ struct CkbArgs {
   int32_t* sym;
 };
 
-// Compact slot -> raster index i * Wl + j of the position
-__device__ __forceinline__ void ckb_position(int64_t slot, int pass, int wl, int* i, int* j) {
-  if (wl & 1) {
-    const int64_t n = 2 * slot + pass;
-    *i = static_cast<int>(n / wl);
-    *j = static_cast<int>(n - static_cast<int64_t>(*i) * wl);
-  } else {
-    const int half = wl >> 1;
-    *i = static_cast<int>(slot / half);
-    const int c = static_cast<int>(slot - static_cast<int64_t>(*i) * half);
-    *j = 2 * c + ((*i + pass) & 1);
-  }
-}
-
-// acc[q] += in[0 .. Kp) x w[0 .. Kp)[col q], k ascending.  `in` is LDS, k-major rows of CKB_TILE floats; `wq[q]` points
-// at w[lane >> 5][column of block q for this lane]; Kp is a multiple of CTX_KPAD, so it is even.
-template <int NQ>
-__device__ __forceinline__ void ckb_mma(f32x16 (&acc)[NQ], const float* in, int Kp, const float* (&wq)[NQ], int O) {
-  constexpr int G = CKB_GROUP;
-  const int lane = threadIdx.x & 63;
-  const float* a = in + lane;
-  const size_t step = 2 * static_cast<size_t>(O);
-  const int steps = Kp >> 1, groups = steps / G;
-  // whole groups of G k-steps: the next group's weights are on their way while this one is multiplied
-  float next[G][NQ];
-  auto load = [&](int g) {
-#pragma unroll
-    for (int u = 0; u < G; ++u)
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) next[u][q] = wq[q][static_cast<size_t>(g * G + u) * step];
-  };
-  if (groups > 0) load(0);
-  for (int g = 0; g < groups; ++g) {
-    float av[G], bv[G][NQ];
-#pragma unroll
-    for (int u = 0; u < G; ++u) {
-      av[u] = a[static_cast<size_t>(g * G + u) * (2 * CKB_TILE)];
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) bv[u][q] = next[u][q];
-    }
-    if (g + 1 < groups) load(g + 1);
-#pragma unroll
-    for (int u = 0; u < G; ++u)
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u][q], acc[q], 0, 0, 0);
-  }
-  for (int s = groups * G; s < steps; ++s) {
-    const float av = a[static_cast<size_t>(s) * (2 * CKB_TILE)];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-      acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, wq[q][static_cast<size_t>(s) * step], acc[q], 0, 0, 0);
-  }
-}
-static_assert(CTX_KPAD % 2 == 0, "a k-step of the MFMA is two input rows");
-
-// What a thread fetches of one staged chunk: position (tid & 31) of the tile, 8 consecutive input rows.
-constexpr int CKB_STAGE_PER_THREAD = CKB_STAGE_K * CKB_TILE / CKB_THREADS;
-static_assert(CKB_STAGE_PER_THREAD * (CKB_THREADS / CKB_TILE) == CKB_STAGE_K, "a chunk is 8 row groups of 32 positions");
-
-struct CkbTile {
-  int b, np;                // image, live positions of the tile
-  int pi, pj;               // this thread's staged position (tid & 31), or pi < 0 when it is beyond the pass
-};
-
-// One layer for the tile: out (k-major, LDS) = act(bias + chain).  The chain takes the LDS-resident rows [0, Kl) of
-// `in` against wl first, then `taps` staged segments: rows [0, Cp) of src[the position, moved by the tap when
-// `shifted`][C channels] against wseg + tap * Cp * O.  A wave accumulates NQ column blocks side by side (blocks
-// wave, wave + 4, ...); NQ is the same for the whole workgroup, and a block beyond the layer's width computes a
-// live column again and drops it.  All threads of the workgroup call it together.  `store` receives (column, first
-// of four positions, the four values).
-template <int NQ, typename Store>
-__device__ __forceinline__ void ckb_layer(const CkbArgs& a, const CkbTile& t, float* stage, const float* in, int Kl,
-                                          const float* wl, const float* src, int C, int Cp, int taps, bool shifted,
-                                          const float* wseg, const float* bias, int O, int Op, Store store) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
-  const int col = lane & 31, kk = lane >> 5;
-  const int nblk = (Op + 31) >> 5;
-  const int spos = threadIdx.x & (CKB_TILE - 1), sk = (threadIdx.x / CKB_TILE) * CKB_STAGE_PER_THREAD;
-  const int per_tap = (Cp + CKB_STAGE_K - 1) / CKB_STAGE_K;
-  const int chunks = taps * per_tap;
-
-  for (int base = 0; base < nblk; base += (CKB_THREADS / 64) * NQ) {
-    f32x16 acc[NQ];
-    const float* wq[NQ];
-    int cq[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      cq[q] = (base + wave + 4 * q) * 32 + col;
-      const int c = min(cq[q], O - 1);
-      const float bv = bias[c];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[q][r] = bv;
-      wq[q] = wl + static_cast<size_t>(kk) * O + c;
-    }
-    if (Kl > 0) ckb_mma<NQ>(acc, in, Kl, wq, O);
-    if (chunks > 0) {
-      float r[CKB_STAGE_PER_THREAD];
-      auto fetch = [&](int c) {
-        const int tap = c / per_tap, k0 = (c - tap * per_tap) * CKB_STAGE_K + sk;
-        int ii = t.pi, jj = t.pj;
-        if (shifted) {
-          ii += ckb_tap_di(tap);
-          jj += ckb_tap_dj(tap);
-        }
-        const bool live = t.pi >= 0 && ii >= 0 && ii < a.hl && jj >= 0 && jj < a.wl;
-        const float* row = src + ((static_cast<int64_t>(t.b) * a.hl + (live ? ii : 0)) * a.wl + (live ? jj : 0)) * C;
-#pragma unroll
-        for (int e = 0; e < CKB_STAGE_PER_THREAD; ++e) r[e] = (live && k0 + e < C) ? row[k0 + e] : 0.f;
-      };
-      fetch(0);
-      for (int c = 0; c < chunks; ++c) {
-        const int tap = c / per_tap, k0 = (c - tap * per_tap) * CKB_STAGE_K;
-        const int kn = min(CKB_STAGE_K, Cp - k0);
-#pragma unroll
-        for (int e = 0; e < CKB_STAGE_PER_THREAD; ++e) stage[(sk + e) * CKB_TILE + spos] = r[e];
-        __syncthreads();
-        if (c + 1 < chunks) fetch(c + 1);
-        const float* wb = wseg + (static_cast<size_t>(tap) * Cp + k0 + kk) * O;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) wq[q] = wb + min(cq[q], O - 1);
-        ckb_mma<NQ>(acc, stage, kn, wq, O);
-        __syncthreads();
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      if (cq[q] < Op) {
-        const bool live = cq[q] < O;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          f32x4 v;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = live ? acc[q][4 * g + e] : 0.f;
-          store(cq[q], 8 * g + 4 * kk, v);
-        }
-      }
-    }
-  }
-}
-
-// ckb_layer with the block count of the layer's width: ceil(blocks / 4), at most CKB_BLOCKS (wider layers take turns)
-template <typename Store>
-__device__ __forceinline__ void ckb_layer_n(const CkbArgs& a, const CkbTile& t, float* stage, const float* in, int Kl,
-                                            const float* wl, const float* src, int C, int Cp, int taps, bool shifted,
-                                            const float* wseg, const float* bias, int O, int Op, Store store) {
-  const int per_wave = (((Op + 31) >> 5) + 3) >> 2;
-  switch (per_wave) {                 // the same for every thread of the grid
-    case 1: ckb_layer<1>(a, t, stage, in, Kl, wl, src, C, Cp, taps, shifted, wseg, bias, O, Op, store); break;
-    case 2: ckb_layer<2>(a, t, stage, in, Kl, wl, src, C, Cp, taps, shifted, wseg, bias, O, Op, store); break;
-    case 3: ckb_layer<3>(a, t, stage, in, Kl, wl, src, C, Cp, taps, shifted, wseg, bias, O, Op, store); break;
-    case 4: ckb_layer<4>(a, t, stage, in, Kl, wl, src, C, Cp, taps, shifted, wseg, bias, O, Op, store); break;
-    default: ckb_layer<CKB_BLOCKS>(a, t, stage, in, Kl, wl, src, C, Cp, taps, shifted, wseg, bias, O, Op, store); break;
-  }
-}
-static_assert(CKB_BLOCKS == 5, "ckb_layer_n lists the block counts");
-
 template <int PASS>
 __global__ void __launch_bounds__(CKB_THREADS) checkerboard_params_kernel(const CkbArgs a) {
   __shared__ __attribute__((aligned(16))) float lds[CKB_LDS_FLOATS];
@@ -222,6 +65,8 @@ __global__ void __launch_bounds__(CKB_THREADS) checkerboard_params_kernel(const 
 
   CkbTile t;
   t.b = b;
+  t.hl = a.hl;
+  t.wl = a.wl;
   t.np = static_cast<int>(min<int64_t>(CKB_TILE, a.positions - slot0));
   {
     const int sp = threadIdx.x & (CKB_TILE - 1);
@@ -229,15 +74,6 @@ __global__ void __launch_bounds__(CKB_THREADS) checkerboard_params_kernel(const 
     t.pj = 0;
     if (sp < t.np) ckb_position(slot0 + sp, PASS, a.wl, &t.pi, &t.pj);
   }
-  auto to = [](float* buf, bool lrelu) {
-    return [buf, lrelu](int col, int pos, f32x4 v) {
-      if (lrelu) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = ctx_lrelu(v[e]);
-      }
-      *reinterpret_cast<f32x4*>(buf + static_cast<size_t>(col) * CKB_TILE + pos) = v;
-    };
-  };
 
   // ctx -> A: the bias alone for the anchors, the bias and the 12 taps' chain for the rest
   if (PASS == 0) {
@@ -247,20 +83,12 @@ __global__ void __launch_bounds__(CKB_THREADS) checkerboard_params_kernel(const 
       bufA[e] = k < L.c2 ? bc[k] : 0.f;
     }
   } else {
-    ckb_layer_n(a, t, stage, nullptr, 0, a.packed, a.y_hat, M, L.mp, CTX_TAPS, true, a.packed + L.wc, a.packed + L.bc,
-              L.c2, L.c2p, to(bufA, false));
+    const CkbSeg none = {};
+    const CkbSeg anchors = {a.y_hat, a.packed + L.wc, M, M, L.mp, CTX_TAPS, 1, 2};
+    ckb_layer_n(t, stage, nullptr, 0, a.packed, 1, anchors, none, a.packed + L.bc, L.c2, L.c2p, ckb_store_to(bufA, false));
   }
   __syncthreads();
-  // h1 -> B: the context rows from A, then the hyperprior rows staged from psi
-  ckb_layer_n(a, t, stage, bufA, L.c2p, a.packed + L.w1c, a.psi, L.p, L.pp, 1, false, a.packed + L.w1p, a.packed + L.b1,
-            L.h1, L.h1p, to(bufB, true));
-  __syncthreads();
-  ckb_layer_n(a, t, stage, bufB, L.h1p, a.packed + L.w2, nullptr, 0, 0, 0, false, nullptr, a.packed + L.b2, L.h2, L.h2p,
-            to(bufA, true));
-  __syncthreads();
-  ckb_layer_n(a, t, stage, bufA, L.h2p, a.packed + L.w3, nullptr, 0, 0, 0, false, nullptr, a.packed + L.b3, L.c2, L.c2,
-            to(bufB, false));
-  __syncthreads();
+  ckb_network(t, L, a.packed, a.psi, bufA, bufB, stage);
 
   // the outputs of the tile, channels innermost
   const float hi = static_cast<float>(a.num_scales - 1);

@@ -129,7 +129,7 @@ def load_checkpoint(model, state_dict):
 # The constructor arguments a model may have beyond lmbda and num_filters, as flags of `train`
 # (bmshj2018.py:449-457, ms2020.py:619-639); the defaults are the constructor's own.
 MODEL_FLAGS = {"num_scales": int, "scale_min": float, "scale_max": float, "latent_depth": int,
-               "hyperprior_depth": int, "num_slices": int, "max_support_slices": int}
+               "hyperprior_depth": int, "num_slices": int, "max_support_slices": int, "stream_positions": int}
 
 
 def compute_dtype_of(precision_policy):

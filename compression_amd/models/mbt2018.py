@@ -67,14 +67,17 @@ class HyperSynthesisTransform(torch.nn.Module):
 
 
 class EntropyParameters(torch.nn.Module):
-    """Pointwise 4M -> 10M / 3 -> 8M / 3 -> 2M on concat(context features, psi), leaky ReLU (0.2) between."""
+    """Pointwise 4M -> 10M / 3 -> 8M / 3 -> 2M on concat(context features, psi), leaky ReLU (0.2) between.  With a
+    `hyper_depth` P other than 2M (a channel group of models/elic2022.py) the input is 2M + P wide and the hidden widths
+    keep their thirds between input and output: 2M + 2P // 3 and 2M + P // 3."""
 
-    def __init__(self, latent_depth):
+    def __init__(self, latent_depth, hyper_depth=None):
         super().__init__()
         M = latent_depth
-        h1, h2 = max(10 * M // 3, 1), max(8 * M // 3, 1)
+        P = 2 * M if hyper_depth is None else int(hyper_depth)
+        h1, h2 = 2 * M + 2 * P // 3, 2 * M + P // 3
         kw = dict(corr=True, use_bias=True, kernel_parameter="variable", activation=None)
-        self.layer_0 = _conv(h1, 1, 4 * M, **kw)
+        self.layer_0 = _conv(h1, 1, 2 * M + P, **kw)
         self.layer_1 = _conv(h2, 1, h1, **kw)
         self.layer_2 = _conv(2 * M, 1, h2, **kw)
 
@@ -85,8 +88,9 @@ class EntropyParameters(torch.nn.Module):
 class HyperpriorContextModel(torch.nn.Module):
     """A mean-scale hyperprior whose entropy parameters come from psi and a context model over decoded values: what
     `MBT2018Model` and `Checkerboard2021Model` share.  A subclass names its context layer and packed-parameter class and
-    supplies `_scan`, `_write_strings` and `_read_strings` (and `_check_latent` where a latent can be too small); with
-    `context=False` the class is the hyperprior alone."""
+    supplies `_scan`, `_write_strings` and `_read_strings` (and `_check_latent` where a latent can be too small); a
+    scheme with more than one context layer (models/elic2022.py) builds its own modules in `_build_context` and supplies
+    `_training_parameters` and `context_params` as well.  With `context=False` the class is the hyperprior alone."""
 
     context_layer = params_class = None
 
@@ -105,8 +109,7 @@ class HyperpriorContextModel(torch.nn.Module):
         self.hyper_synthesis_transform = HyperSynthesisTransform(num_filters, M)
         self.hyperprior = distributions.NoisyDeepFactorized(batch_shape=(num_filters,))
         if self.context:
-            self.context_prediction = self.context_layer(2 * M, M)
-            self.entropy_parameters = EntropyParameters(M)
+            self._build_context()
         self.em_y = self.em_z = None
         self._packed = None
 
@@ -147,6 +150,18 @@ class HyperpriorContextModel(torch.nn.Module):
         return self.hyper_synthesis_transform(z_hat)[:, :y_shape[0], :y_shape[1], :].contiguous()
 
     # --- what a context scheme supplies -------------------------------------------------------------------------------
+    def _build_context(self):
+        """Creates the context modules; a scheme with other modules also overrides `context_params` and
+        `_training_parameters`."""
+        self.context_prediction = self.context_layer(2 * self.latent_depth, self.latent_depth)
+        self.entropy_parameters = EntropyParameters(self.latent_depth)
+
+    def _training_parameters(self, y_tilde, psi):
+        """(mu, indexes) of every position in parallel, teacher-forced on the noisy latent."""
+        M = self.latent_depth
+        out = self.entropy_parameters(torch.cat([self.context_prediction(y_tilde), psi], dim=-1))
+        return out[..., :M].contiguous(), out[..., M:].contiguous()
+
     def _check_latent(self, y_shape):
         """Raises for a latent the scheme cannot code."""
 
@@ -184,8 +199,7 @@ class HyperpriorContextModel(torch.nn.Module):
             # one noise sample: the same y + u feeds the context convolution, the rate and the synthesis
             u = torch.rand_like(y) - 0.5
             y_tilde = y + u
-            out = self.entropy_parameters(torch.cat([self.context_prediction(y_tilde), psi], dim=-1))
-            mu, indexes = out[..., :M].contiguous(), out[..., M:].contiguous()
+            mu, indexes = self._training_parameters(y_tilde, psi)
             _, y_bits = em_y(y.float(), indexes.float(), loc=mu.float(), training=True, noise=u.float())
             y_hat = y_tilde
         else:

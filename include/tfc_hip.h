@@ -1111,6 +1111,49 @@ int tfc_checkerboard_params(int pass, const float* y, float* y_hat, const float*
 int tfc_checkerboard_place(int pass, const float* sym, const float* mu, float* y_hat, int64_t batch, int64_t hl,
                            int64_t wl, int m, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Space-channel context model, SCCTX (after He, Yang, Peng, Mao, Qin, Wang 2022) */
+/* ------------------------------------------------------------------------ */
+
+/* The context model of "ELIC: efficient learned image compression with unevenly grouped space-channel contextual
+ * adaptive coding" (CVPR 2022): the channels of the latent are cut into G groups, the checkerboard above runs inside
+ * every group, and a group sees all earlier groups.  The reference tree carries no program text for it: the
+ * definition, the stream format and the layer shapes are this project's own, and parity with anyone's checkpoints is
+ * unpinned.  With y [batch, Hl, Wl, M], psi [batch, Hl, Wl, P], y_hat = 0 outside the latent, groups (M_0 .. M_{G-1})
+ * with sum M and c_g = M_0 + .. + M_{g-1}, the coding order is group 0 pass 0, group 0 pass 1, group 1 pass 0, ...:
+ * 2 G steps, each parallel over the positions of its pass (anchors, i + j even, are pass 0).  Step (g, pass):
+ *   ctx_g = bc_g
+ *         + sum over ALL 25 taps (di, dj) of the 5x5 window, row-major, channels c < c_g ascending, of
+ *               y_hat[i + di, j + dj, c] . Wch_g[di + 2, dj + 2, c, :]                       (nothing for g = 0)
+ *         + pass 1 only: sum over the 12 checkerboard taps (di + dj odd, row-major), the group's channels ascending, of
+ *               y_hat[i + di, j + dj, c_g + c] . Wsp_g[di + 2, dj + 2, c, :]                              -> 2 M_g
+ *   h1 = lrelu(b1_g + [ctx_g, psi] W1_g)   h2 = lrelu(b2_g + h1 W2_g)   out = b3_g + h2 W3_g        lrelu slope 0.2
+ *   mu = out[:M_g]   index_float = out[M_g:]   idx = tfc_index_prepare(index_float, num_scales)
+ *   sym = int32(rint(y[.., c_g + c] - mu))  (half to even)        y_hat[.., c_g + c] = float32(sym) + mu
+ * all float32; compact order as above, [batch, N_pass, M_g].  With G = 1 this is the checkerboard model, term for
+ * term and in the same order.
+ * Every output element is one chain of float32 fused multiply-adds that starts from its bias and takes one input row
+ * per fmaf in ascending k, in the order written above: the earlier-group taps, then the own-group taps, then (first
+ * layer) the 2 M_g context rows, then the P hyperprior rows.  A neighbour outside the latent and a padded row enter
+ * as zeros and are never skipped; K is never split across waves.  The order depends on (c_g, M_g, P, H1, H2) alone.
+ * `packed` DEV float32 [packed_floats]: ONE GROUP's buffer in the layout of csrc/space_channel_params.h
+ * (scctx_layout): ctx_layout(M_g, P, H1, H2) with Wsp_g on the checkerboard taps, then Wch_g [25][c_g padded][2 M_g].
+ * Checked on the host before any launch: pass, M, c_g, M_g (the group inside the latent), the sizes (as
+ * tfc_checkerboard_params with M_g for M: the activations of 32 positions of THIS group within 160 KiB of LDS), Hl,
+ * Wl, batch, num_scales, packed_floats, null pointers.  batch == 0, or a pass without positions, launches nothing. */
+
+/* The parameters of step (g, pass) for all its positions, ONE launch.  y_hat DEV [batch, Hl, Wl, M] is read at the
+ * channels below c_g everywhere and (pass 1) at the group's channels at anchors; when `y` is given it is written at
+ * the group's channels at the pass's positions.  mu, index_float DEV float32 and idx DEV int32 [batch, N_pass, M_g];
+ * `y` DEV [batch, Hl, Wl, M] or NULL (the decoder): when given, sym DEV int32 [batch, N_pass, M_g] is written too. */
+int tfc_scctx_params(int pass, const float* y, float* y_hat, const float* psi, const float* packed,
+                     int64_t packed_floats, int64_t batch, int64_t hl, int64_t wl, int m, int cg, int mg, int p, int h1,
+                     int h2, int num_scales, float* mu, float* index_float, int32_t* idx, int32_t* sym, void* stream);
+/* The decoder's store of a decoded step: y_hat[position, c_g + c] = sym + mu, the same single float32 add, from
+ * compact sym (float32) and mu [batch, N_pass, M_g] into y_hat [batch, Hl, Wl, M]. */
+int tfc_scctx_place(int pass, const float* sym, const float* mu, float* y_hat, int64_t batch, int64_t hl, int64_t wl,
+                    int m, int cg, int mg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
