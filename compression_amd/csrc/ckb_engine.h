@@ -1,13 +1,35 @@
-// The engine that checkerboard.hip and space_channel.hip share: the compact order of a pass, the MFMA walk over K with
-// the weights a group of k-steps ahead (ckb_mma) and the layer driver for one tile of CKB_TILE positions (ckb_layer).
-// The comment at the head of checkerboard.hip describes the plan; the constants are those of context_params.h.
+// The engine of the checkerboard kernels (space_channel.hip; the checkerboard context model of He, Zheng, Sun, Wang and
+// Qin, CVPR 2021, is their one-group case): the compact order of a pass, the MFMA walk over K with the weights a group
+// of k-steps ahead (ckb_mma) and the layer driver for one tile of CKB_TILE positions (ckb_layer).  The constants are
+// those of context_params.h.  The plan:
 //
-// Every output element is ONE chain: its bias, then one fmaf per input row in ascending k.  v_mfma_f32_32x32x2_f32 is
-// bit for bit D = fmaf(a[k+1], b[k+1], fmaf(a[k], b[k], C)); rows and columns of an MFMA do not interact; nothing here
-// splits K across waves.  A layer's chain takes the LDS-resident rows first and then up to two staged segments in the
-// order given: a segment is a channel range of a [B, Hl, Wl, stride] tensor seen through a list of taps of the 5x5
-// window, taps in ascending order, the channels of a tap ascending, a neighbour outside the latent and a padded row
-// entering as zeros (never skipped).
+// A workgroup of CKB_THREADS threads owns CKB_TILE = 32 consecutive compact positions of one image and runs the four
+// dense layers on v_mfma_f32_32x32x2_f32: the 32 positions are the rows of the A operand, 32 output columns the
+// columns of B, and a wave accumulates up to CKB_BLOCKS column blocks side by side (16 accumulator registers each)
+// while it walks K.  That instruction is bit for bit D = fmaf(a[k+1], b[k+1], fmaf(a[k], b[k], C)), so every output
+// element is ONE chain: its bias, then one fmaf per input row in ascending k (for the correlation: taps in row-major
+// order, the channels of a tap ascending, a neighbour outside the latent contributing fmaf(0, w, acc); for the first
+// layer: the context features, then the P hyperprior features).  Rows and columns of an MFMA do not interact, and
+// nothing here splits K across waves, so the chain depends on the sizes alone: not on the batch, the tile, the slot in
+// the tile or the neighbours that exist.  Encoder and decoder run the same kernel.
+//
+// Activations stay in LDS between the layers, k-major: row k holds the 32 positions' values of feature k, so the A
+// operand of k-step s is the 64 consecutive floats at row 2 s, one ds_read_b32 without a bank conflict, and an
+// accumulator column goes back as four 16-byte stores.  Buffer A holds ctx, then h2; buffer B holds h1, then the
+// output; a third region stages the gathered inputs (a tap's y_hat rows, psi) CKB_STAGE_K rows at a time, the next
+// chunk's global loads in flight while the current one is multiplied.  [ctx, psi] are two K ranges of the first layer.
+// With the checkerboard model's widths A is 64 KiB and B 80 KiB: the kernel declares gfx950's whole 160 KiB of LDS, on
+// purpose (one workgroup of four waves per CU, one wave per SIMD, which is what the f32 MFMA needs to reach its rate).
+//
+// Weights: no two waves of a workgroup use the same weight element (a wave owns its columns for all 32 positions),
+// so a trip through LDS would add traffic and save none; each lane loads its B operand, one float of the packed
+// buffer, straight into a register, 128 contiguous bytes per half wave, eight k-steps ahead.  The whole packed buffer
+// is read once per tile of 32 positions.
+//
+// A layer's chain takes the LDS-resident rows first and then up to two staged segments in the order given: a segment
+// is a channel range of a [B, Hl, Wl, stride] tensor seen through a list of taps of the 5x5 window, taps in ascending
+// order, the channels of a tap ascending, a neighbour outside the latent and a padded row entering as zeros (never
+// skipped).
 #pragma once
 #include "context_shared.h"
 #include "mfma_types.h"

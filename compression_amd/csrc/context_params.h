@@ -99,7 +99,7 @@ inline int64_t ctx_workspace_bytes(int64_t batch, int64_t hl, int64_t wl, int64_
   return (pre + 15) / 16 * 16 + batch * hl * 16;
 }
 
-// ---- the checkerboard context model (checkerboard.hip) -------------------------------------------------------------
+// ---- the checkerboard context model (ckb_engine.h, space_channel.hip) ----------------------------------------------
 // Same packed buffer (ctx_layout), the same CTX_TAPS x Mp rows of wc; only the tap list differs: the 12 offsets of the
 // 5x5 window with di + dj odd, row-major.  Those are the odd elements of the window counted row-major, so packed tap k
 // is element 2 k + 1: (di, dj) = (ckb_tap_di(k), ckb_tap_dj(k)) = (-2,-1) (-2,1) (-1,-2) (-1,0) (-1,2) (0,-1) (0,1) ...
@@ -123,7 +123,7 @@ inline int64_t ckb_positions(int64_t hl, int64_t wl, int pass) { return (hl * wl
 inline int ckb_rows_a(const ContextLayout& L) { return L.a_floats; }
 inline int ckb_rows_b(const ContextLayout& L) { return L.b_floats; }
 
-// The checks of tfc_checkerboard_params beyond ctx_layout / ctx_check_shape; null, or the text.
+// The checks of tfc_checkerboard_params / tfc_scctx_params beyond ctx_layout / ctx_check_shape; null, or the text.
 inline const char* ckb_check(int pass, int64_t batch, int64_t hl, int64_t wl, const ContextLayout& L) {
   if (pass != 0 && pass != 1) return "pass must be 0 or 1";
   const int64_t rows = static_cast<int64_t>(ckb_rows_a(L)) + ckb_rows_b(L);

@@ -1,4 +1,4 @@
-// What context_model.hip and checkerboard.hip share beyond context_params.h, which stays free of device types and of
+// What context_model.hip and ckb_engine.h share beyond context_params.h, which stays free of device types and of
 // the library's error state: the two element-wise device helpers and the size checks every entry point opens with.
 #pragma once
 #include "common.h"

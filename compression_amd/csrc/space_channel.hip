@@ -1,19 +1,21 @@
 // The space-channel context model ("SCCTX") after He, Yang, Peng, Mao, Qin and Wang, "ELIC: efficient learned image
 // compression with unevenly grouped space-channel contextual adaptive coding" (CVPR 2022) on gfx950: the latent's
-// channels are cut into groups, the checkerboard of checkerboard.hip runs inside every group, and a group sees all
-// earlier groups through a full 5x5 window.  ONE launch per (group, pass) computes, for all positions of the pass, the
-// masked correlation, the group's pointwise entropy-parameter network and the quantisation (scctx_params_kernel);
-// scctx_place_kernel is the decoder's store of a decoded (group, pass).  include/tfc_hip.h states the definition.
+// channels are cut into groups, the checkerboard of He, Zheng, Sun, Wang and Qin (CVPR 2021) runs inside every group,
+// and a group sees all earlier groups through a full 5x5 window.  ONE launch per (group, pass) computes, for all
+// positions of the pass, the masked correlation, the group's pointwise entropy-parameter network and the quantisation
+// (scctx_params_kernel); scctx_place_kernel is the decoder's store of a decoded (group, pass).  include/tfc_hip.h
+// states the definition.  The checkerboard model itself is the one-group case, c_g = 0 and M_g = M:
+// tfc_checkerboard_params and tfc_checkerboard_place below run these kernels.
 //
 // The reference tree holds no program text for this model: the definition, the stream format and the layer shapes are
 // this project's own, and parity with anyone's checkpoints is unpinned.
 //
-// The plan is checkerboard.hip's (ckb_engine.h): a workgroup of CKB_THREADS threads owns CKB_TILE = 32 consecutive
+// The plan is the one at the head of ckb_engine.h: a workgroup of CKB_THREADS threads owns CKB_TILE = 32 consecutive
 // compact positions of one image, the four layers run on v_mfma_f32_32x32x2_f32 with the activations k-major in LDS
-// and the weights loaded straight to registers a group of k-steps ahead.  New here: the staged source of the
-// correlation is a channel range of the full y_hat (row stride M; the earlier groups [0, c_g), then the own group
-// [c_g, c_g + M_g)), there are two tap lists (all 25 taps over the earlier groups, the 12 checkerboard taps over the
-// own group) and the context chain has up to two segments, the first of which exists in pass 0 as well when g > 0.
+// and the weights loaded straight to registers a group of k-steps ahead.  The staged source of the correlation is a
+// channel range of the full y_hat (row stride M; the earlier groups [0, c_g), then the own group [c_g, c_g + M_g)),
+// there are two tap lists (all 25 taps over the earlier groups, the 12 checkerboard taps over the own group) and the
+// context chain has up to two segments, the first of which exists in pass 0 as well when g > 0.
 //
 // Every output element stays one chain: its bias, then one fmaf per input row in ascending k: the earlier-group taps
 // (row-major, channels ascending), the own-group taps, for the first layer the 2 M_g context rows and then the P
@@ -131,15 +133,12 @@ __global__ void __launch_bounds__(256) scctx_place_kernel(const ScxPlace a) {
   }
 }
 
-}  // namespace
-}  // namespace tfc
-
-extern "C" int tfc_scctx_params(int pass, const float* y, float* y_hat, const float* psi, const float* packed,
-                                int64_t packed_floats, int64_t batch, int64_t hl, int64_t wl, int m, int cg, int mg,
-                                int p, int h1, int h2, int num_scales, float* mu, float* index_float, int32_t* idx,
-                                int32_t* sym, void* stream) {
-  using namespace tfc;
-  const char* name = "tfc_scctx_params";
+// tfc_scctx_params, and tfc_checkerboard_params with c_g = 0 and M_g = M: errors go by the `name` that was called,
+// profiles by its `label`.
+int params_entry(const char* name, const char* label, int pass, const float* y, float* y_hat, const float* psi,
+                 const float* packed, int64_t packed_floats, int64_t batch, int64_t hl, int64_t wl, int m, int cg, int mg,
+                 int p, int h1, int h2, int num_scales, float* mu, float* index_float, int32_t* idx, int32_t* sym,
+                 void* stream) {
   ScxArgs a = {};
   const char* e = scctx_layout(m, cg, mg, p, h1, h2, &a.S);
   if (!e) e = scctx_check(pass, batch, hl, wl, num_scales, packed_floats, a.S);
@@ -166,7 +165,7 @@ extern "C" int tfc_scctx_params(int pass, const float* y, float* y_hat, const fl
   a.idx = idx;
   a.sym = sym;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  KernelTimer timer("scctx_params", st);
+  KernelTimer timer(label, st);
   const dim3 grid(static_cast<unsigned>(a.tiles * batch));
   if (pass == 0)
     hipLaunchKernelGGL(scctx_params_kernel<0>, grid, dim3(CKB_THREADS), 0, st, a);
@@ -176,10 +175,9 @@ extern "C" int tfc_scctx_params(int pass, const float* y, float* y_hat, const fl
   return 0;
 }
 
-extern "C" int tfc_scctx_place(int pass, const float* sym, const float* mu, float* y_hat, int64_t batch, int64_t hl,
-                               int64_t wl, int m, int cg, int mg, void* stream) {
-  using namespace tfc;
-  const char* name = "tfc_scctx_place";
+// tfc_scctx_place, and tfc_checkerboard_place with c_g = 0 and M_g = M.
+int place_entry(const char* name, const char* label, int pass, const float* sym, const float* mu, float* y_hat,
+                int64_t batch, int64_t hl, int64_t wl, int m, int cg, int mg, void* stream) {
   if (pass != 0 && pass != 1) return fail("%s: pass must be 0 or 1, got %d", name, pass);
   if (m < 1 || m > CTX_MAX_DIM) return fail("%s: M must be in [1, 65536], got %d", name, m);
   if (cg < 0 || mg < 1 || cg > m - mg)
@@ -205,10 +203,42 @@ extern "C" int tfc_scctx_place(int pass, const float* sym, const float* mu, floa
   a.mu = mu;
   a.y_hat = y_hat;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  KernelTimer timer("scctx_place", st);
+  KernelTimer timer(label, st);
   const int64_t blocks = (a.total + 255) / 256;
   hipLaunchKernelGGL(scctx_place_kernel, dim3(static_cast<unsigned>(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st,
                      a);
   TFC_HIP(hipGetLastError());
   return 0;
 }
+
+}  // namespace
+}  // namespace tfc
+
+extern "C" int tfc_scctx_params(int pass, const float* y, float* y_hat, const float* psi, const float* packed,
+                                int64_t packed_floats, int64_t batch, int64_t hl, int64_t wl, int m, int cg, int mg,
+                                int p, int h1, int h2, int num_scales, float* mu, float* index_float, int32_t* idx,
+                                int32_t* sym, void* stream) {
+  return tfc::params_entry("tfc_scctx_params", "scctx_params", pass, y, y_hat, psi, packed, packed_floats, batch, hl, wl,
+                           m, cg, mg, p, h1, h2, num_scales, mu, index_float, idx, sym, stream);
+}
+
+extern "C" int tfc_scctx_place(int pass, const float* sym, const float* mu, float* y_hat, int64_t batch, int64_t hl,
+                               int64_t wl, int m, int cg, int mg, void* stream) {
+  return tfc::place_entry("tfc_scctx_place", "scctx_place", pass, sym, mu, y_hat, batch, hl, wl, m, cg, mg, stream);
+}
+
+// The checkerboard model: one group that is the whole latent.
+extern "C" int tfc_checkerboard_params(int pass, const float* y, float* y_hat, const float* psi, const float* packed,
+                                       int64_t packed_floats, int64_t batch, int64_t hl, int64_t wl, int m, int p,
+                                       int h1, int h2, int num_scales, float* mu, float* index_float, int32_t* idx,
+                                       int32_t* sym, void* stream) {
+  return tfc::params_entry("tfc_checkerboard_params", "checkerboard_params", pass, y, y_hat, psi, packed, packed_floats,
+                           batch, hl, wl, m, 0, m, p, h1, h2, num_scales, mu, index_float, idx, sym, stream);
+}
+
+extern "C" int tfc_checkerboard_place(int pass, const float* sym, const float* mu, float* y_hat, int64_t batch,
+                                      int64_t hl, int64_t wl, int m, void* stream) {
+  return tfc::place_entry("tfc_checkerboard_place", "checkerboard_place", pass, sym, mu, y_hat, batch, hl, wl, m, 0, m,
+                          stream);
+}
+

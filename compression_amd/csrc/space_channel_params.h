@@ -14,7 +14,8 @@
 //                                   is element k, (di, dj) = (k / 5 - 2, k % 5 - 2); cgp = c_g padded to CTX_KPAD with
 //                                   zero rows; absent (0 floats) for c_g = 0
 //
-// so the buffer of a single group (c_g = 0) is the checkerboard model's buffer, float for float.
+// so the buffer of a single group (c_g = 0) is the checkerboard model's buffer, float for float: tfc_checkerboard_params
+// is tfc_scctx_params with c_g = 0 and M_g = M (space_channel.hip).
 #pragma once
 #include "context_params.h"
 
@@ -31,8 +32,12 @@ struct ScctxLayout {
 
 // Fills `S`; returns null, or the text of what is wrong with the sizes.
 inline const char* scctx_layout(int64_t m, int64_t cg, int64_t mg, int64_t p, int64_t h1, int64_t h2, ScctxLayout* S) {
-  if (m < 1 || m > CTX_MAX_DIM) return "M must be in [1, 65536]";
-  if (cg < 0 || mg < 1 || cg > m - mg) return "the group must lie inside the latent: c_g >= 0, M_g >= 1, c_g + M_g <= M";
+  // a group that is the whole latent (the checkerboard model) has no bounds beyond ctx_layout's on M_g = M, and gets
+  // them in ctx_layout's words
+  if (cg != 0 || mg != m) {
+    if (m < 1 || m > CTX_MAX_DIM) return "M must be in [1, 65536]";
+    if (cg < 0 || mg < 1 || cg > m - mg) return "the group must lie inside the latent: c_g >= 0, M_g >= 1, c_g + M_g <= M";
+  }
   if (const char* e = ctx_layout(mg, p, h1, h2, &S->L)) return e;
   S->m = static_cast<int>(m);
   S->cg = static_cast<int>(cg);

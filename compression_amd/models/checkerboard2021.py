@@ -16,7 +16,6 @@ in one launch per pass (`checkerboard_scan` / `checkerboard_decode`), and every 
     python -m compression_amd.models.checkerboard2021 --model_path m.pt decompress out.tfci rec.png"""
 from __future__ import annotations
 
-import numpy as np
 import torch
 
 from .. import layers
@@ -45,10 +44,8 @@ class Checkerboard2021Model(HyperpriorContextModel):
         return checkerboard_ops.checkerboard_scan(y, psi, params)
 
     def _write_strings(self, y, scan):
-        residual = checkerboard_ops.checkerboard_split(y - scan.mu)
-        index = checkerboard_ops.checkerboard_split(scan.index_float)
-        per_pass = [np.asarray(self.em_y.compress(r, i), dtype=object).reshape(-1) for r, i in zip(residual, index)]
-        return np.stack(per_pass, axis=1).reshape(-1)                # [B, 2] -> pass 0, pass 1 of image 0, of image 1...
+        # [B, 2] -> pass 0, pass 1 of image 0, of image 1...
+        return checkerboard_ops.checkerboard_encode(y, scan, self.em_y).reshape(-1)
 
     def _read_strings(self, y_strings, psi, batch, y_shape):
         if y_strings.shape[0] != 2 * batch:

@@ -1,5 +1,7 @@
 """The checkerboard context model of He, Zheng, Sun, Wang and Qin, "Checkerboard context model for efficient learned
-image compression" (CVPR 2021) as two passes that are parallel over positions (csrc/checkerboard.hip).
+image compression" (CVPR 2021) as two passes that are parallel over positions.  It runs as the one-group case of the
+space-channel model's kernels (csrc/space_channel.hip; c_g = 0, M_g = M, one stream per pass), and the launch sites and
+the scan, encode and decode loops of both models are the ones in this file.
 
 The reference tree holds no program text for this model: the definition, the stream format and the layer shapes are
 this project's own, and parity with anyone's checkpoints is unpinned.
@@ -19,9 +21,10 @@ and N_1 = floor(Hl Wl / 2); the slot of (i, j) is (i Wl + j) >> 1 when Wl is odd
 even.  Per image there are two code streams, pass 0 then pass 1: what `LocationScaleIndexedEntropyModel(...,
 coding_rank=2).compress(y - mu, index)` writes for the compact tensor of the pass.
 
-`checkerboard_scan` is the encoder side and the evaluation (two launches), `checkerboard_decode` the decoder side
-(parameters of pass 0, decompress, place, parameters of pass 1, decompress, place), `checkerboard_scan_reference` and
-`checkerboard_parameters_reference` the definition as tensor ops for any float dtype and for CPU tensors."""
+`checkerboard_scan` is the encoder side and the evaluation (two launches), `checkerboard_encode` writes the two strings
+of a scan, `checkerboard_decode` is the decoder side (parameters of pass 0, decompress, place, parameters of pass 1,
+decompress, place), `checkerboard_scan_reference` and `checkerboard_parameters_reference` the definition as tensor ops
+for any float dtype and for CPU tensors."""
 from __future__ import annotations
 
 import collections
@@ -36,7 +39,7 @@ from .context_ops import ContextParams, _check_inputs, _index_prepare, _network,
 __all__ = ["CHECKER_TAPS", "CHECKERBOARD_CONSTANTS", "CheckerboardParams", "CheckerboardScan", "anchor_mask",
            "checkerboard_mask", "checkerboard_split", "checkerboard_merge", "checkerboard_parameters",
            "checkerboard_parameters_reference", "checkerboard_place", "checkerboard_scan", "checkerboard_scan_reference",
-           "checkerboard_decode", "pass_positions"]
+           "checkerboard_decode", "checkerboard_encode", "pass_positions"]
 
 CheckerboardScan = collections.namedtuple("CheckerboardScan", ["sym", "idx", "mu", "y_hat", "index_float"])
 
@@ -143,78 +146,163 @@ def _on_kernel(t):
     return t.is_cuda and t.dtype == torch.float32
 
 
-def _launch_params(pass_, y, y_hat, psi, params):
-    """One tfc_checkerboard_params call -> (mu, index_float, idx, sym or None), compact."""
-    b, hl, wl, _ = psi.shape
+# ---- streams: consecutive compact slots of one pass (ops/scctx_ops.py; the checkerboard model has one per pass) -------
+
+def _check_stream_positions(stream_positions):
+    if int(stream_positions) != stream_positions or int(stream_positions) < 1:
+        raise ValueError(f"stream_positions must be an integer >= 1, got {stream_positions!r}")
+    return int(stream_positions)
+
+
+def stream_split(t, stream_positions):
+    """A compact tensor [B, N, C] -> (full [B, S_full, stream_positions, C] or None, last [B, 1, r, C] or None): the
+    streams of stream_positions slots and the shorter last one."""
+    sp = _check_stream_positions(stream_positions)
+    if t.dim() != 3:
+        raise ValueError(f"t must be [B, N, C], received shape {tuple(t.shape)}")
+    b, n, c = t.shape
+    s_full = n // sp
+    full = t[:, :s_full * sp].reshape(b, s_full, sp, c) if s_full else None
+    last = t[:, s_full * sp:].reshape(b, 1, n - s_full * sp, c) if n > s_full * sp else None
+    return full, last
+
+
+def stream_merge(full, last):
+    """The inverse of `stream_split` -> [B, N, C]."""
+    parts = [v.reshape(v.shape[0], -1, v.shape[3]) for v in (full, last) if v is not None]
+    if not parts:
+        raise ValueError("stream_merge needs at least one part")
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+
+
+# ---- the kernels: both models run csrc/space_channel.hip, the checkerboard model as its one-group case ----------------
+# `steps` holds, per channel group in coding order, (own, packed, c_g): the group's CheckerboardParams, its packed buffer
+# on the device and its first channel; [(params, packed, 0)], one group that is the whole latent, for this model.
+
+def _launch_params(pass_, y, y_hat, psi, own, packed, c_g):
+    """One tfc_scctx_params call for the M_g channels from c_g of `y_hat` -> (mu, index_float, idx, sym or None),
+    compact [B, N_pass, M_g]."""
+    (b, hl, wl, _), m = psi.shape, y_hat.shape[3]
     n = pass_positions(hl, wl, pass_)
-    packed = params.packed(psi.device)
-    mu = torch.empty(b, n, params.m, dtype=torch.float32, device=psi.device)
+    mu = torch.empty(b, n, own.m, dtype=torch.float32, device=psi.device)
     index_float = torch.empty_like(mu)
     idx = torch.empty(mu.shape, dtype=torch.int32, device=psi.device)
     sym = torch.empty_like(idx) if y is not None else None
-    _lib.check(_lib.lib().tfc_checkerboard_params(
+    _lib.check(_lib.lib().tfc_scctx_params(
         pass_, None if y is None else y.data_ptr(), y_hat.data_ptr(), psi.data_ptr(), packed.data_ptr(), packed.numel(),
-        b, hl, wl, params.m, params.p, params.h1, params.h2, params.num_scales, mu.data_ptr(), index_float.data_ptr(),
+        b, hl, wl, m, c_g, own.m, own.p, own.h1, own.h2, own.num_scales, mu.data_ptr(), index_float.data_ptr(),
         idx.data_ptr(), None if sym is None else sym.data_ptr(), _lib.stream_ptr()))
     return mu, index_float, idx, sym
 
 
+def _scan_steps(y, psi, steps):
+    """Two launches per group -> (sym, idx, mu, y_hat, index_float) in the full layout."""
+    hl, wl = y.shape[1:3]
+    y_hat = torch.zeros_like(y)
+    per_group = []
+    for own, packed, c_g in steps:
+        a, b = (_launch_params(pass_, y, y_hat, psi, own, packed, c_g) for pass_ in (0, 1))
+        per_group.append([checkerboard_merge(u, v, hl, wl) for u, v in zip(a, b)])
+    mu, index_float, idx, sym = per_group[0] if len(per_group) == 1 else (
+        torch.cat([group[k] for group in per_group], dim=-1) for k in range(4))
+    return sym, idx, mu, y_hat, index_float
+
+
+def _encode_steps(residual, index, spans, stream_positions, entropy_model):
+    """The strings of residual and index [B, Hl, Wl, M], object array [B, T] in the order group, pass, stream: per
+    (c_g, M_g) of `spans` and pass, the full streams go through one `compress` call as [B, S_full, stream_positions,
+    M_g], a shorter last stream through a second."""
+    columns = []
+    for c, mg in spans:
+        r_g = checkerboard_split(residual[..., c:c + mg].contiguous())
+        i_g = checkerboard_split(index[..., c:c + mg].contiguous())
+        for pass_ in (0, 1):
+            for r, i in zip(stream_split(r_g[pass_], stream_positions), stream_split(i_g[pass_], stream_positions)):
+                if r is not None:
+                    strings = entropy_model.compress(r.contiguous(), i.contiguous())
+                    columns.append(np.asarray(strings, dtype=object).reshape(residual.shape[0], -1))
+    return np.concatenate(columns, axis=1)
+
+
+def _decode_steps(strings, psi, steps, m, stream_positions, entropy_model):
+    """strings [B, T] -> y_hat [B, Hl, Wl, m].  Per group and pass: the parameters (one launch), one `decompress` call
+    for the full streams and one for a shorter last stream, the store."""
+    b, hl, wl, _ = psi.shape
+    y_hat = torch.zeros(b, hl, wl, m, dtype=torch.float32, device=psi.device)
+    at = 0
+    for own, packed, c_g in steps:
+        for pass_ in (0, 1):
+            if pass_positions(hl, wl, pass_) == 0:
+                continue
+            mu, index_float, _, _ = _launch_params(pass_, None, y_hat, psi, own, packed, c_g)
+            parts = []
+            for part in stream_split(index_float, stream_positions):
+                if part is not None:
+                    s = part.shape[1]
+                    part = entropy_model.decompress(strings[:, at:at + s], part.contiguous())
+                    at += s
+                parts.append(part)
+            checkerboard_place(stream_merge(*parts), mu, y_hat, pass_, c_g)
+    return y_hat
+
+
 def checkerboard_parameters(y_hat, psi, params, pass_):
     """(mu, index_float) of one pass in compact order, [B, N_pass, M], given `y_hat` [B, Hl, Wl, M] (read at the anchors
-    by pass 1, not at all by pass 0).  float32 device tensors run tfc_checkerboard_params; CPU tensors and other float
-    dtypes take `checkerboard_parameters_reference`."""
+    by pass 1, not at all by pass 0).  float32 device tensors run tfc_checkerboard_params' kernel (tfc_scctx_params with
+    one group); CPU tensors and other float dtypes take `checkerboard_parameters_reference`."""
     _check(y_hat, psi, params, "y_hat")
     pass_ = _check_pass(pass_)
     if not _on_kernel(y_hat):
         mu, index_float = checkerboard_parameters_reference(y_hat, psi, params)
         return checkerboard_split(mu)[pass_], checkerboard_split(index_float)[pass_]
-    mu, index_float, _, _ = _launch_params(pass_, None, y_hat.detach().contiguous(), psi.detach().contiguous(), params)
-    return mu, index_float
+    return _launch_params(pass_, None, y_hat.detach().contiguous(), psi.detach().contiguous(), params,
+                          params.packed(psi.device), 0)[:2]
 
 
-def checkerboard_place(sym, mu, y_hat, pass_):
-    """y_hat[positions of the pass] = float32(sym) + mu, in place, from compact `sym` and `mu` [B, N_pass, M]."""
+def checkerboard_place(sym, mu, y_hat, pass_, c_g=0):
+    """y_hat[positions of the pass, c_g : c_g + M_g] = float32(sym) + mu, in place, from compact `sym` and `mu`
+    [B, N_pass, M_g]: the whole depth M of y_hat for the checkerboard model, a channel group for ops/scctx_ops.py."""
     pass_ = _check_pass(pass_)
     b, hl, wl, m = y_hat.shape
-    if tuple(sym.shape) != (b, pass_positions(hl, wl, pass_), m) or tuple(mu.shape) != tuple(sym.shape):
-        raise ValueError(f"sym and mu must be [{b}, {pass_positions(hl, wl, pass_)}, {m}], received "
-                         f"{tuple(sym.shape)} and {tuple(mu.shape)}")
+    n, c_g = pass_positions(hl, wl, pass_), int(c_g)
+    if sym.dim() != 3 or tuple(sym.shape[:2]) != (b, n) or tuple(mu.shape) != tuple(sym.shape):
+        raise ValueError(f"sym and mu must be [{b}, {n}, M_g], received {tuple(sym.shape)} and {tuple(mu.shape)}")
+    mg = int(sym.shape[2])
+    if c_g < 0 or mg < 1 or c_g + mg > m:
+        raise ValueError(f"the group must lie inside the latent: c_g {c_g}, M_g {mg}, M {m}")
     if not (_on_kernel(y_hat) and y_hat.is_contiguous()):
         anchors = anchor_mask(hl, wl, y_hat.device).reshape(-1)
-        y_hat.view(b, hl * wl, m)[:, anchors if pass_ == 0 else ~anchors] = sym.to(y_hat.dtype) + mu.to(y_hat.dtype)
+        y_hat.view(b, hl * wl, m)[:, anchors if pass_ == 0 else ~anchors, c_g:c_g + mg] = (
+            sym.to(y_hat.dtype) + mu.to(y_hat.dtype))
         return y_hat
     sym, mu = sym.to(torch.float32).contiguous(), mu.contiguous()
-    _lib.check(_lib.lib().tfc_checkerboard_place(pass_, sym.data_ptr(), mu.data_ptr(), y_hat.data_ptr(), b, hl, wl, m,
-                                                 _lib.stream_ptr()))
+    _lib.check(_lib.lib().tfc_scctx_place(pass_, sym.data_ptr(), mu.data_ptr(), y_hat.data_ptr(), b, hl, wl, m, c_g, mg,
+                                          _lib.stream_ptr()))
     return y_hat
-
-
-def _scan_compact(y, psi, params):
-    """The two launches -> (y_hat full, [(mu, index_float, idx, sym) of pass 0, of pass 1])."""
-    y_hat = torch.zeros_like(y)
-    passes = [_launch_params(pass_, y, y_hat, psi, params) for pass_ in (0, 1)]
-    return y_hat, passes
 
 
 def checkerboard_scan(y, psi, params):
     """y [B, Hl, Wl, M], psi [B, Hl, Wl, P] -> CheckerboardScan(sym int32, idx int32, mu, y_hat, index_float) in the
-    full layout: float32 device tensors run tfc_checkerboard_params twice; CPU tensors and other float dtypes take
+    full layout: float32 device tensors run the kernel twice; CPU tensors and other float dtypes take
     `checkerboard_scan_reference`."""
     _check(y, psi, params)
     if not _on_kernel(y):
         return checkerboard_scan_reference(y, psi, params)
     y, psi = y.detach().contiguous(), psi.detach().contiguous()
-    hl, wl = y.shape[1:3]
-    y_hat, (a, b) = _scan_compact(y, psi, params)
-    mu, index_float, idx, sym = (checkerboard_merge(u, v, hl, wl) for u, v in zip(a, b))
-    return CheckerboardScan(sym, idx, mu, y_hat, index_float)
+    return CheckerboardScan(*_scan_steps(y, psi, [(params, params.packed(psi.device), 0)]))
+
+
+def checkerboard_encode(y, scan, entropy_model):
+    """The strings of a scan, object array [B, 2]: pass 0 and pass 1 of every image, each what
+    `entropy_model.compress(y - mu, index_float)` writes for the compact tensors of the pass."""
+    hl, wl, m = y.shape[1:]
+    return _encode_steps(y - scan.mu, scan.index_float, [(0, m)], max(1, pass_positions(hl, wl, 0)), entropy_model)
 
 
 def checkerboard_decode(strings, psi, params, entropy_model):
-    """The strings [B, 2] (pass 0 and pass 1 of every image: what `entropy_model.compress(y - mu, index_float)` writes
-    for the compact tensors of a pass), psi [B, Hl, Wl, P] float32 on the device and the
-    `LocationScaleIndexedEntropyModel` (coding_rank 2) that wrote them -> y_hat [B, Hl, Wl, M].  A latent of one
-    position has no second pass: its second string is not read."""
+    """The strings [B, 2] (pass 0 and pass 1 of every image: `checkerboard_encode`), psi [B, Hl, Wl, P] float32 on the
+    device and the `LocationScaleIndexedEntropyModel` (coding_rank 2) that wrote them -> y_hat [B, Hl, Wl, M].  A latent
+    of one position has no second pass: its second string is not read."""
     _check(None, psi, params)
     if not _on_kernel(psi):
         raise ValueError("checkerboard_decode needs float32 psi on the device")
@@ -224,11 +312,7 @@ def checkerboard_decode(strings, psi, params, entropy_model):
     if strings.shape != (b, 2):
         raise ValueError(f"strings must have shape [{b}, 2] (pass 0 and pass 1 of every image), received "
                          f"{list(strings.shape)}")
-    y_hat = torch.zeros(b, hl, wl, params.m, dtype=torch.float32, device=psi.device)
-    for pass_ in (0, 1):
-        if pass_positions(hl, wl, pass_) == 0:
-            continue
-        mu, index_float, _, _ = _launch_params(pass_, None, y_hat, psi, params)
-        sym = entropy_model.decompress(strings[:, pass_], index_float)
-        checkerboard_place(sym, mu, y_hat, pass_)
-    return y_hat
+    return _decode_steps(strings, psi, [(params, params.packed(psi.device), 0)], params.m,
+                         max(1, pass_positions(hl, wl, 0)), entropy_model)          # a whole pass is one stream
+
+

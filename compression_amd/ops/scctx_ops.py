@@ -41,9 +41,11 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .checkerboard_ops import (CHECKER_TAPS, CHECKERBOARD_CONSTANTS, CheckerboardParams, anchor_mask, checkerboard_merge,
-                               checkerboard_split, pass_positions, _check_pass, _on_kernel)
-from .context_ops import CONTEXT_CONSTANTS, _index_prepare, _layout, _network, _pad, tap_sum
+from .checkerboard_ops import (CHECKER_TAPS, CHECKERBOARD_CONSTANTS, CheckerboardParams, anchor_mask, checkerboard_place,
+                               checkerboard_split, pass_positions, stream_merge, stream_split, _check_pass,
+                               _check_stream_positions, _decode_steps, _encode_steps, _launch_params, _on_kernel,
+                               _scan_steps)
+from .context_ops import CONTEXT_CONSTANTS, _check_inputs, _index_prepare, _layout, _network, _pad, tap_sum
 
 __all__ = ["ALL_TAPS", "SCCTX_CONSTANTS", "SpaceChannelParams", "SpaceChannelScan", "default_groups", "hidden_widths",
            "scctx_decode", "scctx_encode", "scctx_parameters", "scctx_parameters_reference", "scctx_place", "scctx_scan",
@@ -92,12 +94,6 @@ def _check_groups(groups, m=None):
     return groups
 
 
-def _check_stream_positions(stream_positions):
-    if int(stream_positions) != stream_positions or int(stream_positions) < 1:
-        raise ValueError(f"stream_positions must be an integer >= 1, got {stream_positions!r}")
-    return int(stream_positions)
-
-
 class SpaceChannelParams:
     """The weights of the space-channel context model, checked and packed once per group.
 
@@ -105,6 +101,8 @@ class SpaceChannelParams:
     kernel_bias [2 M_g], w1 [2 M_g + P, H1], b1, w2 [H1, H2], b2, w3 [H2, 2 M_g], b3): HWIO kernels, rows are inputs.
     The checkerboard mask is applied to kernel_sp here, whatever its other taps hold; kernel_ch is used in full.  Any
     widths are taken; `hidden_widths` is the model's rule, not a check.  Holds detached copies."""
+
+    TAPS = ALL_TAPS         # over the earlier groups; CHECKER_TAPS over the own group (`own`)
 
     def __init__(self, groups, num_scales, stream_positions=SCCTX_CONSTANTS["SCCTX_STREAM"]):
         groups = list(groups)
@@ -200,45 +198,10 @@ def stream_counts(hl, wl, stream_positions):
     return tuple(-(-pass_positions(hl, wl, p) // sp) for p in (0, 1))
 
 
-def stream_split(t, stream_positions):
-    """A compact tensor [B, N, C] -> (full [B, S_full, stream_positions, C] or None, last [B, 1, r, C] or None): the
-    streams of stream_positions slots and the shorter last one."""
-    sp = _check_stream_positions(stream_positions)
-    if t.dim() != 3:
-        raise ValueError(f"t must be [B, N, C], received shape {tuple(t.shape)}")
-    b, n, c = t.shape
-    s_full = n // sp
-    full = t[:, :s_full * sp].reshape(b, s_full, sp, c) if s_full else None
-    last = t[:, s_full * sp:].reshape(b, 1, n - s_full * sp, c) if n > s_full * sp else None
-    return full, last
-
-
-def stream_merge(full, last):
-    """The inverse of `stream_split` -> [B, N, C]."""
-    parts = [v.reshape(v.shape[0], -1, v.shape[3]) for v in (full, last) if v is not None]
-    if not parts:
-        raise ValueError("stream_merge needs at least one part")
-    return torch.cat(parts, dim=1)
-
-
 # ---- the definition as tensor ops ---------------------------------------------------------------------------------------
 
 def _check(y, psi, params, what="y"):
-    if not isinstance(params, SpaceChannelParams):
-        raise TypeError("params must be a SpaceChannelParams")
-    if psi.dim() != 4 or psi.shape[-1] != params.p:
-        raise ValueError(f"psi must be [B, Hl, Wl, {params.p}], received shape {tuple(psi.shape)}")
-    if y is not None:
-        if y.dim() != 4 or y.shape[-1] != params.m:
-            raise ValueError(f"{what} must be [B, Hl, Wl, {params.m}], received shape {tuple(y.shape)}")
-        if tuple(y.shape[:3]) != tuple(psi.shape[:3]):
-            raise ValueError(f"{what} and psi must share [B, Hl, Wl], received {tuple(y.shape)} and {tuple(psi.shape)}")
-        if y.device != psi.device or y.dtype != psi.dtype:
-            raise ValueError(f"{what} and psi must share dtype and device")
-    if psi.shape[1] < 1 or psi.shape[2] < 1:
-        raise ValueError(f"Hl and Wl must be at least 1, received shape {tuple(psi.shape)}")
-    if not psi.dtype.is_floating_point:
-        raise TypeError("y and psi must be floating point")
+    _check_inputs(y, psi, params, what, kind=SpaceChannelParams)
 
 
 def _check_group(g, params):
@@ -291,28 +254,19 @@ def scctx_scan_reference(y, psi, params):
                             y_hat, index_float)
 
 
-# ---- the kernels ------------------------------------------------------------------------------------------------------
+# ---- the kernels: the launch sites and the loops are checkerboard_ops', which runs as the one-group case ---------------
 
-def _launch_params(g, pass_, y, y_hat, psi, params):
-    """One tfc_scctx_params call -> (mu, index_float, idx, sym or None), compact [B, N_pass, M_g]."""
-    if not params.own[g].fits_kernel():
+def _steps(params, device, gs=None):
+    """The step list of the groups `gs` (all of them when None), each checked against the kernel's LDS."""
+    steps = []
+    for g in range(len(params)) if gs is None else gs:
         own, c = params.own[g], CHECKERBOARD_CONSTANTS
-        raise ValueError(f"group {g} (M_g {own.m}, P {own.p}, H1 {own.h1}, H2 {own.h2}) does not fit the kernel: the "
-                         f"activations of one tile of {c['CKB_TILE']} positions need more than {4 * c['CKB_LDS_FLOATS']} "
-                         "bytes of LDS")
-    b, hl, wl, _ = psi.shape
-    n = pass_positions(hl, wl, pass_)
-    own = params.own[g]
-    packed = params.packed(g, psi.device)
-    mu = torch.empty(b, n, own.m, dtype=torch.float32, device=psi.device)
-    index_float = torch.empty_like(mu)
-    idx = torch.empty(mu.shape, dtype=torch.int32, device=psi.device)
-    sym = torch.empty_like(idx) if y is not None else None
-    _lib.check(_lib.lib().tfc_scctx_params(
-        pass_, None if y is None else y.data_ptr(), y_hat.data_ptr(), psi.data_ptr(), packed.data_ptr(), packed.numel(),
-        b, hl, wl, params.m, params.offsets[g], own.m, own.p, own.h1, own.h2, params.num_scales, mu.data_ptr(),
-        index_float.data_ptr(), idx.data_ptr(), None if sym is None else sym.data_ptr(), _lib.stream_ptr()))
-    return mu, index_float, idx, sym
+        if not own.fits_kernel():
+            raise ValueError(f"group {g} (M_g {own.m}, P {own.p}, H1 {own.h1}, H2 {own.h2}) does not fit the kernel: the "
+                             f"activations of one tile of {c['CKB_TILE']} positions need more than "
+                             f"{4 * c['CKB_LDS_FLOATS']} bytes of LDS")
+        steps.append((own, params.packed(g, device), params.offsets[g]))
+    return steps
 
 
 def scctx_parameters(y_hat, psi, params, g, pass_):
@@ -324,30 +278,14 @@ def scctx_parameters(y_hat, psi, params, g, pass_):
     if not _on_kernel(y_hat):
         mu, index_float = _group_reference(y_hat, psi, params, g)
         return checkerboard_split(mu)[pass_], checkerboard_split(index_float)[pass_]
-    mu, index_float, _, _ = _launch_params(g, pass_, None, y_hat.detach().contiguous(), psi.detach().contiguous(), params)
-    return mu, index_float
+    ((own, packed, c_g),) = _steps(params, psi.device, [g])
+    return _launch_params(pass_, None, y_hat.detach().contiguous(), psi.detach().contiguous(), own, packed, c_g)[:2]
 
 
 def scctx_place(sym, mu, y_hat, c_g, pass_):
     """y_hat[positions of the pass, c_g : c_g + M_g] = float32(sym) + mu, in place, from compact `sym` and `mu`
     [B, N_pass, M_g]."""
-    pass_ = _check_pass(pass_)
-    b, hl, wl, m = y_hat.shape
-    n, c_g = pass_positions(hl, wl, pass_), int(c_g)
-    if sym.dim() != 3 or tuple(sym.shape[:2]) != (b, n) or tuple(mu.shape) != tuple(sym.shape):
-        raise ValueError(f"sym and mu must be [{b}, {n}, M_g], received {tuple(sym.shape)} and {tuple(mu.shape)}")
-    mg = int(sym.shape[2])
-    if c_g < 0 or mg < 1 or c_g + mg > m:
-        raise ValueError(f"the group must lie inside the latent: c_g {c_g}, M_g {mg}, M {m}")
-    if not (_on_kernel(y_hat) and y_hat.is_contiguous()):
-        anchors = anchor_mask(hl, wl, y_hat.device).reshape(-1)
-        y_hat.view(b, hl * wl, m)[:, anchors if pass_ == 0 else ~anchors, c_g:c_g + mg] = (
-            sym.to(y_hat.dtype) + mu.to(y_hat.dtype))
-        return y_hat
-    sym, mu = sym.to(torch.float32).contiguous(), mu.contiguous()
-    _lib.check(_lib.lib().tfc_scctx_place(pass_, sym.data_ptr(), mu.data_ptr(), y_hat.data_ptr(), b, hl, wl, m, c_g, mg,
-                                          _lib.stream_ptr()))
-    return y_hat
+    return checkerboard_place(sym, mu, y_hat, pass_, c_g)
 
 
 def scctx_scan(y, psi, params):
@@ -358,14 +296,7 @@ def scctx_scan(y, psi, params):
     if not _on_kernel(y):
         return scctx_scan_reference(y, psi, params)
     y, psi = y.detach().contiguous(), psi.detach().contiguous()
-    hl, wl = y.shape[1:3]
-    y_hat = torch.zeros_like(y)
-    per_group = []
-    for g in range(len(params)):
-        a, b = (_launch_params(g, pass_, y, y_hat, psi, params) for pass_ in (0, 1))
-        per_group.append([checkerboard_merge(u, v, hl, wl) for u, v in zip(a, b)])
-    mu, index_float, idx, sym = (torch.cat([group[k] for group in per_group], dim=-1) for k in range(4))
-    return SpaceChannelScan(sym, idx, mu, y_hat, index_float)
+    return SpaceChannelScan(*_scan_steps(y, psi, _steps(params, psi.device)))
 
 
 def scctx_encode(y, scan, params, entropy_model):
@@ -377,20 +308,8 @@ def scctx_encode(y, scan, params, entropy_model):
     if y.dim() != 4 or y.shape[-1] != params.m or tuple(scan.mu.shape) != tuple(y.shape):
         raise ValueError(f"y and the scan must be [B, Hl, Wl, {params.m}], received shapes {tuple(y.shape)} and "
                          f"{tuple(scan.mu.shape)}")
-    residual, index = (y - scan.mu), scan.index_float
-    b = y.shape[0]
-    columns = []
-    for g in range(len(params)):
-        c, mg = params.offsets[g], params.groups[g]
-        r_g = checkerboard_split(residual[..., c:c + mg].contiguous())
-        i_g = checkerboard_split(index[..., c:c + mg].contiguous())
-        for pass_ in (0, 1):
-            for r, i in zip(stream_split(r_g[pass_], params.stream_positions),
-                            stream_split(i_g[pass_], params.stream_positions)):
-                if r is not None:
-                    strings = entropy_model.compress(r.contiguous(), i.contiguous())
-                    columns.append(np.asarray(strings, dtype=object).reshape(b, -1))
-    return np.concatenate(columns, axis=1)
+    return _encode_steps(y - scan.mu, scan.index_float, zip(params.offsets, params.groups), params.stream_positions,
+                         entropy_model)
 
 
 def scctx_decode(strings, psi, params, entropy_model):
@@ -409,20 +328,5 @@ def scctx_decode(strings, psi, params, entropy_model):
         raise ValueError(f"strings must have shape [{b}, {per_image}] ({len(params)} groups x ({counts[0]} + {counts[1]}) "
                          f"streams of {params.stream_positions} positions for every image), received "
                          f"{list(strings.shape)}")
-    y_hat = torch.zeros(b, hl, wl, params.m, dtype=torch.float32, device=psi.device)
-    at = 0
-    for g in range(len(params)):
-        for pass_ in (0, 1):
-            if counts[pass_] == 0:
-                continue
-            mu, index_float, _, _ = _launch_params(g, pass_, None, y_hat, psi, params)
-            parts = []
-            for index in stream_split(index_float, params.stream_positions):
-                if index is None:
-                    parts.append(None)
-                    continue
-                s = index.shape[1]
-                parts.append(entropy_model.decompress(strings[:, at:at + s], index.contiguous()))
-                at += s
-            scctx_place(stream_merge(*parts), mu, y_hat, params.offsets[g], pass_)
-    return y_hat
+    return _decode_steps(strings, psi, _steps(params, psi.device), params.m, params.stream_positions, entropy_model)
+

@@ -1096,7 +1096,10 @@ int tfc_context_decode(const tfc_tables* tables, const uint8_t* blob, const int6
  * hold these taps in row-major order (tap k is element 2 k + 1 of the 5x5 window).
  * Checked on the host before any launch: pass, sizes (as tfc_context_scan, and the activations of 32 positions within
  * 160 KiB of LDS, which the kernel declares in full), Hl, Wl, batch, num_scales, packed_floats, null pointers.
- * batch == 0, or a pass without positions (pass 1 of a 1x1 latent), launches nothing. */
+ * batch == 0, or a pass without positions (pass 1 of a 1x1 latent), launches nothing.
+ * The two entries are tfc_scctx_params and tfc_scctx_place below with one group that is the whole latent, c_g = 0 and
+ * M_g = M: the same kernels, the same checks (an error names the entry that was called and lists c_g and M_g too),
+ * the same packed buffer. */
 
 /* The parameters of one pass for all its positions, ONE launch (a workgroup per 32 positions of an image).  y_hat
  * DEV [batch, Hl, Wl, M] is read at the anchors (pass 1) and, when `y` is given, written at the pass's positions.

@@ -11,7 +11,7 @@ from context_ref import index_prepare, make_case, network  # noqa: F401
 
 CHECKER_TAPS = tuple((di, dj) for di in range(-2, 3) for dj in range(-2, 3) if (di + dj) % 2)
 
-# positions of one workgroup of csrc/checkerboard.hip (CKB_TILE)
+# positions of one workgroup of csrc/space_channel.hip (CKB_TILE)
 KERNEL_TILE = 32
 
 # (B, Hl, Wl, M, H1, H2); P = 2M

@@ -1,4 +1,4 @@
-"""GPU tier of the checkerboard context model (csrc/checkerboard.hip): checkerboard_scan against itself (exact, and
+"""GPU tier of the checkerboard context model (the one-group case of csrc/space_channel.hip): checkerboard_scan against itself (exact, and
 image by image against the batched call), against the float64 definition teacher-forced on its own y_hat, and
 checkerboard_decode against the strings the indexed entropy model writes from the scan's outputs (bit-identical y_hat,
 also for one image taken out of a batched encode).

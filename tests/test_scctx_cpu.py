@@ -203,7 +203,7 @@ def test_fits_kernel_is_the_lds_check_per_group():
     assert not wide.fits_kernel()
     assert [own.fits_kernel() for own in wide.own] == [True, True, True, True, False]
     with pytest.raises(ValueError, match="does not fit the kernel"):
-        scctx_ops._launch_params(4, 0, None, torch.zeros(1, 1, 2, 320), torch.zeros(1, 1, 2, 640), wide)
+        scctx_ops._steps(wide, "cpu", [4])
 
 
 def test_argument_errors_are_text():

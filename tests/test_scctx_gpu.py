@@ -1,8 +1,9 @@
 """GPU tier of the space-channel context model (csrc/space_channel.hip): scctx_scan against itself (exact, step by step
-against the compact entry, image by image against the batched call), the single group against the checkerboard kernel
-(bit for bit, strings included), against the float64 definition teacher-forced on its own y_hat, causality on the
-device, and scctx_decode against the strings the indexed entropy model writes from the scan's outputs (bit-identical
-y_hat, also for one image taken out of a batched encode).
+against the compact entry, image by image against the batched call), the single group against the checkerboard model's
+ops and hand-written two-string format (bit for bit; both run these kernels, and test_context_digests_gpu.py pins them
+to the former checkerboard kernel), the raw checkerboard entries against the raw one-group entries, against the float64
+definition teacher-forced on its own y_hat, causality on the device, and scctx_decode against the strings the indexed
+entropy model writes from the scan's outputs (bit-identical y_hat, also for one image taken out of a batched encode).
 
 The teacher-forced bound.  FLOAT32_DEVIATION_MU / _INDEX are the largest deviations of the float32 torch evaluation of
 `scctx_parameters_reference` from its float64 evaluation, measured on the CPU on these inputs (all SHAPES; y_hat of the
@@ -136,6 +137,53 @@ def test_one_group_is_the_checkerboard_kernel_bit_for_bit(single, entropy_model)
     want_strings = _checker_strings(entropy_model, case["y"], want)
     assert strings.shape == want_strings.shape == (b, 2)
     assert [bytes(s) for s in strings.reshape(-1)] == [bytes(s) for s in want_strings.reshape(-1)]
+
+
+@pytest.mark.parametrize("shape", [(1, 1, 2, 8, 26, 21), (2, 9, 15, 8, 26, 21)], ids=lambda s: "x".join(map(str, s[:4])))
+def test_the_checkerboard_entries_are_the_one_group_entries(shape):
+    """Raw tfc_checkerboard_params / _place against raw tfc_scctx_params / _place with c_g = 0 and M_g = M on the same
+    buffers: both passes, with and without y, every output."""
+    import context_ref
+    from compression_amd import _lib
+    lib = _lib.lib()
+    y, psi, weights = context_ref.make_case(shape, NUM_SCALES)
+    own = checkerboard_ops.CheckerboardParams(*[torch.from_numpy(w) for w in weights], NUM_SCALES)
+    y, psi = torch.from_numpy(y).cuda(), torch.from_numpy(psi).cuda()
+    b, hl, wl, m = y.shape
+    packed = own.packed(y.device)
+    sizes = (own.p, own.h1, own.h2, NUM_SCALES)
+
+    def run(entry, group, pass_, y_in, y_hat):
+        n = checkerboard_ops.pass_positions(hl, wl, pass_)
+        mu, index = torch.zeros(b, n, m, device=y.device), torch.zeros(b, n, m, device=y.device)
+        idx = torch.zeros(b, n, m, dtype=torch.int32, device=y.device)
+        sym = torch.zeros_like(idx)
+        _lib.check(entry(pass_, None if y_in is None else y_in.data_ptr(), y_hat.data_ptr(), psi.data_ptr(),
+                         packed.data_ptr(), packed.numel(), b, hl, wl, m, *group, *sizes, mu.data_ptr(), index.data_ptr(),
+                         idx.data_ptr(), None if y_in is None else sym.data_ptr(), None))
+        return mu, index, idx, sym
+
+    def chain(params_entry, place_entry, group):
+        """The encoder's two passes, then the decoder's: parameters without y and the store, pass after pass."""
+        out, y_hat = [], torch.zeros_like(y)
+        for pass_ in (0, 1):
+            out += run(params_entry, group, pass_, y, y_hat)
+        decoded = torch.zeros_like(y)
+        for pass_ in (0, 1):
+            mu, index, idx, _ = run(params_entry, group, pass_, None, decoded)
+            sym = out[4 * pass_ + 3].to(torch.float32)
+            _lib.check(place_entry(pass_, sym.data_ptr(), mu.data_ptr(), decoded.data_ptr(), b, hl, wl, m, *group, None))
+            out += [mu, index, idx, decoded.clone()]
+        torch.cuda.synchronize()
+        return out + [y_hat]
+
+    checker = chain(lib.tfc_checkerboard_params, lib.tfc_checkerboard_place, ())
+    group = chain(lib.tfc_scctx_params, lib.tfc_scctx_place, (0, m))
+    assert len(checker) == len(group) == 17
+    for k, (a, g) in enumerate(zip(checker, group)):
+        assert torch.equal(a, g), k
+    assert torch.equal(checker[-1], checker[-2])                # the decoder's y_hat is the encoder's
+    assert bool(checker[-1].abs().sum() > 0)
 
 
 def test_scan_matches_the_float64_definition_teacher_forced(case):
