@@ -120,6 +120,9 @@ SIGNATURES = {
                              _int, _int, _int, _int, _int, _int, _int, _vp]),
     "tfc_conv3d_wgrad": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                 _int, _int, _int, _int, _int, _int, _int, _vp]),
+    "tfc_conv3d_plan": (_int, [_int, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int,
+                               C.POINTER(C.c_int32)]),
+    "tfc_conv3d_wgrad_plan": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, C.POINTER(C.c_int32)]),
     "tfc_factorized_bits_forward": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _vp, _int, _int,
                                            _vp, _vp, _vp]),
     "tfc_factorized_bits_backward": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _int, _int, _vp, _vp,

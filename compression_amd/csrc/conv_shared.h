@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <initializer_list>
 #include <type_traits>
 
@@ -44,6 +45,14 @@ __device__ inline float split_plane(float a, int plane) {
   __bf16 p[3];
   split3(a, &p[0], &p[1], &p[2]);
   return static_cast<float>(plane == 0 ? p[0] : plane == 1 ? p[1] : p[2]);
+}
+
+// bytes of input planes per chunk of images, for the rank-2 and the rank-3 float32 path (TFC_CONV_F32_CHUNK_BYTES: the
+// tests run several chunks at a small shape; read per call)
+inline size_t conv_f32_chunk_bytes() {
+  const char* e = std::getenv("TFC_CONV_F32_CHUNK_BYTES");
+  const long long v = e ? std::atoll(e) : 0;
+  return v > 0 ? static_cast<size_t>(v) : size_t{2} << 30;
 }
 
 // One 2-D forward call, as the C ABI entries state it and as a route states a nested one.

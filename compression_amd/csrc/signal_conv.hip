@@ -1955,12 +1955,6 @@ static bool conv_f32_split_enabled() {
   const char* e = std::getenv("TFC_CONV_F32");
   return !(e && std::strcmp(e, "native") == 0);
 }
-// bytes of input planes per chunk of images (TFC_CONV_F32_CHUNK_BYTES: the tests run several chunks at a small shape)
-static size_t conv_f32_chunk_bytes() {
-  const char* e = std::getenv("TFC_CONV_F32_CHUNK_BYTES");
-  const long long v = e ? std::atoll(e) : 0;
-  return v > 0 ? static_cast<size_t>(v) : size_t{2} << 30;
-}
 
 // The planes of the input are 3x its bytes: images go through in chunks of ~2 GB of planes (bmshj2018's first 192 -> 192
 // layer at 128 x 768x512 would need 29 GB at once), each chunk split and convolved before the next — the kernel's six

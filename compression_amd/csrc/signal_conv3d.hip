@@ -1,6 +1,6 @@
 // SignalConv1D / SignalConv3D on the bfloat16 matrix cores: tfc_conv3d_down, tfc_conv3d_up and
-// tfc_conv3d_wgrad.  Activations NDHWC, kernels the layer's float32 DHWIO, one stride per axis; rank 1 is the case
-// d = h = 1, kd = kh = 1.
+// tfc_conv3d_wgrad, and the host-only queries tfc_conv3d_plan / tfc_conv3d_wgrad_plan.  Activations NDHWC, kernels the
+// layer's float32 DHWIO, one stride per axis; rank 1 is the case d = h = 1, kd = kh = 1.
 //
 // Forward: an implicit GEMM per output phase.  A phase is the set of outputs o * OS + PH0 (per axis) that one
 // stride-S correlation with T taps produces:
@@ -322,17 +322,25 @@ struct Phase {
   int A[3], B[3];
 };
 
-int conv3d_bf16(const char* name, const __bf16* x, const float* w, int planes, const float* bias, void* y, bool out_f32,
-                int64_t n, const int64_t in[3], int64_t cin_k, int64_t cin_w, int64_t cout, const int k[3], const int s[3],
-                int activation, int up, hipStream_t st) {
+// What the host chooses for one forward call: the phases, the tile, the column blocks and the LDS stage.  conv3d_bf16
+// launches from it and tfc_conv3d_plan reports it, so the two cannot drift.
+struct FwdPlan {
+  std::vector<Phase> phases;
+  int64_t yd[3];             // the output tensor's extents
+  int TW, TH, NT, nblk, tiles_w, tiles_h;
+  size_t patch_pieces, lds;
+};
+
+int conv3d_plan(const char* name, int up, const int64_t in[3], int64_t cout, const int k[3], const int s[3], FwdPlan* plan) {
   // phases
   int nph = 1;
   for (int a = 0; a < 3; ++a) nph *= up ? s[a] : 1;
-  int64_t yd[3];
+  int64_t* yd = plan->yd;
   for (int a = 0; a < 3; ++a) yd[a] = up ? in[a] * s[a] : ceil_div(in[a], s[a]);
   for (int a = 0; a < 3; ++a)
     if (yd[a] >= (1ll << 31) || in[a] >= (1ll << 31)) return fail("%s: extent too large (%lld)", name, static_cast<long long>(yd[a]));
-  std::vector<Phase> phases(nph);
+  std::vector<Phase>& phases = plan->phases;
+  phases.assign(nph, Phase{});
   for (int p = 0; p < nph; ++p) {
     Phase& f = phases[p];
     int rest = p;
@@ -356,7 +364,6 @@ int conv3d_bf16(const char* name, const __bf16* x, const float* w, int planes, c
   const int ow = phases[0].OD[2];
   int TW = ow > 64 ? 128 : ow > 32 ? 64 : 32;
   int NT = pick_nt(cout);
-  const int cblocks = static_cast<int>(cin_k / 16);
   // LDS: the largest patch of any phase, then the largest weight stage
   auto lds_of = [&](int tw, int nt, size_t* patch_pieces) {
     size_t pp = 0, wp = 0;
@@ -373,11 +380,27 @@ int conv3d_bf16(const char* name, const __bf16* x, const float* w, int planes, c
   // two workgroups per CU where possible: narrower column blocks first, then narrower tiles
   while (NT > 1 && lds_of(TW, NT, nullptr) > kHalfLds) --NT;
   while (TW > 32 && lds_of(TW, NT, nullptr) > kHalfLds) TW /= 2;
-  size_t patch_pieces = 0;
-  const size_t lds = lds_of(TW, NT, &patch_pieces);
-  if (lds > kLdsBytes) return fail("%s: kernel support too large for one workgroup's LDS (%zu bytes)", name, lds);
-  const int nblk = static_cast<int>(ceil_div(cout, 32 * NT));
-  if (nblk > 65535) return fail("%s: too many output channels for one launch", name);
+  plan->lds = lds_of(TW, NT, &plan->patch_pieces);
+  if (plan->lds > kLdsBytes) return fail("%s: kernel support too large for one workgroup's LDS (%zu bytes)", name, plan->lds);
+  plan->nblk = static_cast<int>(ceil_div(cout, 32 * NT));
+  if (plan->nblk > 65535) return fail("%s: too many output channels for one launch", name);
+  plan->TW = TW; plan->TH = kTile / TW; plan->NT = NT;
+  plan->tiles_w = static_cast<int>(ceil_div(phases[0].OD[2], TW));          // every phase has the same output grid
+  plan->tiles_h = static_cast<int>(ceil_div(phases[0].OD[1], plan->TH));
+  return 0;
+}
+
+int conv3d_bf16(const char* name, const __bf16* x, const float* w, int planes, const float* bias, void* y, bool out_f32,
+                int64_t n, const int64_t in[3], int64_t cin_k, int64_t cin_w, int64_t cout, const int k[3], const int s[3],
+                int activation, int up, hipStream_t st) {
+  FwdPlan plan;
+  if (int rc = conv3d_plan(name, up, in, cout, k, s, &plan)) return rc;
+  const std::vector<Phase>& phases = plan.phases;
+  const int nph = static_cast<int>(phases.size());
+  const int64_t* yd = plan.yd;
+  const int TW = plan.TW, NT = plan.NT, nblk = plan.nblk;
+  const size_t patch_pieces = plan.patch_pieces, lds = plan.lds;
+  const int cblocks = static_cast<int>(cin_k / 16);
   // packed weights of every phase
   std::vector<long long> wofs(nph);
   long long wtotal = 0;
@@ -412,12 +435,12 @@ int conv3d_bf16(const char* name, const __bf16* x, const float* w, int planes, c
     g.YD = static_cast<int>(yd[0]); g.YH = static_cast<int>(yd[1]); g.YW = static_cast<int>(yd[2]);
     g.Cout = static_cast<int>(cout);
     for (int a = 0; a < 3; ++a) { g.S[a] = f.S[a]; g.J0[a] = f.J0[a]; g.T[a] = f.T[a]; g.OS[a] = f.OS[a]; g.PH0[a] = f.PH0[a]; }
-    g.TW = TW; g.TH = kTile / TW; g.lgTW = TW == 128 ? 7 : TW == 64 ? 6 : 5;
+    g.TW = TW; g.TH = plan.TH; g.lgTW = TW == 128 ? 7 : TW == 64 ? 6 : 5;
     g.PR = (g.TH - 1) * f.S[1] + f.T[1];
     g.PC = (TW - 1) * f.S[2] + f.T[2];
     g.PCh = (g.PC + f.S[2] - 1) / f.S[2];
-    g.tiles_w = static_cast<int>(ceil_div(g.OW, TW));
-    g.tiles_h = static_cast<int>(ceil_div(g.OH, g.TH));
+    g.tiles_w = plan.tiles_w;
+    g.tiles_h = plan.tiles_h;
     g.wofs = wofs[p];
     g.patch_pieces = static_cast<int>(patch_pieces);
     g.activation = activation;
@@ -444,31 +467,42 @@ int conv3d_bf16(const char* name, const __bf16* x, const float* w, int planes, c
   return 0;
 }
 
+// the scalar arguments of a forward call, as conv3d_entry and tfc_conv3d_plan both demand them
+int conv3d_check(const char* name, int64_t n, const int64_t in[3], int64_t cin, int64_t cout, const int k[3], const int s[3]) {
+  if (k[0] < 1 || k[1] < 1 || k[2] < 1) return fail("%s: kernel support must be >= 1 (got %d, %d, %d)", name, k[0], k[1], k[2]);
+  if (s[0] < 1 || s[1] < 1 || s[2] < 1) return fail("%s: strides must be >= 1 (got %d, %d, %d)", name, s[0], s[1], s[2]);
+  if (n < 0 || in[0] < 0 || in[1] < 0 || in[2] < 0) return fail("%s: negative extent", name);
+  if (cin < 1 || cout < 1) return fail("%s: channel counts must be >= 1", name);
+  if (cin % 16) return fail("%s: input channels must be a multiple of 16 (got %lld)", name, static_cast<long long>(cin));
+  if (cin >= (1 << 24) || cout >= (1 << 24)) return fail("%s: too many channels", name);
+  return 0;
+}
+int conv3d_check_extents(const char* name, const int64_t in[3], const int s[3]) {
+  for (int a = 0; a < 3; ++a)
+    if (in[a] >= (1ll << 31) / std::max(1, s[a])) return fail("%s: extent too large", name);
+  return 0;
+}
+
 int conv3d_entry(const char* name, const void* x, const void* w, const float* bias, void* y, int dtype, int64_t n,
                  int64_t d, int64_t h, int64_t wd, int64_t cin, int64_t cout, int kd, int kh, int kw, int sd, int sh,
                  int sw, int activation, int up, void* stream) {
   if (int rc = check_dtype(name, dtype)) return rc;
-  if (kd < 1 || kh < 1 || kw < 1) return fail("%s: kernel support must be >= 1 (got %d, %d, %d)", name, kd, kh, kw);
-  if (sd < 1 || sh < 1 || sw < 1) return fail("%s: strides must be >= 1 (got %d, %d, %d)", name, sd, sh, sw);
-  if (n < 0 || d < 0 || h < 0 || wd < 0) return fail("%s: negative extent", name);
-  if (cin < 1 || cout < 1) return fail("%s: channel counts must be >= 1", name);
-  if (cin % 16) return fail("%s: input channels must be a multiple of 16 (got %lld)", name, static_cast<long long>(cin));
-  if (activation != 0 && activation != 1) return fail("%s: activation must be 0 (none) or 1 (relu)", name);
-  if (cin >= (1 << 24) || cout >= (1 << 24)) return fail("%s: too many channels", name);
-  if (n == 0 || d == 0 || h == 0 || wd == 0) return 0;
-  if (!x || !w || !y) return fail("%s: x, w and y must not be null", name);
   const int64_t in[3] = {d, h, wd};
   const int k[3] = {kd, kh, kw}, s[3] = {sd, sh, sw};
-  for (int a = 0; a < 3; ++a)
-    if (in[a] >= (1ll << 31) / std::max(1, s[a])) return fail("%s: extent too large", name);
+  if (int rc = conv3d_check(name, n, in, cin, cout, k, s)) return rc;
+  if (activation != 0 && activation != 1) return fail("%s: activation must be 0 (none) or 1 (relu)", name);
+  if (n == 0 || d == 0 || h == 0 || wd == 0) return 0;
+  if (!x || !w || !y) return fail("%s: x, w and y must not be null", name);
+  if (int rc = conv3d_check_extents(name, in, s)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (dtype == 1)
     return conv3d_bf16(name, static_cast<const __bf16*>(x), static_cast<const float*>(w), 1, bias, y, false, n, in, cin,
                        cin, cout, k, s, activation, up, st);
   // float32: six bfloat16 planes (split3) through the same kernel, float32 out; images in chunks of ~2 GB of planes
+  // (conv_f32_chunk_bytes: TFC_CONV_F32_CHUNK_BYTES, as the rank-2 path)
   const long long pix_image = d * h * wd;
   const size_t plane_bytes = static_cast<size_t>(pix_image) * 6 * cin * sizeof(__bf16);
-  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, static_cast<int64_t>((size_t{2} << 30) / plane_bytes)));
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, static_cast<int64_t>(conv_f32_chunk_bytes() / plane_bytes)));
   if (ceil_div(pix_image * chunk * (cin / 8), 256) > kMaxGrid) return fail("%s: problem too large for one launch", name);
   DevBuf xs;
   TFC_HIP(xs.alloc(plane_bytes * static_cast<size_t>(chunk), st));
@@ -487,6 +521,45 @@ int conv3d_entry(const char* name, const void* x, const void* w, const float* bi
                              static_cast<float*>(y) + n0 * out_image, true, nc, in, 6 * cin, cin, cout, k, s, activation, up, st))
       return rc;
   }
+  return 0;
+}
+
+// the scalar arguments of a weight gradient call, as tfc_conv3d_wgrad and tfc_conv3d_wgrad_plan both demand them
+int conv3d_wgrad_check(const char* name, int64_t n, std::initializer_list<int64_t> extents, int64_t ca, int64_t cb, int kd,
+                       int kh, int kw) {
+  if (kd < 1 || kh < 1 || kw < 1) return fail("%s: kernel support must be >= 1 (got %d, %d, %d)", name, kd, kh, kw);
+  if (n < 0) return fail("%s: negative extent", name);
+  for (int64_t e : extents)
+    if (e < 0) return fail("%s: negative extent", name);
+  if (ca < 16 || cb < 16 || ca % 16 || cb % 16)
+    return fail("%s: channel counts must be multiples of 16 (got %lld, %lld)", name, static_cast<long long>(ca),
+                static_cast<long long>(cb));
+  if (static_cast<long long>(kd) * kh * kw >= (1ll << 20)) return fail("%s: kernel support too large", name);
+  if (ca >= (1 << 24) || cb >= (1 << 24)) return fail("%s: too many channels", name);
+  for (int64_t e : extents)
+    if (e >= (1ll << 31)) return fail("%s: extent too large", name);
+  return 0;
+}
+
+// What the host chooses for one weight gradient call over P > 0 pixels of B: the 64 x 64 channel tiles and the chunks of
+// pixels.  tfc_conv3d_wgrad launches from it and tfc_conv3d_wgrad_plan reports it.
+struct WgradPlan {
+  long long tiles_ca, tiles_cb, chunks, chunk_steps;      // chunk_steps: LDS stages of 64 pixels per chunk
+};
+
+int conv3d_wgrad_plan(const char* name, long long P, long long taps, int64_t ca, int64_t cb, WgradPlan* plan) {
+  plan->tiles_ca = ceil_div(ca, 64);
+  plan->tiles_cb = ceil_div(cb, 64);
+  const long long tiles = plan->tiles_ca * plan->tiles_cb;
+  if (tiles > 65535 || taps > kMaxGrid) return fail("%s: problem too large for one launch", name);
+  // chunks of B's pixels: about 4096 workgroups in all, and at most 256 MB of partials
+  const long long per_chunk = taps * ca * cb;
+  const long long steps = ceil_div(P, 64);
+  long long chunks = std::min<long long>(steps, std::max<long long>(1, ceil_div(4096, taps * tiles)));
+  chunks = std::max<long long>(1, std::min<long long>(chunks, static_cast<long long>((size_t{256} << 20) / (static_cast<size_t>(per_chunk) * 4))));
+  chunks = std::min<long long>(chunks, 65535);
+  plan->chunk_steps = ceil_div(steps, chunks);
+  plan->chunks = ceil_div(steps, plan->chunk_steps);
   return 0;
 }
 
@@ -513,18 +586,10 @@ extern "C" int tfc_conv3d_wgrad(const void* a, const void* b, float* dw, int dty
   using namespace tfc;
   const char* name = "tfc_conv3d_wgrad";
   if (int rc = check_dtype(name, dtype)) return rc;
-  if (kd < 1 || kh < 1 || kw < 1) return fail("%s: kernel support must be >= 1 (got %d, %d, %d)", name, kd, kh, kw);
   if (sd < 1 || sh < 1 || sw < 1) return fail("%s: strides must be >= 1 (got %d, %d, %d)", name, sd, sh, sw);
-  if (n < 0 || da < 0 || ha < 0 || wa < 0 || db < 0 || hb < 0 || wb < 0) return fail("%s: negative extent", name);
-  if (ca < 16 || cb < 16 || ca % 16 || cb % 16)
-    return fail("%s: channel counts must be multiples of 16 (got %lld, %lld)", name, static_cast<long long>(ca),
-                static_cast<long long>(cb));
   if (transpose != 0 && transpose != 1) return fail("%s: transpose must be 0 or 1", name);
+  if (int rc = conv3d_wgrad_check(name, n, {da, ha, wa, db, hb, wb}, ca, cb, kd, kh, kw)) return rc;
   const long long taps = static_cast<long long>(kd) * kh * kw;
-  if (taps >= (1ll << 20)) return fail("%s: kernel support too large", name);
-  if (ca >= (1 << 24) || cb >= (1 << 24)) return fail("%s: too many channels", name);
-  for (int64_t e : {da, ha, wa, db, hb, wb})
-    if (e >= (1ll << 31)) return fail("%s: extent too large", name);
   if (!dw) return fail("%s: dw must not be null", name);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const long long per_chunk = taps * ca * cb;
@@ -539,18 +604,11 @@ extern "C" int tfc_conv3d_wgrad(const void* a, const void* b, float* dw, int dty
   g.DA = static_cast<int>(da); g.HA = static_cast<int>(ha); g.WA = static_cast<int>(wa); g.CA = static_cast<int>(ca);
   g.DB = static_cast<int>(db); g.HB = static_cast<int>(hb); g.WB = static_cast<int>(wb); g.CB = static_cast<int>(cb);
   g.k[0] = kd; g.k[1] = kh; g.k[2] = kw; g.s[0] = sd; g.s[1] = sh; g.s[2] = sw;
-  const long long cat = ceil_div(ca, 64);
-  g.cbt = static_cast<int>(ceil_div(cb, 64));
-  const long long tiles = cat * g.cbt;
-  if (tiles > 65535 || taps > kMaxGrid) return fail("%s: problem too large for one launch", name);
-  // chunks of B's pixels: about 4096 workgroups in all, and at most 256 MB of partials
-  const long long steps = ceil_div(P, 64);
-  long long chunks = std::min<long long>(steps, std::max<long long>(1, ceil_div(4096, taps * tiles)));
-  chunks = std::max<long long>(1, std::min<long long>(chunks, static_cast<long long>((size_t{256} << 20) / (static_cast<size_t>(per_chunk) * 4))));
-  chunks = std::min<long long>(chunks, 65535);
-  const long long chunk_steps = ceil_div(steps, chunks);
-  chunks = ceil_div(steps, chunk_steps);
-  g.chunk_px = chunk_steps * 64;
+  WgradPlan plan;
+  if (int rc = conv3d_wgrad_plan(name, P, taps, ca, cb, &plan)) return rc;
+  g.cbt = static_cast<int>(plan.tiles_cb);
+  const long long tiles = plan.tiles_ca * plan.tiles_cb, chunks = plan.chunks;
+  g.chunk_px = plan.chunk_steps * 64;
   DevBuf part;
   TFC_HIP(part.alloc(static_cast<size_t>(chunks * per_chunk) * sizeof(float), st));
   KernelTimer timer("conv3d", st);
@@ -567,5 +625,41 @@ extern "C" int tfc_conv3d_wgrad(const void* a, const void* b, float* dw, int dty
                      part.as<float>(), per_chunk, static_cast<int>(chunks), static_cast<int>(ca), static_cast<int>(cb),
                      transpose, dw);
   TFC_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int tfc_conv3d_plan(int up, int64_t d, int64_t h, int64_t wd, int64_t cin_k, int64_t cout, int kd, int kh,
+                               int kw, int sd, int sh, int sw, int32_t* out) {
+  using namespace tfc;
+  const char* name = "tfc_conv3d_plan";
+  const int64_t in[3] = {d, h, wd};
+  const int k[3] = {kd, kh, kw}, s[3] = {sd, sh, sw};
+  if (up != 0 && up != 1) return fail("%s: up must be 0 or 1", name);
+  if (int rc = conv3d_check(name, 1, in, cin_k, cout, k, s)) return rc;
+  if (d == 0 || h == 0 || wd == 0) return fail("%s: an empty input launches nothing", name);
+  if (int rc = conv3d_check_extents(name, in, s)) return rc;
+  if (!out) return fail("%s: out must not be null", name);
+  FwdPlan plan;
+  if (int rc = conv3d_plan(name, up, in, cout, k, s, &plan)) return rc;
+  const int32_t v[8] = {plan.TW, plan.TH, plan.NT, plan.nblk, plan.tiles_w, plan.tiles_h,
+                        static_cast<int32_t>(plan.phases.size()), static_cast<int32_t>(plan.lds)};
+  std::copy(v, v + 8, out);
+  return 0;
+}
+
+extern "C" int tfc_conv3d_wgrad_plan(int64_t n, int64_t db, int64_t hb, int64_t wb, int64_t ca, int64_t cb, int kd, int kh,
+                                     int kw, int32_t* out) {
+  using namespace tfc;
+  const char* name = "tfc_conv3d_wgrad_plan";
+  if (int rc = conv3d_wgrad_check(name, n, {db, hb, wb}, ca, cb, kd, kh, kw)) return rc;
+  const long long P = n * db * hb * wb;
+  if (P == 0) return fail("%s: an empty cotangent launches nothing", name);
+  if (!out) return fail("%s: out must not be null", name);
+  WgradPlan plan;
+  if (int rc = conv3d_wgrad_plan(name, P, static_cast<long long>(kd) * kh * kw, ca, cb, &plan)) return rc;
+  const int32_t v[5] = {static_cast<int32_t>(plan.tiles_ca), static_cast<int32_t>(plan.tiles_cb),
+                        static_cast<int32_t>(plan.chunks), static_cast<int32_t>(plan.chunk_steps),
+                        static_cast<int32_t>(P - (plan.chunks - 1) * plan.chunk_steps * 64)};
+  std::copy(v, v + 5, out);
   return 0;
 }

@@ -328,6 +328,29 @@ def conv3d_wgrad(a, b, kernel_support, strides, transpose):
     return dw[..., :cb, :ca] if transpose else dw[..., :ca, :cb]
 
 
+CONV3D_PLAN_FIELDS = ("TW", "TH", "NT", "nblk", "tiles_w", "tiles_h", "phases", "lds_bytes")
+CONV3D_WGRAD_PLAN_FIELDS = ("tiles_ca", "tiles_cb", "chunks", "chunk_steps", "pixels_in_last_chunk")
+
+
+def conv3d_plan(up, extent, cin_k, cout, kernel_support, strides):
+    """What the host of tfc_conv3d_down / tfc_conv3d_up chooses for an input of `extent` (d, h, w) with cin_k channels as
+    the kernel sees them (Cin for bfloat16, 6 Cin for float32), as a dict over CONV3D_PLAN_FIELDS (include/tfc_hip.h,
+    tfc_conv3d_plan).  Host only: needs no device and launches nothing."""
+    import ctypes
+    out = (ctypes.c_int32 * len(CONV3D_PLAN_FIELDS))()
+    _lib.check(_lib.lib().tfc_conv3d_plan(int(bool(up)), *extent, cin_k, cout, *kernel_support, *strides, out))
+    return dict(zip(CONV3D_PLAN_FIELDS, out))
+
+
+def conv3d_wgrad_plan(n, b_extent, ca, cb, kernel_support):
+    """What the host of tfc_conv3d_wgrad chooses over B's grid [n, *b_extent], as a dict over CONV3D_WGRAD_PLAN_FIELDS
+    (include/tfc_hip.h, tfc_conv3d_wgrad_plan).  Host only."""
+    import ctypes
+    out = (ctypes.c_int32 * len(CONV3D_WGRAD_PLAN_FIELDS))()
+    _lib.check(_lib.lib().tfc_conv3d_wgrad_plan(n, *b_extent, ca, cb, *kernel_support, out))
+    return dict(zip(CONV3D_WGRAD_PLAN_FIELDS, out))
+
+
 # per number of spatial axes: (forward launcher, weight gradient); rank 2 takes one stride, rank 3 one per axis
 _CONV_KERNELS = {2: (_conv, conv2d_wgrad), 3: (_conv3d, conv3d_wgrad)}
 

@@ -646,6 +646,21 @@ int tfc_conv3d_wgrad(const void* a, const void* b, float* dw, int dtype, int64_t
                      int64_t da, int64_t ha, int64_t wa, int64_t ca, int64_t db, int64_t hb, int64_t wb,
                      int64_t cb, int kd, int kh, int kw, int sd, int sh, int sw, int transpose, void* stream);
 
+/* What the host would choose for such calls, from the functions the launches themselves take it from.  Host only:
+ * nothing is launched and no device is touched, so a test can pick and assert its shapes from the kernels' own tile and
+ * chunk rules (no reference counterpart).  Arguments are checked as by the calls; an empty problem is an error.
+ * tfc_conv3d_plan: one image of tfc_conv3d_down (up = 0) / tfc_conv3d_up (up = 1) with cin_k input channels AS THE
+ * KERNEL SEES THEM (Cin for bfloat16, 6 Cin for float32's planes) -> out HOST int32[8] = TW, TH (the tile: TH x TW
+ * output samples of a phase), NT (32-column tiles per workgroup), nblk (column blocks), tiles_w, tiles_h (per phase
+ * and depth slice), phases (launches), lds_bytes (one workgroup's stage).
+ * tfc_conv3d_wgrad_plan: tfc_conv3d_wgrad over B's grid [n,db,hb,wb] -> out HOST int32[5] = tiles_ca, tiles_cb (64
+ * channels each), chunks (of B's pixels, each summed by one workgroup per tap and tile), chunk_steps (LDS stages of
+ * 64 pixels per chunk), pixels_in_last_chunk. */
+int tfc_conv3d_plan(int up, int64_t d, int64_t h, int64_t wd, int64_t cin_k, int64_t cout,
+                    int kd, int kh, int kw, int sd, int sh, int sw, int32_t* out);
+int tfc_conv3d_wgrad_plan(int64_t n, int64_t db, int64_t hb, int64_t wb, int64_t ca, int64_t cb,
+                          int kd, int kh, int kw, int32_t* out);
+
 /* ------------------------------------------------------------------------ */
 /* Training-time entropy bottleneck (deep factorized prior), fused          */
 /* ------------------------------------------------------------------------ */

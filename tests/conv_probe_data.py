@@ -38,7 +38,8 @@ proves its power without a device, tests/test_conv_probes_gpu.py runs it on the 
        576    0.100    6.0              0.70               transposed 5x5 x2 64 -> 4
 
    (The transposed cases count the taps of the fullest phase; the other phases sum fewer products, hence their lower
-   shares.)  The input-gradient cases, on |gy|, |w|: 8.0 at the most, 0.55 non-zero at the least.
+   shares.)  The input-gradient cases, on |gy|, |w|: 8.0 at the most, 0.55 non-zero at the least.  The ten
+   GEOMETRY_CASES_3D (K 48 ... 1296, densities 0.346 ... 0.067): 10.02 at the most, 0.54 non-zero at the least.
 
 2. Impulse responses: the bfloat16 kernels' rounding of their float32 weights (pack_bf16 and the casts of the packing
    kernels).  x is bfloat16 zeros with isolated ones, the weights are full-mantissa float32, the oracle runs on
@@ -181,8 +182,143 @@ GRADIENT_CASES = [
     case("grad-down3d-333-s122", False, 1, (3, 6, 9), 16, 16, (3, 3, 3), (1, 2, 2)),
     case("grad-up3d-115-s122", True, 1, (2, 4, 19), 16, 16, (1, 1, 5), (1, 2, 2)),
 ]
+GRADIENT_CASES += [
+    # dx of the first runs the transposed rank-3 kernel with two phases over two W tiles, dx of the second the correlation
+    case("grad-down1d-5-s2-w261", False, 1, (1, 1, 261), 32, 16, (1, 1, 5), (1, 1, 2)),
+    case("grad-up1d-5-s2-w131", True, 1, (1, 1, 131), 16, 32, (1, 1, 5), (1, 1, 2)),
+]
 BIAS_RELU_CASE = PLANE_CASES_2D[1]
-PLANE_CASES = PLANE_CASES_2D + [CHUNKED_CASE] + PLANE_CASES_3D
+
+# ---- the rank-3 kernels' tile, block and chunk structure (csrc/signal_conv3d.hip) -----------------------------------
+# Shapes chosen from the host's rule, which tfc_conv3d_plan reports: GEOMETRY_PLANS holds what each case must reach,
+# and tests/test_conv3d_geometry_cpu.py asserts it from the library, so a retune that moves a case off its branch fails
+# there and names the case.
+GEOMETRY_CASES_3D = [
+    case("down1d-5-s1-w300", False, 2, (1, 1, 300), 16, 32, (1, 1, 5), (1, 1, 1)),
+    case("down1d-5-s2-w261", False, 1, (1, 1, 261), 32, 16, (1, 1, 5), (1, 1, 2)),
+    case("up1d-5-s2-w131", True, 1, (1, 1, 131), 16, 32, (1, 1, 5), (1, 1, 2)),
+    case("down3d-333-h5-w40-c128", False, 2, (2, 5, 40), 16, 128, (3, 3, 3), (1, 1, 1)),
+    case("down3d-133-h2-w129", False, 1, (1, 2, 129), 32, 32, (1, 3, 3), (1, 1, 1)),
+    case("down3d-199-h6-w70", False, 1, (1, 6, 70), 16, 32, (1, 9, 9), (1, 1, 1)),
+    case("down3d-177-h3-w70-c128", False, 1, (1, 3, 70), 16, 128, (1, 7, 7), (1, 1, 1)),
+    case("down3d-333-s122-c200", False, 1, (2, 6, 70), 16, 200, (3, 3, 3), (1, 2, 2)),
+    case("up3d-335-s122-c72", True, 1, (2, 3, 70), 32, 72, (3, 3, 5), (1, 2, 2)),
+    case("up3d-333-s212-w33", True, 3, (2, 3, 33), 16, 16, (3, 3, 3), (2, 1, 2)),
+]
+# name -> the plan fields the case is there for (TW, TH: the tile; NT: 32-column tiles per workgroup; nblk: column
+# blocks; tiles_w, tiles_h; phases), and what follows from them:
+#   last_tile_w   samples of the last W tile that are inside the row (of a phase's output grid)
+#   last_tile_h   rows of the last H tile that are inside
+#   last_blk_cols output channels of the last column block (of 32 NT)
+#   tw_from, nt_from   what the row length / Cout alone would pick, where the LDS loops narrow it
+#   lds_over_half True: the stage is above half the LDS (one workgroup per CU)
+#   f32_cblocks_per_plane  16-channel blocks per plane in float32 (above 1: a pack that took the plane from the channel
+#                 block would be wrong)
+GEOMETRY_PLANS = {
+    "down1d-5-s1-w300": dict(TW=128, TH=1, tiles_w=3, tiles_h=1, phases=1, last_tile_w=44),
+    "down1d-5-s2-w261": dict(TW=128, tiles_w=2, phases=1, last_tile_w=3, f32_cblocks_per_plane=2),
+    "up1d-5-s2-w131": dict(TW=128, tiles_w=2, phases=2, last_tile_w=3),
+    "down3d-333-h5-w40-c128": dict(TW=64, TH=2, tiles_w=1, tiles_h=3, last_tile_h=1, NT=4, nblk=1, phases=1),
+    "down3d-133-h2-w129": dict(TW=128, TH=1, tiles_w=2, tiles_h=2, last_tile_w=1, phases=1),
+    "down3d-199-h6-w70": dict(tw_from=128, TW=32, TH=4, tiles_w=3, tiles_h=2, lds_over_half=True, phases=1),
+    "down3d-177-h3-w70-c128": dict(nt_from=4, NT=1, nblk=4, TW=128, lds_over_half=False, phases=1),
+    "down3d-333-s122-c200": dict(NT=1, nblk=7, last_blk_cols=8, TW=64, TH=2, phases=1),
+    "up3d-335-s122-c72": dict(phases=4, NT=3, nblk=1, last_blk_cols=72, TW=128, TH=1, tiles_h=3),
+    "up3d-333-s212-w33": dict(phases=4, TW=64, TH=2, tiles_w=1, tiles_h=2, last_tile_h=1),
+}
+GEOMETRY_BIAS_RELU_CASE = GEOMETRY_CASES_3D[7]               # the bias is read at blk > 0, the last column block is partial
+GEOMETRY_CHUNKED_CASE = GEOMETRY_CASES_3D[9]                 # three images
+assert set(GEOMETRY_PLANS) == {c["name"] for c in GEOMETRY_CASES_3D}
+
+# Weight gradient: G[t][ca][cb] = sum over B's P pixels.  `up` as the layer's direction: down calls
+# conv3d_wgrad(x, gy, ..., False) (A = x carries Cin, B = gy), up calls conv3d_wgrad(gy, x, ..., True) (A = gy carries
+# Cout, B = x).  WGRAD_PLANS: what tfc_conv3d_wgrad_plan must report (pixels = P, stages of 64 pixels).
+WGRAD_CASES_3D = [
+    case("wgrad-down-335-s122-80-144", False, 2, (3, 18, 74), 80, 144, (3, 3, 5), (1, 2, 2)),
+    case("wgrad-up-355-s122-128-80", True, 2, (2, 13, 33), 128, 80, (3, 5, 5), (1, 2, 2)),
+]
+WGRAD_PLANS = {
+    "wgrad-down-335-s122-80-144": dict(pixels=1998, ca=80, cb=144, tiles_ca=2, tiles_cb=3, chunks=16, chunk_steps=2,
+                                       pixels_in_last_chunk=78),
+    "wgrad-up-355-s122-128-80": dict(pixels=1716, ca=80, cb=128, tiles_ca=2, tiles_cb=2, chunks=14, chunk_steps=2,
+                                     pixels_in_last_chunk=52),
+}
+WGRAD_LEVELS = {"x2_g2": (2, 2), "x3_g1": (3, 1), "x1_g3": (1, 3)}       # float32: digits of x, of gy
+# One-level data (values in {-1, 0, +1}: each one bfloat16, every sum an integer below 16, hence one bfloat16) for the
+# bfloat16 kernels.  Sums of +-1 cancel to exactly zero far more often than sums of several digits do: at
+# density_for(K) the forward cases have 0.35 ... 0.66 non-zero outputs (six of the ten below a half; the lowest are the
+# transposed cases, whose thinner phases sum fewer products), at density_for(P) the two weight gradients 0.55 and 0.49.
+# The abs-sum has room, so these probes draw denser: ONE_LEVEL_DENSITY / sqrt(K) forward, WGRAD_ONE_LEVEL_DENSITY /
+# sqrt(P) for the weight gradient.  Measured (tests/test_conv3d_geometry_cpu.py prints them):
+#
+#       case                          K / P  density  largest abs-sum  non-zero outputs
+#       down1d-5-s1-w300              80     0.402    12.0             0.766
+#       down1d-5-s2-w261              160    0.285    12.0             0.774
+#       up1d-5-s2-w131                48     0.520    11.0             0.734
+#       down3d-333-h5-w40-c128        432    0.173    10.0             0.653
+#       down3d-133-h2-w129            288    0.212    9.0              0.699
+#       down3d-199-h6-w70             1296   0.100    10.0             0.690
+#       down3d-177-h3-w70-c128        784    0.129    7.0              0.598
+#       down3d-333-s122-c200          432    0.173    10.0             0.686
+#       up3d-335-s122-c72             576    0.150    9.0              0.549
+#       up3d-333-s212-w33             192    0.260    10.0             0.551
+#       wgrad-down-335-s122-80-144    1998   0.0626   11.0             0.620
+#       wgrad-up-355-s122-128-80      1716   0.0676   10.0             0.564
+#
+# and, float32, the level pairs of WGRAD_LEVELS at density_for(P): abs-sums of at most 10.02, non-zero shares 0.74 ...
+# 0.87.
+ONE_LEVEL_DENSITY = 3.6
+WGRAD_ONE_LEVEL_DENSITY = 2.8
+
+
+def wgrad_geometry(c):
+    """-> (extent of B's grid, CA, CB, P) of the weight gradient call of layer case c."""
+    y_extent = tuple(n * s if c["up"] else -(-n // s) for n, s in zip(c["extent"], c["strides"]))
+    b_extent = c["extent"] if c["up"] else y_extent
+    ca, cb = (c["cout"], c["cin"]) if c["up"] else (c["cin"], c["cout"])
+    return b_extent, ca, cb, c["n"] * math.prod(b_extent)
+
+
+@functools.lru_cache(maxsize=None)
+def _wgrad_data(key, levels):
+    c = _BY_NAME[key]
+    x_levels, g_levels = WGRAD_LEVELS.get(levels, (1, 1))
+    pixels = wgrad_geometry(c)[3]
+    density = density_for(pixels) if levels in WGRAD_LEVELS else WGRAD_ONE_LEVEL_DENSITY / math.sqrt(pixels)
+    rng = np.random.default_rng(_seed(c, levels, 3))
+    x = probe_values((c["n"],) + c["extent"] + (c["cin"],), x_levels, density, rng)
+    shape = c["support"] + (c["cin"], c["cout"])
+    w = torch.zeros(shape, dtype=torch.float64, requires_grad=True)
+    y = oracle(c, x.double(), w)
+    gy = probe_values(tuple(y.shape), g_levels, density, rng)
+    y.backward(gy.double())
+    wa = torch.zeros(shape, dtype=torch.float64, requires_grad=True)
+    oracle(c, x.abs().double(), wa).backward(gy.abs().double())
+    return x, gy, w.grad, wa.grad
+
+
+def wgrad_data(c, levels):
+    """-> (x float32, gy float32, the oracle's kernel gradient [*support, Cin, Cout] of oracle(c, x, w) against gy (float64
+    autograd), its abs-sum: the same on |x|, |gy|), made once.  levels: a key of WGRAD_LEVELS, or "one_level"."""
+    return _wgrad_data(c["name"], levels)
+
+
+@functools.lru_cache(maxsize=None)
+def _one_level_data(key):
+    c = _BY_NAME[key]
+    rng = np.random.default_rng(_seed(c, "one_level"))
+    density = ONE_LEVEL_DENSITY / math.sqrt(products_per_output(c))
+    x = probe_values((c["n"],) + c["extent"] + (c["cin"],), 1, density, rng)
+    w = probe_values(c["support"] + (c["cin"], c["cout"]), 1, density, rng)
+    return x, w, oracle(c, x, w)
+
+
+def one_level_data(c):
+    """-> (x, kernel, the float64 oracle's output), x and kernel in {-1, 0, +1} (float32 tensors; each value one bfloat16)."""
+    return _one_level_data(c["name"])
+
+
+PLANE_CASES = PLANE_CASES_2D + [CHUNKED_CASE] + PLANE_CASES_3D + GEOMETRY_CASES_3D
 
 
 # ---- impulse responses ---------------------------------------------------------------------------------------------
@@ -283,5 +419,5 @@ def impulse_data(c):
     return _impulse_data(c["name"])
 
 
-_BY_NAME = {c["name"]: c for c in PLANE_CASES + GRADIENT_CASES + IMPULSE_CASES}
-assert len(_BY_NAME) == len(PLANE_CASES + GRADIENT_CASES + IMPULSE_CASES)
+_BY_NAME = {c["name"]: c for c in PLANE_CASES + GRADIENT_CASES + IMPULSE_CASES + WGRAD_CASES_3D}
+assert len(_BY_NAME) == len(PLANE_CASES + GRADIENT_CASES + IMPULSE_CASES + WGRAD_CASES_3D)

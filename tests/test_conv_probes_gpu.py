@@ -98,7 +98,9 @@ def test_float32_plane_probe_in_several_chunks_of_images(monkeypatch):
 
 # The input gradient is the OTHER direction's kernel on the cotangent with the kernel's channel axes swapped, Cin = Cout
 # = 16: the gradient of a down layer runs the transposed second-generation / rank-3 kernel on six planes of gy, that of
-# an up layer the correlation.  gy is drawn from the x-side grid, the kernel from the w-side grid.
+# an up layer the correlation.  gy is drawn from the x-side grid, the kernel from the w-side grid.  The two rank-1 cases
+# (261 and 131 samples, 32 <-> 16 channels) are wider than one 128-sample tile: dx of grad-down1d-5-s2-w261 runs the
+# transposed kernel's two phases over two W tiles, dx of grad-up1d-5-s2-w131 the stride-2 correlation over two.
 @pytest.mark.parametrize("probe", PROBES)
 @pytest.mark.parametrize("c", pd.GRADIENT_CASES, ids=pd.case_id)
 def test_float32_input_gradient_equals_the_oracle_on_plane_probes(c, probe):
