@@ -114,6 +114,7 @@ SIGNATURES = {
     "tfc_conv2d_drop_weights": (_int, [C.c_uint64]),
     "tfc_conv2d_wgrad": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int,
                                 _int, _int, _int, _vp]),
+    "tfc_conv2d_wgrad_plan": (_int, [_int, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, C.POINTER(C.c_int32)]),
     "tfc_conv3d_down": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64,
                                _int, _int, _int, _int, _int, _int, _int, _vp]),
     "tfc_conv3d_up": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64,

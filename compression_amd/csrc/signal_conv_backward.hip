@@ -40,8 +40,9 @@ struct WgradGeom {
 
 // Row stride (elements) of a row-major bf16 stage in LDS whose rows ds_read_b64_tr_b16 reads without bank conflicts:
 // stride in dwords = 16 mod 32 (gdn_backward.hip pg_row_elems).
+constexpr int wg_row_elems(int C) { return C + 2 * (((16 - (C / 2) % 32) + 32) % 32); }
 template <int C>
-constexpr int wg_row_elems() { return C + 2 * (((16 - (C / 2) % 32) + 32) % 32); }
+constexpr int wg_row_elems() { return wg_row_elems(C); }
 
 // KTA / KTB = 32-channel tiles of A / B (1 with CA <= 4 = narrow tensor)
 template <typename T, int KTA, int KTB, bool TRB = false>
@@ -363,30 +364,71 @@ __global__ void conv_wgrad_reduce_kernel(const float* partial, int taps, int chu
   else dw[idx] += s;
 }
 
-template <typename T, int KTA, int KTB>
-int launch_wgrad(WgradGeom g, int transpose, float* dw, hipStream_t st) {
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const int taps = g.kh * g.kw;
-  const long long stages = ceil_div(g.N * g.HB * g.WB, static_cast<long long>(WG_PIX));
+// the scalar arguments of a weight gradient call, as tfc_conv2d_wgrad and tfc_conv2d_wgrad_plan both demand them
+int conv2d_wgrad_check(const char* name, int dtype, int64_t n, int64_t hb, int64_t wb, int64_t ca, int64_t cb, int kh,
+                       int kw, int stride) {
+  if (int rc = check_dtype(name, dtype)) return rc;
+  if (kh < 1 || kw < 1 || stride < 1 || ca < 1 || cb < 1) return fail("%s: bad geometry", name);
+  auto ok = [](int64_t c) { return c <= 4 || (c % 32 == 0 && c <= 256); };
+  if (!ok(ca) || !ok(cb))
+    return fail("%s: channel counts must be <= 4 or multiples of 32 up to 256 (got %lld, %lld)", name,
+                static_cast<long long>(ca), static_cast<long long>(cb));
+  if (n < 0 || hb < 0 || wb < 0) return fail("%s: negative extent", name);
+  return 0;
+}
+
+inline int tiles_of(int64_t c) { return c <= 4 ? 1 : static_cast<int>(c / 32); }
+
+// TFC_WGRAD_TR = 0 (read once per process): the transpose by hand (the round-5 staging) for every bfloat16 pair
+inline bool wgrad_tr_enabled() {
+  static const bool tr_on = [] { const char* e = std::getenv("TFC_WGRAD_TR"); return !(e && e[0] == '0'); }();
+  return tr_on;
+}
+
+// What the host chooses for one weight gradient call over P > 0 pixels of B on a device of `cus` compute units: the
+// build (32-channel tiles per side, transposing reads or not), the workgroups per tap and one workgroup's LDS.
+// tfc_conv2d_wgrad launches from it and tfc_conv2d_wgrad_plan reports it.
+struct WgradPlan {
+  int tiles_ca, tiles_cb;      // KTA, KTB of the build
+  int chunks;                  // workgroups per tap: workgroup `chunk` takes stages chunk, chunk + chunks, ...
+  long long stages;            // LDS stages of WG_PIX pixels
+  int tr;                      // WgradGeom::tr
+  size_t lds;                  // dynamic LDS bytes of one workgroup
+};
+
+int conv2d_wgrad_plan(const char* name, int dtype, long long P, int taps, int64_t ca, int64_t cb, int cus,
+                      WgradPlan* plan) {
+  const int ka = tiles_of(ca), kb = tiles_of(cb);
+  auto built = [](int k) { return k == 1 || k == 2 || k == 4 || k == 6 || k == 8; };          // dispatch_wgrad's pairs
+  if (!built(ka) || !built(kb))
+    return fail("%s: channel pair (%d, %d) is not built (each side: <= 4 channels, or 32, 64, 128, "
+                "192 or 256)", name, static_cast<int>(ca), static_cast<int>(cb));
+  if (cus < 1) return fail("%s: cus must be >= 1 (got %d)", name, cus);
+  plan->tiles_ca = ka;
+  plan->tiles_cb = kb;
+  plan->stages = ceil_div(P, static_cast<long long>(WG_PIX));
   // taps x chunks workgroups: at most two per CU, and not a few more than that (525 workgroups on 256 CUs, one resident
   // per CU, were three rounds of which the last ran 13)
-  g.chunks = static_cast<int>(std::max<long long>(1, std::min<long long>(stages, (2 * cus) / taps)));
+  plan->chunks = static_cast<int>(std::max<long long>(1, std::min<long long>(plan->stages, (2 * cus) / taps)));
+  const bool bf = dtype == 1;
+  plan->lds = bf ? sizeof(unsigned short) * (ka + kb) * 32 * WG_STRIDE : sizeof(float) * WG_PIX * (ka + kb) * 32;
+  plan->tr = wgrad_tr_enabled() && bf && ca >= 32 && cb >= 32 && P < (1ll << 31) ? 1 : 0;
+  if (plan->tr)
+    plan->lds = std::max(plan->lds, sizeof(unsigned short) * WG_PIX * (wg_row_elems(ka * 32) + wg_row_elems(kb * 32)));
+  return 0;
+}
+
+template <typename T, int KTA, int KTB>
+int launch_wgrad(WgradGeom g, const WgradPlan& plan, int transpose, float* dw, hipStream_t st) {
+  const int taps = g.kh * g.kw;
+  g.chunks = plan.chunks;
+  g.tr = plan.tr;
+  const size_t lds = plan.lds;
   DevBuf partial;
   TFC_HIP(partial.alloc(sizeof(float) * static_cast<size_t>(taps) * g.chunks * g.CA * g.CB, st));
   g.partial = partial.as<float>();
-  size_t lds = sizeof(T) == 2 ? sizeof(unsigned short) * (KTA + KTB) * 32 * WG_STRIDE
-                              : sizeof(float) * WG_PIX * (KTA + KTB) * 32;
-  {
-    // TFC_WGRAD_TR = 0: the transpose by hand (the round-5 staging)
-    static const bool tr_on = [] { const char* e = std::getenv("TFC_WGRAD_TR"); return !(e && e[0] == '0'); }();
-    g.tr = tr_on && sizeof(T) == 2 && g.CA >= 32 && g.CB >= 32 && g.N * g.HB * g.WB < (1ll << 31) ? 1 : 0;
-    fast_div_setup(static_cast<unsigned int>(g.WB), &g.wb_mul, &g.wb_sh);
-    fast_div_setup(static_cast<unsigned int>(g.HB), &g.hb_mul, &g.hb_sh);
-    if (g.tr)
-      lds = std::max(lds, sizeof(unsigned short) * WG_PIX * (wg_row_elems<KTA * 32>() + wg_row_elems<KTB * 32>()));
-  }
+  fast_div_setup(static_cast<unsigned int>(g.WB), &g.wb_mul, &g.wb_sh);
+  fast_div_setup(static_cast<unsigned int>(g.HB), &g.hb_mul, &g.hb_sh);
   {
     KernelTimer timer("conv2d_wgrad", st);
     if constexpr (sizeof(T) == 2) {
@@ -411,18 +453,16 @@ int launch_wgrad(WgradGeom g, int transpose, float* dw, hipStream_t st) {
   return 0;
 }
 
-inline int tiles_of(int64_t c) { return c <= 4 ? 1 : static_cast<int>(c / 32); }
-
+// the build of the plan's tile pair (conv2d_wgrad_plan admits the 25 pairs below and no other)
 template <typename T>
-int dispatch_wgrad(WgradGeom g, int transpose, float* dw, hipStream_t st) {
-  const int ka = tiles_of(g.CA), kb = tiles_of(g.CB);
-#define TFC_WG(KA, KB) if (ka == KA && kb == KB) return launch_wgrad<T, KA, KB>(g, transpose, dw, st)
+int dispatch_wgrad(WgradGeom g, const WgradPlan& plan, int transpose, float* dw, hipStream_t st) {
+  const int ka = plan.tiles_ca, kb = plan.tiles_cb;
+#define TFC_WG(KA, KB) if (ka == KA && kb == KB) return launch_wgrad<T, KA, KB>(g, plan, transpose, dw, st)
 #define TFC_WG_ROW(KA) TFC_WG(KA, 1); TFC_WG(KA, 2); TFC_WG(KA, 4); TFC_WG(KA, 6); TFC_WG(KA, 8)
   TFC_WG_ROW(1); TFC_WG_ROW(2); TFC_WG_ROW(4); TFC_WG_ROW(6); TFC_WG_ROW(8);
 #undef TFC_WG_ROW
 #undef TFC_WG
-  return fail("tfc_conv2d_wgrad: channel pair (%d, %d) is not built (each side: <= 4 channels, or 32, 64, 128, "
-              "192 or 256)", g.CA, g.CB);
+  return fail("tfc_conv2d_wgrad: no build for the plan's tile pair (%d, %d)", ka, kb);
 }
 
 }  // namespace tfc
@@ -431,18 +471,36 @@ extern "C" int tfc_conv2d_wgrad(const void* a, const void* b, float* dw, int dty
                                 int64_t wa, int64_t ca, int64_t hb, int64_t wb, int64_t cb, int kh, int kw,
                                 int stride, int transpose, void* stream) {
   using namespace tfc;
-  if (int rc = check_dtype("tfc_conv2d_wgrad", dtype)) return rc;
-  if (kh < 1 || kw < 1 || stride < 1 || ca < 1 || cb < 1) return fail("tfc_conv2d_wgrad: bad geometry");
-  auto ok = [](int64_t c) { return c <= 4 || (c % 32 == 0 && c <= 256); };
-  if (!ok(ca) || !ok(cb))
-    return fail("tfc_conv2d_wgrad: channel counts must be <= 4 or multiples of 32 up to 256 (got %lld, %lld)",
-                static_cast<long long>(ca), static_cast<long long>(cb));
+  const char* name = "tfc_conv2d_wgrad";
+  if (int rc = conv2d_wgrad_check(name, dtype, n, hb, wb, ca, cb, kh, kw, stride)) return rc;
   if (n == 0 || hb == 0 || wb == 0) return 0;
   WgradGeom g{};
   g.A = a; g.B = b; g.N = n;
   g.HA = static_cast<int>(ha); g.WA = static_cast<int>(wa); g.CA = static_cast<int>(ca);
   g.HB = static_cast<int>(hb); g.WB = static_cast<int>(wb); g.CB = static_cast<int>(cb);
   g.kh = kh; g.kw = kw; g.stride = stride;
+  int dev = 0, cus = 256;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  WgradPlan plan;
+  if (int rc = conv2d_wgrad_plan(name, dtype, n * hb * wb, kh * kw, ca, cb, cus, &plan)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return dtype == 1 ? dispatch_wgrad<__bf16>(g, transpose, dw, st) : dispatch_wgrad<float>(g, transpose, dw, st);
+  return dtype == 1 ? dispatch_wgrad<__bf16>(g, plan, transpose, dw, st) : dispatch_wgrad<float>(g, plan, transpose, dw, st);
+}
+
+extern "C" int tfc_conv2d_wgrad_plan(int dtype, int64_t n, int64_t hb, int64_t wb, int64_t ca, int64_t cb, int kh, int kw,
+                                     int cus, int32_t* out) {
+  using namespace tfc;
+  const char* name = "tfc_conv2d_wgrad_plan";
+  if (int rc = conv2d_wgrad_check(name, dtype, n, hb, wb, ca, cb, kh, kw, 1)) return rc;
+  if (n == 0 || hb == 0 || wb == 0) return fail("%s: an empty cotangent launches nothing", name);
+  if (!out) return fail("%s: out must not be null", name);
+  const long long P = n * hb * wb;
+  WgradPlan plan;
+  if (int rc = conv2d_wgrad_plan(name, dtype, P, kh * kw, ca, cb, cus, &plan)) return rc;
+  const int32_t v[7] = {plan.tiles_ca, plan.tiles_cb, plan.chunks,
+                        static_cast<int32_t>(ceil_div(plan.stages, static_cast<long long>(plan.chunks))),
+                        static_cast<int32_t>(P - (plan.stages - 1) * WG_PIX), plan.tr, static_cast<int32_t>(plan.lds)};
+  std::copy(v, v + 7, out);
+  return 0;
 }

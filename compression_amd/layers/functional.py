@@ -294,6 +294,19 @@ def _conv2d_wgrad_launch(a, b, kernel_support, stride, transpose):
     return dw
 
 
+CONV2D_WGRAD_PLAN_FIELDS = ("tiles_ca", "tiles_cb", "chunks", "chunk_steps", "pixels_in_last_stage", "tr", "lds_bytes")
+
+
+def conv2d_wgrad_plan(n, b_extent, ca, cb, kernel_support, dtype, cus):
+    """What the host of tfc_conv2d_wgrad chooses over B's grid [n, *b_extent] for tensors of `dtype` on a device of `cus`
+    compute units, as a dict over CONV2D_WGRAD_PLAN_FIELDS (include/tfc_hip.h, tfc_conv2d_wgrad_plan).  Host only: needs
+    no device and launches nothing."""
+    import ctypes
+    out = (ctypes.c_int32 * len(CONV2D_WGRAD_PLAN_FIELDS))()
+    _lib.check(_lib.lib().tfc_conv2d_wgrad_plan(_DTYPE_CODE[dtype], n, *b_extent, ca, cb, *kernel_support, int(cus), out))
+    return dict(zip(CONV2D_WGRAD_PLAN_FIELDS, out))
+
+
 def _conv3d(x, kernel, bias, strides, activation, up):
     kernel, bias = _conv_args(x, kernel, bias, 3)
     x, kernel = pad_channels(x).contiguous(), pad_channels(kernel, dim=-2).contiguous()

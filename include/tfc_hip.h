@@ -617,6 +617,17 @@ int tfc_conv2d_wgrad(const void* a, const void* b, float* dw, int dtype, int64_t
                      int64_t wa, int64_t ca, int64_t hb, int64_t wb, int64_t cb, int kh, int kw,
                      int stride, int transpose, void* stream);
 
+/* What the host of tfc_conv2d_wgrad would choose over B's grid [n,hb,wb] on a device of `cus` compute units, from the
+ * function the launch itself takes it from (the launch reads `cus` from its device).  Host only: nothing is launched
+ * and no device is touched (no reference counterpart).  dtype, ca, cb, kh, kw are checked as by the call and fail with
+ * the same text, the channel pairs that are not built (a side of 96, 160 or 224) included; an empty problem and
+ * cus < 1 are errors.  out HOST int32[7] = tiles_ca, tiles_cb (32-channel tiles of the build; 1 for <= 4 channels),
+ * chunks (workgroups per tap; workgroup c takes the 64-pixel stages c, c + chunks, ...), chunk_steps (= ceil(stages /
+ * chunks): the most stages one workgroup walks), pixels_in_last_stage, tr (1: the bfloat16 build with row-major
+ * stages and transposing LDS reads; 0 under TFC_WGRAD_TR=0, which a process reads once), lds_bytes (one workgroup). */
+int tfc_conv2d_wgrad_plan(int dtype, int64_t n, int64_t hb, int64_t wb, int64_t ca, int64_t cb, int kh, int kw,
+                          int cus, int32_t* out);
+
 /* ------------------------------------------------------------------------ */
 /* SignalConv1D / SignalConv3D (same_zeros, explicit padding, NDHWC)        */
 /* ------------------------------------------------------------------------ */

@@ -419,5 +419,100 @@ def impulse_data(c):
     return _impulse_data(c["name"])
 
 
-_BY_NAME = {c["name"]: c for c in PLANE_CASES + GRADIENT_CASES + IMPULSE_CASES + WGRAD_CASES_3D}
-assert len(_BY_NAME) == len(PLANE_CASES + GRADIENT_CASES + IMPULSE_CASES + WGRAD_CASES_3D)
+# ---- the rank-2 weight gradient where its loops repeat (csrc/signal_conv_backward.hip, conv_wgrad_kernel) -----------
+# A workgroup owns one tap and the 64-pixel stages chunk, chunk + chunks, ... of B's grid, chunks = max(1, min(stages,
+# 2 CUs / taps)) — so what a shape reaches depends on the device, and tfc_conv2d_wgrad_plan is asked for it with the CU
+# count as an argument: WGRAD_PLANS_2D is what it must report for 256 CUs (tests/test_conv2d_wgrad_cpu.py; the GPU tier
+# asks again with the device's own count).  Each case is named for the branch it is there for:
+#   loop-tr-*          both sides wide: bfloat16 runs the transposing-read build; three trips of the stage loop (the
+#                      prefetch inside the loop, the barriers around stage_to_lds, the strided walk), a ragged last stage,
+#                      HA = 65 < HB s = 66 (iy < HA); the `up` one transposes the store, KTA = 1 against KTB = 6
+#   loop-narrowA-*     A has 3 channels (stage_narrow; B through pair_store in bfloat16), 81 taps, stride 4, odd extents
+#   loop-8x8-*         the largest tile pair and LDS stage, WB = 64 (fast_div by a power of two), every stage full
+#   one-chunk-*        529 taps: (2 CUs) / taps == 0, one workgroup per tap walks every stage
+#   row-1x3-*          kh != kw (tap / kw, tap % kw), HB = 1 (fast_div by 1: mul == 0), 170 chunks
+#   col-4x1s2-*        kh != kw the other way round with an even kh, WB = 1, two images (n = m / (WB HB)), HA = 8193 < 8194
+#   even-4x2s2-*       even supports on both axes with kh != kw (k / 2 is not (k - 1) / 2), odd extents in front of stride 2
+#   edges-p63/64/65    one partial stage, one exact stage, one pixel over (a second chunk of one pixel)
+#   layer-*            through SignalConv2D: conv2d_wgrad's zero channels to 96 / 160 and its channel blocks (64 + 32,
+#                      128 + 32) at the loop-tr size; every block pair has the plan below
+# (A WB = 1 column with an even kw cannot meet the non-zero share asked of the data: ix = tx - kw / 2 is inside a one-
+# or two-column A for at most half of the taps, so half of dw is structurally zero.  Hence a (4, 1) column and the even
+# kw in a case of its own.)
+WGRAD_CASES_2D = [
+    case("loop-tr-5x5s2-64-128", False, 2, (65, 81), 64, 128, (5, 5), (2, 2)),
+    case("loop-tr-up-5x5s2-192-32", True, 2, (33, 41), 192, 32, (5, 5), (2, 2)),
+    case("loop-narrowA-9x9s4-3-64", False, 1, (97, 131), 3, 64, (9, 9), (4, 4)),
+    case("loop-narrowA-up-9x9s4-64-3", True, 1, (25, 33), 64, 3, (9, 9), (4, 4)),
+    case("loop-8x8-5x5s1-256-256", False, 1, (41, 64), 256, 256, (5, 5), (1, 1)),
+    case("one-chunk-23x23-3-32", False, 1, (29, 37), 3, 32, (23, 23), (1, 1)),
+    case("row-1x3-128-64", False, 1, (1, 21900), 128, 64, (1, 3), (1, 1)),
+    case("col-4x1s2-32-64", False, 2, (8193, 1), 32, 64, (4, 1), (2, 2)),
+    case("even-4x2s2-32-64", False, 1, (13, 19), 32, 64, (4, 2), (2, 2)),
+    case("edges-p63-3x3-32-32", False, 1, (7, 9), 32, 32, (3, 3), (1, 1)),
+    case("edges-p64-3x3-32-32", False, 1, (8, 8), 32, 32, (3, 3), (1, 1)),
+    case("edges-p65-3x3-32-32", False, 1, (5, 13), 32, 32, (3, 3), (1, 1)),
+]
+WGRAD_LAYER_CASES_2D = [
+    case("layer-80-144", False, 2, (65, 81), 80, 144, (5, 5), (2, 2)),
+    case("layer-up-144-80", True, 2, (33, 41), 144, 80, (5, 5), (2, 2)),
+]
+WGRAD_LOOP_CASES_2D = [c for c in WGRAD_CASES_2D if c["name"].startswith("loop-")]
+WGRAD_WIDE_LOOP_CASES_2D = [c for c in WGRAD_LOOP_CASES_2D if min(c["cin"], c["cout"]) >= 32]
+# name -> what tfc_conv2d_wgrad_plan reports at 256 CUs: pixels = P, (ca, cb) the call's channel counts, the fields of
+# functional.CONV2D_WGRAD_PLAN_FIELDS that do not depend on the dtype, then (tr, lds_bytes) for float32 and bfloat16.
+# The layer cases: `blocks` = the (ca, cb) pairs conv2d_wgrad launches, which share everything but the tiles.
+def _plan_2d(pixels, ca, cb, tiles_ca, tiles_cb, chunks, chunk_steps, pixels_in_last_stage, float32, bfloat16):
+    return dict(pixels=pixels, ca=ca, cb=cb, tiles_ca=tiles_ca, tiles_cb=tiles_cb, chunks=chunks, chunk_steps=chunk_steps,
+                pixels_in_last_stage=pixels_in_last_stage, float32=dict(zip(("tr", "lds_bytes"), float32)),
+                bfloat16=dict(zip(("tr", "lds_bytes"), bfloat16)))
+
+
+WGRAD_PLANS_2D = {
+    "loop-tr-5x5s2-64-128": _plan_2d(2706, 64, 128, 2, 4, 20, 3, 18, (0, 49152), (1, 32768)),
+    "loop-tr-up-5x5s2-192-32": _plan_2d(2706, 32, 192, 1, 6, 20, 3, 18, (0, 57344), (1, 32768)),
+    "loop-narrowA-9x9s4-3-64": _plan_2d(825, 3, 64, 1, 2, 6, 3, 57, (0, 24576), (0, 13824)),
+    "loop-narrowA-up-9x9s4-64-3": _plan_2d(825, 3, 64, 1, 2, 6, 3, 57, (0, 24576), (0, 13824)),
+    "loop-8x8-5x5s1-256-256": _plan_2d(2624, 256, 256, 8, 8, 20, 3, 64, (0, 131072), (1, 73728)),
+    "one-chunk-23x23-3-32": _plan_2d(1073, 3, 32, 1, 1, 1, 17, 49, (0, 16384), (0, 9216)),
+    "row-1x3-128-64": _plan_2d(21900, 128, 64, 4, 2, 170, 3, 12, (0, 49152), (1, 32768)),
+    "col-4x1s2-32-64": _plan_2d(8194, 32, 64, 1, 2, 128, 2, 2, (0, 24576), (1, 16384)),
+    "even-4x2s2-32-64": _plan_2d(70, 32, 64, 1, 2, 2, 1, 6, (0, 24576), (1, 16384)),
+    "edges-p63-3x3-32-32": _plan_2d(63, 32, 32, 1, 1, 1, 1, 63, (0, 16384), (1, 9216)),
+    "edges-p64-3x3-32-32": _plan_2d(64, 32, 32, 1, 1, 1, 1, 64, (0, 16384), (1, 9216)),
+    "edges-p65-3x3-32-32": _plan_2d(65, 32, 32, 1, 1, 2, 1, 1, (0, 16384), (1, 9216)),
+}
+# the layer cases: conv2d_wgrad's widths and channel blocks, restated, and what every block pair's plan has in common
+WGRAD_LAYER_PLANS_2D = {
+    "layer-80-144": dict(pixels=2706, widths=(96, 160), blocks_ca=(64, 32), blocks_cb=(128, 32), chunks=20, chunk_steps=3,
+                         pixels_in_last_stage=18),
+    "layer-up-144-80": dict(pixels=2706, widths=(96, 160), blocks_ca=(64, 32), blocks_cb=(128, 32), chunks=20,
+                            chunk_steps=3, pixels_in_last_stage=18),
+}
+assert set(WGRAD_PLANS_2D) == {c["name"] for c in WGRAD_CASES_2D}
+assert set(WGRAD_LAYER_PLANS_2D) == {c["name"] for c in WGRAD_LAYER_CASES_2D}
+# Measured on wgrad_data (tests/test_conv2d_wgrad_cpu.py prints them): largest abs-sum / share of non-zero entries of
+# dw; one_level at WGRAD_ONE_LEVEL_DENSITY / sqrt(P), the level pairs of WGRAD_LEVELS at density_for(P).
+#
+#       case                          P      one_level      x2_g2          x3_g1          x1_g3
+#       loop-tr-5x5s2-64-128          2706   10.0 / 0.678   9.020 / 0.920  9.012 / 0.882  9.012 / 0.880
+#       loop-tr-up-5x5s2-192-32       2706   11.0 / 0.677   9.014 / 0.924  9.018 / 0.889  9.008 / 0.880
+#       loop-narrowA-9x9s4-3-64       825    8.0 / 0.684    8.027 / 0.917  8.014 / 0.891  8.010 / 0.879
+#       loop-narrowA-up-9x9s4-64-3    825    9.0 / 0.679    8.018 / 0.920  9.010 / 0.884  8.012 / 0.885
+#       loop-8x8-5x5s1-256-256        2624   13.0 / 0.679   10.025 / 0.922 11.012 / 0.883 10.014 / 0.882
+#       one-chunk-23x23-3-32          1073   8.0 / 0.578    6.023 / 0.820  9.008 / 0.764  8.012 / 0.738
+#       row-1x3-128-64                21900  11.0 / 0.693   9.029 / 0.927  8.012 / 0.887  8.012 / 0.890
+#       col-4x1s2-32-64               8194   11.0 / 0.683   7.016 / 0.932  9.008 / 0.896  9.018 / 0.889
+#       even-4x2s2-32-64              70     9.0 / 0.663    8.016 / 0.914  8.010 / 0.836  7.004 / 0.865
+#       edges-p63-3x3-32-32           63     8.0 / 0.645    8.023 / 0.901  6.010 / 0.852  6.010 / 0.864
+#       edges-p64-3x3-32-32           64     7.0 / 0.645    8.020 / 0.900  6.012 / 0.865  6.012 / 0.850
+#       edges-p65-3x3-32-32           65     8.0 / 0.666    7.018 / 0.887  7.010 / 0.842  6.014 / 0.844
+#       layer-80-144                  2706   11.0 / 0.682   10.023 / 0.921 10.012 / 0.879 9.014 / 0.879
+#       layer-up-144-80               2706   11.0 / 0.682   9.027 / 0.923  10.010 / 0.884 11.006 / 0.882
+# (one-chunk: at 13 x 17 pixels most taps of a 23 x 23 kernel meet few pixels inside A and 0.39 of dw is non-zero;
+# 29 x 37 is the extent at which the one-level share is above a half.)
+
+
+_ALL_CASES = (PLANE_CASES + GRADIENT_CASES + IMPULSE_CASES + WGRAD_CASES_3D + WGRAD_CASES_2D + WGRAD_LAYER_CASES_2D)
+_BY_NAME = {c["name"]: c for c in _ALL_CASES}
+assert len(_BY_NAME) == len(_ALL_CASES)
