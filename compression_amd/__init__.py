@@ -15,6 +15,8 @@ from .ops.train_ops import scale_crop_patches, scale_crop_patches_reference  # n
 from .ops.video_ops import (pack_frames, pack_frames_reference, rgb_to_ycbcr, rgb_to_ycbcr_reference,  # noqa: F401
                             unpack_frames, unpack_frames_reference, ycbcr_to_rgb, ycbcr_to_rgb_reference)
 from .ops.vq_ops import ecvq_assign, ecvq_assign_reference, ecvq_counts  # noqa: F401
+from .ops.attention_ops import (gelu, gelu_reference, layer_norm, layer_norm_reference, window_attention,  # noqa: F401
+                                window_attention_reference)
 from .ops.lvac_ops import (PointBlocks, RahtTree, point_mlp_loss, point_mlp_loss_reference, raht_synthesize,  # noqa: F401
                            raht_synthesize_reference)
 from .ops.flow_ops import (gaussian_scale_space, gaussian_scale_space_reference, scale_space_predict,  # noqa: F401

@@ -372,10 +372,12 @@ void cnorm_launch_vec(const CnormPlan& plan, int dtype, unsigned blocks, hipStre
 #undef TFC_CNORM_CASE
 }
 
-int cnorm_validate(const char* name, int dtype, int64_t pixels, int64_t channels, float epsilon) {
+int cnorm_validate(const char* name, int dtype, int64_t pixels, int64_t channels, float epsilon, bool biased) {
   if (int rc = check_dtype(name, dtype)) return rc;
   if (pixels < 0) return fail("%s: pixels must be non-negative, got %lld", name, static_cast<long long>(pixels));
-  if (channels < 2 || channels > (1 << 24))
+  if (biased && (channels < 1 || channels > (1 << 24)))
+    return fail("%s: channels must be in [1, 2^24], got %lld", name, static_cast<long long>(channels));
+  if (!biased && (channels < 2 || channels > (1 << 24)))
     return fail("%s: channels must be at least 2 (the variance divides by channels - 1), got %lld", name,
                 static_cast<long long>(channels));
   if (!std::isfinite(epsilon) || epsilon < 0.f) return fail("%s: epsilon must be finite and non-negative", name);
@@ -389,22 +391,18 @@ int cnorm_cus() {
   return cus;
 }
 
-}  // namespace
-}  // namespace tfc
-
-extern "C" int tfc_channel_norm_forward(const void* x, const float* gamma, const float* beta, const void* residual,
-                                        void* y, int dtype, int64_t pixels, int64_t channels, float epsilon, int relu,
-                                        void* stream) {
-  using namespace tfc;
-  if (int rc = cnorm_validate("tfc_channel_norm_forward", dtype, pixels, channels, epsilon)) return rc;
+// Both norms: `biased` (layer norm) divides the sum of squares by C, ChannelNorm by C - 1; nothing else differs.
+int cnorm_forward(const char* name, const void* x, const float* gamma, const float* beta, const void* residual, void* y,
+                  int dtype, int64_t pixels, int64_t channels, float epsilon, int relu, bool biased, void* stream) {
+  if (int rc = cnorm_validate(name, dtype, pixels, channels, epsilon, biased)) return rc;
   if (pixels == 0) return 0;
-  if (!x || !y) return fail("tfc_channel_norm_forward: x and y must not be null");
+  if (!x || !y) return fail("%s: x and y must not be null", name);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int cus = cnorm_cus();
   CnormParams p = {};
   p.x = x; p.res = residual; p.y = y; p.gamma = gamma; p.beta = beta;
   p.C = static_cast<int>(channels);
-  p.eps = epsilon; p.cf = static_cast<float>(channels); p.cm1f = static_cast<float>(channels - 1);
+  p.eps = epsilon; p.cf = static_cast<float>(channels); p.cm1f = static_cast<float>(channels - (biased ? 0 : 1));
   p.relu = relu ? 1 : 0;
   // x + y beyond half the 256 MB Infinity Cache: y goes out non-temporal — the rule and the figure of the GDN
   // kernels (csrc/gdn_common.h, TFC_GDN_NT), inherited, not measured here.  TFC_CNORM_NT = 0 / 1: never / always.
@@ -433,23 +431,22 @@ extern "C" int tfc_channel_norm_forward(const void* x, const float* gamma, const
   return 0;
 }
 
-extern "C" int tfc_channel_norm_backward(const void* x, const void* g, const float* gamma, const float* beta, void* dx,
-                                         float* dgamma, float* dbeta, int dtype, int64_t pixels, int64_t channels,
-                                         float epsilon, int relu, void* stream) {
-  using namespace tfc;
-  if (int rc = cnorm_validate("tfc_channel_norm_backward", dtype, pixels, channels, epsilon)) return rc;
+int cnorm_backward(const char* name, const void* x, const void* g, const float* gamma, const float* beta, void* dx,
+                   float* dgamma, float* dbeta, int dtype, int64_t pixels, int64_t channels, float epsilon, int relu,
+                   bool biased, void* stream) {
+  if (int rc = cnorm_validate(name, dtype, pixels, channels, epsilon, biased)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (pixels == 0) {
     if (dgamma) TFC_HIP(hipMemsetAsync(dgamma, 0, sizeof(float) * channels, st));
     if (dbeta) TFC_HIP(hipMemsetAsync(dbeta, 0, sizeof(float) * channels, st));
     return 0;
   }
-  if (!x || !g || !dx) return fail("tfc_channel_norm_backward: x, g and dx must not be null");
+  if (!x || !g || !dx) return fail("%s: x, g and dx must not be null", name);
   const int cus = cnorm_cus();
   CnormParams p = {};
   p.x = x; p.g = g; p.y = dx; p.gamma = gamma; p.beta = beta;
   p.C = static_cast<int>(channels);
-  p.eps = epsilon; p.cf = static_cast<float>(channels); p.cm1f = static_cast<float>(channels - 1);
+  p.eps = epsilon; p.cf = static_cast<float>(channels); p.cm1f = static_cast<float>(channels - (biased ? 0 : 1));
   p.relu = relu ? 1 : 0;
   const CnormPlan plan = cnorm_plan(dtype, pixels, channels, {x, g, dx, gamma, beta});
   unsigned vblocks = 0, rblocks = 0;
@@ -480,4 +477,35 @@ extern "C" int tfc_channel_norm_backward(const void* x, const void* g, const flo
                        st, p.part, vparts + rparts, p.C, dgamma, dbeta);
   TFC_HIP(hipGetLastError());
   return 0;
+}
+
+}  // namespace
+}  // namespace tfc
+
+extern "C" int tfc_channel_norm_forward(const void* x, const float* gamma, const float* beta, const void* residual,
+                                        void* y, int dtype, int64_t pixels, int64_t channels, float epsilon, int relu,
+                                        void* stream) {
+  return tfc::cnorm_forward("tfc_channel_norm_forward", x, gamma, beta, residual, y, dtype, pixels, channels, epsilon,
+                            relu, false, stream);
+}
+
+extern "C" int tfc_channel_norm_backward(const void* x, const void* g, const float* gamma, const float* beta, void* dx,
+                                         float* dgamma, float* dbeta, int dtype, int64_t pixels, int64_t channels,
+                                         float epsilon, int relu, void* stream) {
+  return tfc::cnorm_backward("tfc_channel_norm_backward", x, g, gamma, beta, dx, dgamma, dbeta, dtype, pixels, channels,
+                             epsilon, relu, false, stream);
+}
+
+extern "C" int tfc_layer_norm_forward(const void* x, const float* gamma, const float* beta, const void* residual,
+                                      void* y, int dtype, int64_t pixels, int64_t channels, float epsilon,
+                                      void* stream) {
+  return tfc::cnorm_forward("tfc_layer_norm_forward", x, gamma, beta, residual, y, dtype, pixels, channels, epsilon, 0,
+                            true, stream);
+}
+
+extern "C" int tfc_layer_norm_backward(const void* x, const void* g, const float* gamma, const float* beta, void* dx,
+                                       float* dgamma, float* dbeta, int dtype, int64_t pixels, int64_t channels,
+                                       float epsilon, void* stream) {
+  return tfc::cnorm_backward("tfc_layer_norm_backward", x, g, gamma, beta, dx, dgamma, dbeta, dtype, pixels, channels,
+                             epsilon, 0, true, stream);
 }

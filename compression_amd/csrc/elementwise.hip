@@ -222,3 +222,69 @@ extern "C" int tfc_index_prepare(const void* indexes, int dtype, int32_t* out, i
   TFC_HIP(hipGetLastError());
   return 0;
 }
+
+// Exact GELU (the MLP of a Swin block), y = 0.5 x (1 + erf(x / sqrt 2)), and its backward
+// dx = g (0.5 (1 + erf(x / sqrt 2)) + x exp(-x^2 / 2) / sqrt(2 pi)), in float32.  One kernel each: a thread takes
+// 16-byte granules (`groups` of them, 0 where a base is not 16-byte aligned), the elements behind the last whole
+// granule go one by one in the same launch.
+namespace tfc {
+namespace {
+
+template <bool BWD>
+__device__ inline float gelu_one(float x, float g) {
+  const float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752f));
+  if (!BWD) return x * cdf;
+  return g * fmaf(x * 0.3989422804014327f, expf(-0.5f * x * x), cdf);
+}
+
+template <bool BF16, bool BWD>
+__global__ void __launch_bounds__(256) gelu_kernel(const void* x, const void* g, void* y, long long groups,
+                                                   long long count) {
+  constexpr int EPG = BF16 ? 8 : 4;
+  const long long stride = static_cast<long long>(gridDim.x) * 256;
+  const long long first = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+  for (long long i = first; i < groups; i += stride) {
+    float v[EPG], gv[EPG];
+    unpack<BF16>(static_cast<const u32x4*>(x)[i], v);
+    if (BWD) unpack<BF16>(static_cast<const u32x4*>(g)[i], gv);
+#pragma unroll
+    for (int e = 0; e < EPG; ++e) v[e] = gelu_one<BWD>(v[e], BWD ? gv[e] : 0.f);
+    static_cast<u32x4*>(y)[i] = repack<BF16>(v);
+  }
+  for (long long i = groups * EPG + first; i < count; i += stride)
+    store<BF16>(y, i, gelu_one<BWD>(load<BF16>(x, i), BWD ? load<BF16>(g, i) : 0.f));
+}
+
+int gelu_launch(const char* name, const void* x, const void* g, void* y, int dtype, int64_t count, bool bwd,
+                void* stream) {
+  if (int rc = check_dtype(name, dtype)) return rc;
+  if (count < 0) return fail("%s: count must be non-negative, got %lld", name, static_cast<long long>(count));
+  if (count == 0) return 0;
+  if (!x || !y || (bwd && !g)) return fail("%s: null tensor", name);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  bool aligned = reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(y) % 16 == 0;
+  if (bwd) aligned = aligned && reinterpret_cast<uintptr_t>(g) % 16 == 0;
+  const long long per = dtype == 1 ? 8 : 4;
+  const long long groups = aligned ? count / per : 0;
+  const long long items = std::max<long long>(groups, count - groups * per);
+  const unsigned blocks = static_cast<unsigned>(std::max<long long>(1, std::min<long long>(ceil_div(items, 1024), 4096)));
+  KernelTimer timer(bwd ? "gelu_backward" : "gelu_forward", st);
+  const long long n = count;
+  if (dtype == 1 && bwd) hipLaunchKernelGGL((gelu_kernel<true, true>), dim3(blocks), dim3(256), 0, st, x, g, y, groups, n);
+  else if (dtype == 1) hipLaunchKernelGGL((gelu_kernel<true, false>), dim3(blocks), dim3(256), 0, st, x, g, y, groups, n);
+  else if (bwd) hipLaunchKernelGGL((gelu_kernel<false, true>), dim3(blocks), dim3(256), 0, st, x, g, y, groups, n);
+  else hipLaunchKernelGGL((gelu_kernel<false, false>), dim3(blocks), dim3(256), 0, st, x, g, y, groups, n);
+  TFC_HIP(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+}  // namespace tfc
+
+extern "C" int tfc_gelu_forward(const void* x, void* y, int dtype, int64_t count, void* stream) {
+  return tfc::gelu_launch("tfc_gelu_forward", x, nullptr, y, dtype, count, false, stream);
+}
+
+extern "C" int tfc_gelu_backward(const void* x, const void* g, void* dx, int dtype, int64_t count, void* stream) {
+  return tfc::gelu_launch("tfc_gelu_backward", x, g, dx, dtype, count, true, stream);
+}

@@ -1183,6 +1183,56 @@ int tfc_scctx_params(int pass, const float* y, float* y_hat, const float* psi, c
 int tfc_scctx_place(int pass, const float* sym, const float* mu, float* y_hat, int64_t batch, int64_t hl, int64_t wl,
                     int m, int cg, int mg, void* stream);
 
+/* Shifted-window attention (the attention of a Swin block; "Transformer-based Transform Coding", Zhu, Yang and Cohen,
+ * ICLR 2022).  The definition is this library's own; parity with anyone's checkpoints is not pinned.
+ *   qkv DEV [batch, height, width, 3 C] dtype (0 f32, 1 bf16), C = heads * head_dim; channel which * C + head *
+ *   head_dim + j holds q (which = 0), k (1), v (2).  table DEV float32 [heads, (2 ws - 1)^2].  out DEV [batch, height,
+ *   width, C] dtype, channel head * head_dim + j.  ws = window, s = shift (0 or ws / 2).
+ * Padded grid: Hp = ceil(height / ws) ws, Wp likewise.  Window (wy, wx), token (ty, tx) sits at rolled coordinate
+ * r = (wy ws + ty, wx ws + tx); its source coordinate is (yp, xp) = ((r_y + s) mod Hp, (r_x + s) mod Wp); it is VALID
+ * iff yp < height and xp < width; its wrap flags are (r_y + s >= Hp, r_x + s >= Wp).
+ * Per head, for a valid query i and the keys j of the same window:
+ *   S_ij = head_dim^-1/2 q_i . k_j + table[head, (ty_i - ty_j + ws - 1) (2 ws - 1) + (tx_i - tx_j + ws - 1)]
+ * j takes part iff it is valid and has the same two wrap flags as i; every other j has weight exactly 0 (it is
+ * excluded, not given a large negative score).  P_i = softmax over the j that take part; out_i = sum_j P_ij v_j,
+ * written at (yp, xp).  Invalid positions are neither read nor written; no padded, rolled or partitioned tensor is
+ * made.  The definition is applied literally when Hp == ws too.
+ * float32: products as float32 fmaf chains, softmax in float32.  bf16: both products on the bf16 MFMA with float32
+ * accumulation, softmax in float32, exp(S - max) rounded to bf16 before P.V, the row sum from the unrounded values, out
+ * rounded once.  A window's output depends on that window's tokens and the table only: it is bit-identical whatever
+ * else is in the image or the batch.
+ * window in {4, 8}, head_dim in {16, 32}, heads >= 1, batch, height, width >= 1; qkv and out 16-byte aligned. */
+int tfc_window_attention_forward(const void* qkv, const float* table, void* out, int dtype, int64_t batch,
+                                 int64_t height, int64_t width, int heads, int head_dim, int window, int shift,
+                                 void* stream);
+/* Its backward, deterministic, S and P recomputed from qkv.  dout = dL/dout DEV [batch, height, width, C] dtype.  With
+ * dP = dout V^T and dS = P o (dP - rowsum(dP o P)):
+ *   dV = P^T dout,   dQ = head_dim^-1/2 dS K,   dK = head_dim^-1/2 dS^T Q      -> dqkv DEV [batch, height, width, 3 C] dtype
+ *   dtable[head, rel] = sum over batches, windows and pairs of dS              -> dtable DEV float32, as table
+ * dtable is summed through per-workgroup partials merged in a fixed order (no float atomics): two calls give the same
+ * bits.  dqkv or dtable may be NULL: that gradient is not computed. */
+int tfc_window_attention_backward(const void* qkv, const float* table, const void* dout, void* dqkv, float* dtable,
+                                  int dtype, int64_t batch, int64_t height, int64_t width, int heads, int head_dim,
+                                  int window, int shift, void* stream);
+
+/* Layer normalisation over the last axis, on the ChannelNorm kernels (csrc/channel_norm.hip) with the BIASED variance:
+ *   mean_p = sum_c x[p,c] / C;   var_p = sum_c (x[p,c] - mean_p)^2 / C
+ *   y[p,c] = (x[p,c] - mean_p) * rsqrt(var_p + epsilon) * gamma[c] + beta[c];   residual != NULL: y += residual[p,c].
+ * Arguments as tfc_channel_norm_forward (no ReLU); channels >= 1. */
+int tfc_layer_norm_forward(const void* x, const float* gamma, const float* beta, const void* residual, void* y,
+                           int dtype, int64_t pixels, int64_t channels, float epsilon, void* stream);
+/* Its backward without the residual (whose gradient is g itself), xhat = (x - mean) rstd:
+ *   dx = rstd (g gamma - sum_c(g gamma) / C - xhat sum_c(g gamma xhat) / C);  dgamma[c] = sum_p g xhat;  dbeta[c] = sum_p g
+ * dgamma, dbeta DEV float32 [channels] or NULL, summed in a fixed order as tfc_channel_norm_backward does. */
+int tfc_layer_norm_backward(const void* x, const void* g, const float* gamma, const float* beta, void* dx,
+                            float* dgamma, float* dbeta, int dtype, int64_t pixels, int64_t channels, float epsilon,
+                            void* stream);
+
+/* Exact GELU, y = 0.5 x (1 + erf(x / sqrt 2)), `count` values of dtype (0 f32, 1 bf16), computed in float32. */
+int tfc_gelu_forward(const void* x, void* y, int dtype, int64_t count, void* stream);
+/* Its backward: dx = g (0.5 (1 + erf(x / sqrt 2)) + x exp(-x^2 / 2) / sqrt(2 pi)). */
+int tfc_gelu_backward(const void* x, const void* g, void* dx, int dtype, int64_t count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
