@@ -43,7 +43,7 @@
 
 #include "../../include/tfc_hip.h"
 #include "bf16_io.h"
-#include "common.h"
+#include "launch.h"
 #include "unit_sum.h"
 
 namespace tfc {
@@ -384,13 +384,6 @@ int cnorm_validate(const char* name, int dtype, int64_t pixels, int64_t channels
   return 0;
 }
 
-int cnorm_cus() {
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  return cus;
-}
-
 // Both norms: `biased` (layer norm) divides the sum of squares by C, ChannelNorm by C - 1; nothing else differs.
 int cnorm_forward(const char* name, const void* x, const float* gamma, const float* beta, const void* residual, void* y,
                   int dtype, int64_t pixels, int64_t channels, float epsilon, int relu, bool biased, void* stream) {
@@ -398,17 +391,17 @@ int cnorm_forward(const char* name, const void* x, const float* gamma, const flo
   if (pixels == 0) return 0;
   if (!x || !y) return fail("%s: x and y must not be null", name);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int cus = cnorm_cus();
+  const int cus = device_cus();
   CnormParams p = {};
   p.x = x; p.res = residual; p.y = y; p.gamma = gamma; p.beta = beta;
   p.C = static_cast<int>(channels);
   p.eps = epsilon; p.cf = static_cast<float>(channels); p.cm1f = static_cast<float>(channels - (biased ? 0 : 1));
   p.relu = relu ? 1 : 0;
-  // x + y beyond half the 256 MB Infinity Cache: y goes out non-temporal — the rule and the figure of the GDN
-  // kernels (csrc/gdn_common.h, TFC_GDN_NT), inherited, not measured here.  TFC_CNORM_NT = 0 / 1: never / always.
-  static const int nt_env = [] { const char* e = std::getenv("TFC_CNORM_NT"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
+  // x + y beyond the cache: y goes out non-temporal — the rule and the figure of the GDN kernels (TFC_GDN_NT),
+  // inherited, not measured here.  TFC_CNORM_NT = 0 / 1: never / always.
+  static const int nt_env = env_switch("TFC_CNORM_NT");
   const long long bytes = pixels * channels * dtype_bytes(dtype);
-  p.nt = nt_env >= 0 ? nt_env : (2 * bytes > (128ll << 20) ? 1 : 0);
+  p.nt = beyond_cache(2 * bytes, nt_env);
   const CnormPlan plan = cnorm_plan(dtype, pixels, channels, {x, y, residual, gamma, beta});
   KernelTimer timer("channel_norm_forward", st);
   long long done = 0;
@@ -442,7 +435,7 @@ int cnorm_backward(const char* name, const void* x, const void* g, const float* 
     return 0;
   }
   if (!x || !g || !dx) return fail("%s: x, g and dx must not be null", name);
-  const int cus = cnorm_cus();
+  const int cus = device_cus();
   CnormParams p = {};
   p.x = x; p.g = g; p.y = dx; p.gamma = gamma; p.beta = beta;
   p.C = static_cast<int>(channels);

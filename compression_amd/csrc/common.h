@@ -73,10 +73,7 @@ struct BlockCache {
   std::vector<hipEvent_t> events;                           // recycled
   size_t cached = 0;
   size_t limit;
-  BlockCache() {
-    const char* e = std::getenv("TFC_CACHE_LIMIT_MB");
-    limit = static_cast<size_t>(e ? std::atoll(e) : 65536) << 20;
-  }
+  BlockCache();                                             // runtime.hip: the limit is TFC_CACHE_LIMIT_MB's
   static BlockCache& get() {
     static BlockCache* c = new BlockCache;                  // leaked: released blocks may arrive during exit
     return *c;

@@ -753,10 +753,7 @@ extern "C" int tfc_debug_conv3_waits(unsigned long long* out, int wgs) {
 }
 #endif
 
-static int conv3_gen() {
-  const char* e = std::getenv("TFC_CONV_GEN");
-  return e ? std::atoi(e) : 3;
-}
+static int conv3_gen() { return env_int("TFC_CONV_GEN", 3); }
 
 int run_conv3(const __bf16* x, const float* w, const float* bias, __bf16* y, ConvGeom c, PackGeom g,
               unsigned long long key, hipStream_t st) {
@@ -772,7 +769,7 @@ int run_conv3(const __bf16* x, const float* w, const float* bias, __bf16* y, Con
   // Since its workgroups take their blocks in XCD order (xcd_order: neighbouring blocks' patches meet in one L2) it is
   // ahead on the wide stride-2 maps too: 6.87-6.98 -> 6.32-6.37 ms at 384x256, 1.73-1.76 -> 1.57-1.61 at 192x128 (same
   // box, alternating; TFC_CONV_DOWN3=0 keeps those on the second generation).
-  static const bool down3 = [] { const char* e = std::getenv("TFC_CONV_DOWN3"); return !(e && e[0] == '0'); }();
+  static const bool down3 = env_switch("TFC_CONV_DOWN3") != 0;
   const bool wide_down = down3 && !g.up && c.sd == 2 && c.xcd;
   if (conv3_gen() < 4 && !(g.up && c.su == 2) && !small_down && !wide_down) return -1;
   {
@@ -831,9 +828,6 @@ int run_conv3(const __bf16* x, const float* w, const float* bias, __bf16* y, Con
     });
     if (rc) return rc;
   }
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   KernelTimer timer("conv2d", st);
   const int tap_counts[4] = {25, 9, 6, 4};
   for (int ntv : tap_counts) {
@@ -862,7 +856,7 @@ int run_conv3(const __bf16* x, const float* w, const float* bias, __bf16* y, Con
     }
     d.obias = static_cast<int>(lds_all);
     lds_all += 1024;
-    if (lds_all + 32768 <= 160 * 1024) {
+    if (lds_all + 32768 <= kLdsBytesPerCu) {
       d.ostage = static_cast<int>(lds_all);
       lds_all += 32768;
     } else if (resident && wbufs >= 32768) {
@@ -872,24 +866,20 @@ int run_conv3(const __bf16* x, const float* w, const float* bias, __bf16* y, Con
     } else {
       return -1;
     }
-    if (lds_all > 160 * 1024) return -1;
+    if (lds_all > kLdsBytesPerCu) return -1;
     // One workgroup per block and group.  (A grid of one workgroup per CU, each taking every W-th block, is the same
     // speed alone on the chip — round 6, with the cheaper epilogue: 2 % / 6 % ahead on the stride-2 / transposed layer —
     // but keeps the kernels of other steps in flight out of its CUs: C4 51.6 instead of 47.6 ms per step,
     // profiles/r03_notes.md.)
-    {
-      static const int nt_env = [] { const char* e = std::getenv("TFC_CONV_NT"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
-      const long long out_bytes = c.N * c.OH * c.OW * c.Cout * (c.out_f32 ? 4 : 2);
-      c.nt_out = nt_env >= 0 ? nt_env : (out_bytes > (128ll << 20) ? 1 : 0);
-    }
+    static const int nt_env = env_switch("TFC_CONV_NT");
+    c.nt_out = beyond_cache(c.N * c.OH * c.OW * c.Cout * (c.out_f32 ? 4 : 2), nt_env);
     const long long nblk = c.N * d.BXn * d.BYn * d.gcount;
-    if (nblk >= (1ll << 31)) return fail("tfc_conv2d: problem too large for one launch");
+    if (nblk > kMaxGridX) return fail("tfc_conv2d: problem too large for one launch");
     const dim3 grid(static_cast<unsigned>(nblk));
 #define TFC_CONV3_LAUNCH_G(NT, CHV, NCHV, NPGV, G, F32)                                                    \
     do {                                                                                                   \
-      TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_bf16_kernel<NT, CHV, NCHV, NPGV, G, F32>),  \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_all)));     \
-      hipLaunchKernelGGL((conv3_bf16_kernel<NT, CHV, NCHV, NPGV, G, F32>), grid, dim3(256), lds_all, st, x, packed.p, bias, y, c, d); \
+      if (int rc = launch(&conv3_bf16_kernel<NT, CHV, NCHV, NPGV, G, F32>, grid, dim3(256), lds_all, st, x, packed.p, bias, y, c, d)) \
+        return rc;                                                                                         \
     } while (0)
 #define TFC_CONV3_LAUNCH(NT, CHV, NCHV, NPGV)                                                              \
     do {                                                                                                   \
@@ -910,7 +900,6 @@ int run_conv3(const __bf16* x, const float* w, const float* bias, __bf16* y, Con
 #undef TFC_CONV3_LAUNCH
 #undef TFC_CONV3_LAUNCH_G
   }
-  TFC_HIP(hipGetLastError());
   return 0;
 }
 

@@ -1,6 +1,7 @@
-// What the convolution units share.  First the device helpers signal_conv3d.hip and signal_conv_backward.hip use too;
-// then the 2-D forward layer's call, its routes, the implicit GEMM's geometry and the cache of packed weights, for
-// signal_conv.hip and conv_gemm3.hip.  State lives in ONE unit: the cache and the thread's next key in signal_conv.hip.
+// What the convolution units share.  First the device helpers and the float32 path's split and chunk loop, which
+// signal_conv3d.hip and signal_conv_backward.hip use too; then the 2-D forward layer's call, its routes, the implicit
+// GEMM's geometry and the cache of packed weights, for signal_conv.hip and conv_gemm3.hip.  State and the shared kernels
+// live in ONE unit: the cache, the thread's next key, conv_pack_kernel and conv_split_x_kernel in signal_conv.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,7 +12,7 @@
 
 #include "../../include/tfc_hip.h"
 #include "bf16_io.h"
-#include "common.h"
+#include "launch.h"
 #include "gdn_params.h"
 
 namespace tfc {
@@ -50,9 +51,35 @@ __device__ inline float split_plane(float a, int plane) {
 // bytes of input planes per chunk of images, for the rank-2 and the rank-3 float32 path (TFC_CONV_F32_CHUNK_BYTES: the
 // tests run several chunks at a small shape; read per call)
 inline size_t conv_f32_chunk_bytes() {
-  const char* e = std::getenv("TFC_CONV_F32_CHUNK_BYTES");
+  const char* e = env_str("TFC_CONV_F32_CHUNK_BYTES");
   const long long v = e ? std::atoll(e) : 0;
   return v > 0 ? static_cast<size_t>(v) : size_t{2} << 30;
+}
+
+// conv_split_x_kernel (signal_conv.hip): x float32 [pixels, C] -> xs, its six bfloat16 planes [pixels, 6 C]; C % 8 == 0
+void launch_conv_split_x(const float* x, long long pixels, int C, __bf16* xs, hipStream_t st);
+
+// The float32 path's walk over a batch x [n, pix_image, cin], for every rank.  The planes are 3x the input's bytes, so the
+// images go through in chunks of ~2 GB of planes (bmshj2018's first 192 -> 192 layer at 128 x 768x512 would need 29 GB at
+// once): each chunk is split under the timer `label`, then body(n0, images, planes) convolves images n0 .. n0 + images.
+template <typename Body>
+int conv_f32_chunks(const char* name, const char* label, const float* x, int64_t n, long long pix_image, int64_t cin,
+                    hipStream_t st, Body&& body) {
+  const size_t plane_bytes = static_cast<size_t>(pix_image) * 6 * cin * sizeof(__bf16);
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, static_cast<int64_t>(conv_f32_chunk_bytes() / std::max<size_t>(plane_bytes, 1))));
+  if (ceil_div(pix_image * chunk * (cin / 8), 256) > kMaxGridX) return fail("%s: problem too large for one launch", name);
+  DevBuf xs;
+  TFC_HIP(xs.alloc(plane_bytes * static_cast<size_t>(chunk), st));
+  for (int64_t n0 = 0; n0 < n; n0 += chunk) {
+    const int64_t images = std::min<int64_t>(chunk, n - n0);
+    {
+      KernelTimer timer(label, st);
+      launch_conv_split_x(x + n0 * pix_image * cin, pix_image * images, static_cast<int>(cin), xs.as<__bf16>(), st);
+      TFC_HIP(hipGetLastError());
+    }
+    if (int rc = body(n0, images, xs.as<__bf16>())) return rc;
+  }
+  return 0;
 }
 
 // One 2-D forward call, as the C ABI entries state it and as a route states a nested one.

@@ -23,7 +23,7 @@
 
 #include "../../include/tfc_hip.h"
 #include "bf16_io.h"
-#include "common.h"
+#include "bits_common.h"
 #include "laplace_tail.h"
 #include "reduce_rows.h"
 
@@ -140,7 +140,7 @@ __global__ void __launch_bounds__(512) factorized_forward_kernel(BitsParams p) {
     if (p.log_prob) p.log_prob[unit * p.elems + e] = lp;
     acc += lp;
   }
-  // block sum in a fixed order: wave shuffles, then lane 0 of each wave through LDS
+  // block sum in a fixed order: wave shuffles, then lane 0 of each wave through LDS (its own copy: bits_common.h)
   __shared__ float wsum[16];
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) acc += __shfl_down(acc, d, 64);
@@ -151,15 +151,6 @@ __global__ void __launch_bounds__(512) factorized_forward_kernel(BitsParams p) {
     for (int w = 0; w < (p.threads + 63) / 64; ++w) s += wsum[w];
     p.partial[blockIdx.x] = s;
   }
-}
-
-__global__ void factorized_bits_reduce_kernel(const float* partial, int blocks_per_unit, long long units,
-                                              float* bits) {
-  const long long u = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x;
-  if (u >= units) return;
-  float s = 0.f;
-  for (int b = 0; b < blocks_per_unit; ++b) s += partial[u * blocks_per_unit + b];
-  bits[u] = s * -1.4426950408889634f;          // / -ln 2
 }
 
 // log sigmoid(x) and log sigmoid(-x) from one exp and one log: they differ by x exactly
@@ -312,13 +303,8 @@ int plan_blocks(long long units, long long elems, int channels, int* threads, in
   int t = (512 / channels) * channels;             // largest multiple of channels <= 512
   while (t > 256 && (t - channels) >= 192) t -= channels;   // keep blocks around 192..256 threads
   *threads = t;
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const long long rows = ceil_div(elems, t);
-  long long want = ceil_div(static_cast<long long>(cus) * 8, std::max<long long>(units, 1));
-  *blocks_per_unit = static_cast<int>(std::max<long long>(1, std::min<long long>(rows, want)));
-  if (units * *blocks_per_unit >= (1ll << 31)) return fail("tfc_factorized_bits: problem too large");
+  *blocks_per_unit = bits_blocks_per_unit(units, elems, t);
+  if (units * *blocks_per_unit > kMaxGridX) return fail("tfc_factorized_bits: problem too large");
   return 0;
 }
 
@@ -332,8 +318,7 @@ int run_forward(BitsParams p, float* bits, hipStream_t st) {
     hipLaunchKernelGGL((factorized_forward_kernel<T, K, W>), dim3(static_cast<unsigned>(p.units * p.blocks_per_unit)),
                        dim3(p.threads), 0, st, p);
   }
-  hipLaunchKernelGGL(factorized_bits_reduce_kernel, dim3(static_cast<unsigned>(ceil_div(p.units, 256))), dim3(256),
-                     0, st, p.partial, p.blocks_per_unit, p.units, bits);
+  launch_bits_reduce(p.partial, p.blocks_per_unit, p.units, bits, st);
   TFC_HIP(hipGetLastError());
   return 0;
 }
@@ -349,17 +334,8 @@ int run_backward(BitsParams p, float* dparams, hipStream_t st) {
   const size_t lds = sizeof(float) * p.threads * L::kParams;
   {
     KernelTimer timer("factorized_backward", st);
-    if (p.threads <= 256) {
-      TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&factorized_backward_kernel<T, K, W, 256>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-      hipLaunchKernelGGL((factorized_backward_kernel<T, K, W, 256>), dim3(static_cast<unsigned>(blocks)),
-                         dim3(p.threads), lds, st, p);
-    } else {
-      TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&factorized_backward_kernel<T, K, W, 512>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-      hipLaunchKernelGGL((factorized_backward_kernel<T, K, W, 512>), dim3(static_cast<unsigned>(blocks)),
-                         dim3(p.threads), lds, st, p);
-    }
+    const auto kernel = p.threads <= 256 ? &factorized_backward_kernel<T, K, W, 256> : &factorized_backward_kernel<T, K, W, 512>;
+    if (int rc = launch(kernel, dim3(static_cast<unsigned>(blocks)), dim3(p.threads), lds, st, p)) return rc;
   }
   launch_sum_rows(p.dpartial, blocks, n, n, dparams, st);   // dparams += block partials, fixed order
   TFC_HIP(hipGetLastError());

@@ -619,20 +619,15 @@ __global__ void __launch_bounds__(256, (pg_wgs<T, KT>())) gdn_param_grad_kernel(
 template <typename T, int KT>
 int launch_param_grad(GdnParams p, float* dgamma, float* dbeta, hipStream_t st) {
   constexpr int C = KT * 32;
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   const long long stages = ceil_div(p.pixels, static_cast<long long>(PG_PIX));
-  const int blocks = static_cast<int>(std::max<long long>(1, std::min<long long>(stages, pg_wgs<T, KT>() * cus)));
+  const int blocks = static_cast<int>(std::max<long long>(1, std::min<long long>(stages, pg_wgs<T, KT>() * device_cus())));
   const size_t lds = sizeof(T) == 2 ? (TFC_GDN_PG_TR != 0 && KT <= 6 ? sizeof(unsigned short) * 2 * PG_PIX * pg_row_elems<C>()
                                                            : sizeof(unsigned short) * 2 * C * PG_STRIDE)
                                     : sizeof(float) * 2 * PG_PIX * C;
   DevBuf partial;
   TFC_HIP(partial.alloc(sizeof(float) * static_cast<size_t>(blocks) * (C * C + C), st));
   KernelTimer timer("gdn_backward_params", st);   // gradient kernel + the reduction of its partials
-  TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gdn_param_grad_kernel<T, KT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-  hipLaunchKernelGGL((gdn_param_grad_kernel<T, KT>), dim3(blocks), dim3(256), lds, st, p, partial.as<float>());
+  if (int rc = launch(&gdn_param_grad_kernel<T, KT>, dim3(blocks), dim3(256), lds, st, p, partial.as<float>())) return rc;
   // dgamma / dbeta += the block partials, summed in a fixed order
   launch_sum_rows(partial.as<float>(), blocks, C * C + C, C * C, dgamma, st);
   launch_sum_rows(partial.as<float>() + C * C, blocks, C * C + C, C, dbeta, st);
@@ -642,11 +637,8 @@ int launch_param_grad(GdnParams p, float* dgamma, float* dbeta, hipStream_t st) 
 
 template <int KT, bool PLAIN>
 int launch_gdn_bwd_fused_variant(GdnParams p, hipStream_t st) {
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   const long long want = ceil_div(p.tiles, TFC_GDN_BWD_THREADS / 64);
-  const unsigned blocks = static_cast<unsigned>(std::max<long long>(1, std::min<long long>(want, cus)));
+  const unsigned blocks = static_cast<unsigned>(std::max<long long>(1, std::min<long long>(want, device_cus())));
   constexpr int IMG = KT * KT * 2 * 64;
   const size_t lds = sizeof(bf16x8) * 2 * IMG + sizeof(float) * KT * 32;
   DevBuf image;
@@ -658,11 +650,7 @@ int launch_gdn_bwd_fused_variant(GdnParams p, hipStream_t st) {
                      KT * 32, 1, image.as<bf16x8>() + IMG);
   p.image = image.p;
   KernelTimer timer("gdn_backward_fused", st);
-  TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gdn_bwd_fused_bf16_kernel<KT, PLAIN>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-  hipLaunchKernelGGL((gdn_bwd_fused_bf16_kernel<KT, PLAIN>), dim3(blocks), dim3(TFC_GDN_BWD_THREADS), lds, st, p);
-  TFC_HIP(hipGetLastError());
-  return 0;
+  return launch(&gdn_bwd_fused_bf16_kernel<KT, PLAIN>, dim3(blocks), dim3(TFC_GDN_BWD_THREADS), lds, st, p);
 }
 
 template <int KT>

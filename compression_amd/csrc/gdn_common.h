@@ -33,7 +33,7 @@
 
 #include "../../include/tfc_hip.h"
 #include "bf16_io.h"
-#include "common.h"
+#include "launch.h"
 
 namespace tfc {
 
@@ -540,14 +540,11 @@ static __global__ void gdn_prep_f32_kernel(const float* gamma, const float* beta
 // DTYPES: bit 0 = instantiate the float32 kernels, bit 1 = the bfloat16 ones.
 template <int KT, int MODE, bool PLAIN, int DTYPES, bool GEN = false>
 int launch_gdn_variant(GdnParams p, int dtype, hipStream_t st) {
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   // bf16: 8 waves (2 per SIMD, <= 256 VGPRs each); f32: 4 waves so that the 96 x + 96
   // accumulator registers fit the 512-entry unified file without spilling.
   const int waves_per_block = dtype == 1 ? 8 : 4;
   const long long want = ceil_div(p.tiles, waves_per_block);
-  const unsigned blocks = static_cast<unsigned>(std::max<long long>(1, std::min<long long>(want, cus)));
+  const unsigned blocks = static_cast<unsigned>(std::max<long long>(1, std::min<long long>(want, device_cus())));
   const char* label = MODE == MODE_FWD ? "gdn_forward" : MODE == MODE_BWD_T ? "gdn_backward_t" : "gdn_backward_dx";
   const int transposed = MODE == MODE_BWD_DX;
   DevBuf image;
@@ -564,16 +561,11 @@ int launch_gdn_variant(GdnParams p, int dtype, hipStream_t st) {
       p.image = image.p;
     }
     KernelTimer timer(label, st);
-    // x + y beyond half the 256 MB Infinity Cache: y's lines go out non-temporal (TFC_GDN_NT = 0 / 1: never / always)
-    {
-      static const int nt_env = [] { const char* e = std::getenv("TFC_GDN_NT"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
-      p.nt_store = nt_env >= 0 ? nt_env : (static_cast<long long>(p.pixels) * KT * 32 * 4 > (128ll << 20) ? 1 : 0);
-    }
+    // x + y beyond the cache: y's lines go out non-temporal (TFC_GDN_NT = 0 / 1: never / always)
+    static const int nt_env = env_switch("TFC_GDN_NT");
+    p.nt_store = beyond_cache(static_cast<long long>(p.pixels) * KT * 32 * 4, nt_env);
     const size_t lds_lines = TFC_GDN_LINES != 0 && MODE == MODE_FWD && KT <= 7 ? ((lds + 15) & ~size_t{15}) + static_cast<size_t>(waves_per_block) * 4096 : lds;
-    TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gdn_fwd_bf16_kernel<KT, MODE, PLAIN, GEN>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_lines)));
-    hipLaunchKernelGGL((gdn_fwd_bf16_kernel<KT, MODE, PLAIN, GEN>), dim3(blocks), dim3(64 * waves_per_block), lds_lines,
-                       st, p);
+    return launch(&gdn_fwd_bf16_kernel<KT, MODE, PLAIN, GEN>, dim3(blocks), dim3(64 * waves_per_block), lds_lines, st, p);
    } else {
     return fail("tfc_gdn: bfloat16 kernel not built for this configuration");
    }
@@ -590,16 +582,11 @@ int launch_gdn_variant(GdnParams p, int dtype, hipStream_t st) {
         p.image = image.p;
       }
       KernelTimer timer(label, st);
-      TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gdn_fwd_f32_kernel<KT, MODE, PLAIN, GEN>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-      hipLaunchKernelGGL((gdn_fwd_f32_kernel<KT, MODE, PLAIN, GEN>), dim3(blocks), dim3(64 * waves_per_block), lds,
-                         st, p);
+      return launch(&gdn_fwd_f32_kernel<KT, MODE, PLAIN, GEN>, dim3(blocks), dim3(64 * waves_per_block), lds, st, p);
     } else {
       return fail("tfc_gdn: float32 path supports up to 192 channels (Gamma must fit in LDS)");
     }
   }
-  TFC_HIP(hipGetLastError());
-  return 0;
 }
 
 template <int KT, int MODE, int DTYPES = 3>

@@ -36,7 +36,7 @@
 
 #include "../../include/tfc_hip.h"
 #include "bf16_io.h"
-#include "common.h"
+#include "launch.h"
 #include "unit_sum.h"
 
 namespace tfc {
@@ -260,11 +260,8 @@ LpipsPlan lpips_plan(int dtype, long long C, std::initializer_list<const void*> 
 
 // Workgroups per image: two steps per wave where there are enough, about 32 waves per CU over all images at most.
 int lpips_blocks(const LpipsPlan& plan, long long N, long long P) {
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   const long long steps = plan.vec ? ceil_div(P, 64 >> plan.lpr_log2) : P;
-  const long long cap = std::max<long long>(1, 8ll * cus / N);
+  const long long cap = std::max<long long>(1, 8ll * device_cus() / N);
   return static_cast<int>(std::max<long long>(1, std::min<long long>(ceil_div(steps, 2 * kLpWaves), cap)));
 }
 

@@ -20,7 +20,7 @@
 
 #include "../../include/tfc_hip.h"
 #include "bf16_io.h"
-#include "common.h"
+#include "bits_common.h"
 #include "laplace_tail.h"
 
 namespace tfc {
@@ -80,7 +80,7 @@ __global__ void __launch_bounds__(kThreads) noisy_normal_forward_kernel(NnParams
     if (p.tail_mass > 0.f) lp = tail_mix(lp, v, p.tail_mass);
     acc += lp;
   }
-  __shared__ float wsum[kThreads / 64];
+  __shared__ float wsum[kThreads / 64];              // the block sum: its own copy (bits_common.h says why)
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) acc += __shfl_down(acc, d, 64);
   if ((t & 63) == 0) wsum[t >> 6] = acc;
@@ -90,14 +90,6 @@ __global__ void __launch_bounds__(kThreads) noisy_normal_forward_kernel(NnParams
     for (int w = 0; w < kThreads / 64; ++w) s += wsum[w];     // fixed order
     p.partial[blockIdx.x] = s;
   }
-}
-
-__global__ void noisy_normal_reduce_kernel(const float* partial, int blocks_per_unit, long long units, float* bits) {
-  const long long u = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x;
-  if (u >= units) return;
-  float s = 0.f;
-  for (int b = 0; b < blocks_per_unit; ++b) s += partial[u * blocks_per_unit + b];
-  bits[u] = s * -1.4426950408889634f;
 }
 
 template <typename T>
@@ -145,13 +137,8 @@ __global__ void __launch_bounds__(kThreads) noisy_normal_backward_kernel(NnParam
 }
 
 int plan(long long units, long long elems, int* blocks_per_unit) {
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const long long rows = ceil_div(elems, kThreads);
-  const long long want = ceil_div(static_cast<long long>(cus) * 8, std::max<long long>(units, 1));
-  *blocks_per_unit = static_cast<int>(std::max<long long>(1, std::min<long long>(rows, want)));
-  if (units * *blocks_per_unit >= (1ll << 31)) return fail("tfc_noisy_normal_bits: problem too large");
+  *blocks_per_unit = bits_blocks_per_unit(units, elems, kThreads);
+  if (units * *blocks_per_unit > kMaxGridX) return fail("tfc_noisy_normal_bits: problem too large");
   return 0;
 }
 
@@ -178,8 +165,7 @@ int nn_forward(const char* who, const void* y, const void* noise, const float* s
     if (dtype == 0) hipLaunchKernelGGL(noisy_normal_forward_kernel<float>, grid, dim3(kThreads), 0, st, p);
     else hipLaunchKernelGGL(noisy_normal_forward_kernel<__hip_bfloat16>, grid, dim3(kThreads), 0, st, p);
   }
-  hipLaunchKernelGGL(noisy_normal_reduce_kernel, dim3(static_cast<unsigned>(ceil_div(units, 256))), dim3(256), 0, st,
-                     p.partial, p.blocks_per_unit, static_cast<long long>(units), bits);
+  launch_bits_reduce(p.partial, p.blocks_per_unit, units, bits, st);
   TFC_HIP(hipGetLastError());
   return 0;
 }

@@ -23,7 +23,7 @@
 #include <type_traits>
 
 #include "../../include/tfc_hip.h"
-#include "common.h"
+#include "launch.h"
 #include "sort_order.h"
 
 namespace tfc {
@@ -227,16 +227,12 @@ extern "C" int tfc_build_tables_overflow(const float* pmf, int64_t rows, int64_t
   if (rows == 0) return 0;
   const size_t n = static_cast<size_t>(max_length) + 1;
   const size_t lds = n * (sizeof(double) + 2 * sizeof(int) + sizeof(float));
-  if (lds > 160 * 1024)
+  if (lds > kLdsBytesPerCu)
     return fail("`pmf` rows of %lld elements exceed the on-chip table builder's limit (%d)",
-                static_cast<long long>(n), static_cast<int>(160 * 1024 / 20));
+                static_cast<long long>(n), static_cast<int>(kLdsBytesPerCu / 20));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&pmf_to_cdf_ragged_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-  hipLaunchKernelGGL(pmf_to_cdf_ragged_kernel, dim3(static_cast<unsigned>(rows)), dim3(64), lds, st, pmf, stride,
-                     lengths, offsets, precision, overflow, out);
-  TFC_HIP(hipGetLastError());
-  return 0;
+  return launch(pmf_to_cdf_ragged_kernel, dim3(static_cast<unsigned>(rows)), dim3(64), lds, st, pmf, stride, lengths,
+                offsets, precision, overflow, out);
 }
 
 extern "C" int tfc_pmf_to_quantized_cdf(const float* pmf, int64_t rows, int64_t n, int precision,
@@ -247,14 +243,10 @@ extern "C" int tfc_pmf_to_quantized_cdf(const float* pmf, int64_t rows, int64_t 
   if (n <= 1) return fail("`pmf` size should be at least 2 in the last axis.");
   if (rows == 0) return 0;
   const size_t lds = static_cast<size_t>(n) * (sizeof(double) + 2 * sizeof(int));
-  if (lds > 160 * 1024)
+  if (lds > kLdsBytesPerCu)
     return fail("`pmf` rows of %lld elements exceed the on-chip table builder's limit (%d)",
-                static_cast<long long>(n), static_cast<int>(160 * 1024 / 16));
+                static_cast<long long>(n), static_cast<int>(kLdsBytesPerCu / 16));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&pmf_to_cdf_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-  hipLaunchKernelGGL(pmf_to_cdf_kernel, dim3(static_cast<unsigned>(rows)), dim3(64), lds, st, pmf,
-                     rows, static_cast<int>(n), precision, cdf);
-  TFC_HIP(hipGetLastError());
-  return 0;
+  return launch(pmf_to_cdf_kernel, dim3(static_cast<unsigned>(rows)), dim3(64), lds, st, pmf, rows, static_cast<int>(n),
+                precision, cdf);
 }

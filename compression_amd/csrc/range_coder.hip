@@ -38,7 +38,7 @@
 #include <vector>
 
 #include "../../include/tfc_hip.h"
-#include "common.h"
+#include "launch.h"
 #include "range_coder_device.h"
 #include "range_tables.h"
 #include "range_wave.h"
@@ -612,17 +612,14 @@ __global__ void fill_state_many_kernel(uint8_t* ctl, long long ctl_bytes, int64_
 }  // namespace tfc
 
 // ===========================================================================
-// Host side: environment knobs and process-wide state
+// Host side: the coder's switches and process-wide state
 // ===========================================================================
-// Everything in this section exists once per process, behind the function that names it.
+// Everything in this section exists once per process, behind the function that names it.  (env_int and the table of all
+// switches: launch.h.)
 
 namespace {
 
-// An integer knob of the environment; `fallback` where it is not set.
-int env_int(const char* name, int fallback) {
-  const char* e = std::getenv(name);
-  return e ? std::atoi(e) : fallback;
-}
+constexpr int kLds = static_cast<int>(kLdsBytesPerCu);      // the lane and chain plans count LDS in int
 
 // Which image the pipelined decoder's chain runs on — 1 "full" (the lane-per-stream kernels' image, one bit per quotient
 // value), 2 "pairs" (the compact image, TFC_PDEC_STEP_H: half the bitmaps, ~10 % more cycles per row), 0: full where it
@@ -630,7 +627,7 @@ int env_int(const char* name, int fallback) {
 // tfc_set_pipe_format / TFC_PIPE_FORMAT, TFC_PIPE_WAVES: an A/B and test switch.
 std::atomic<int>& pipe_format_value() {
   static std::atomic<int> v{[] {
-    const char* e = std::getenv("TFC_PIPE_FORMAT");
+    const char* e = env_str("TFC_PIPE_FORMAT");
     if (e && std::strcmp(e, "full") == 0) return 1;
     if (e && std::strcmp(e, "pairs") == 0) return 2;
     return 0;
@@ -720,7 +717,6 @@ inline int side_stream(hipStream_t st, SideStream* out) {
 // (per device ordinal: a process may drive several devices of different memory sizes)
 struct PipeDeviceInfo {
   size_t temp_bytes = 0;
-  int cus = 0;
 };
 inline const PipeDeviceInfo& pipe_device_info() {
   constexpr int kMaxDevices = 64;
@@ -731,12 +727,7 @@ inline const PipeDeviceInfo& pipe_device_info() {
   dev = std::min(std::max(dev, 0), kMaxDevices - 1);
   std::call_once(once[dev], [dev] {
     PipeDeviceInfo& d = info[dev];
-    d.cus = 256;
-    if (hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
-      (void)hipGetLastError();
-      d.cus = 256;
-    }
-    if (std::getenv("TFC_PIPE_TEMP_MB")) {
+    if (env_str("TFC_PIPE_TEMP_MB")) {
       d.temp_bytes = static_cast<size_t>(std::max(1, env_int("TFC_PIPE_TEMP_MB", 0))) << 20;
       return;
     }
@@ -833,7 +824,7 @@ int select_family(const tfc_tables* t, int mode, int64_t streams, int64_t elems,
   // the lane kernels address a stream's bytes with 32 bits, and their LDS plan (image + one wave's
   // staging planes, any variant of the encoder) has to fit the CU
   const bool lanes_ok = t->lanes_ok && elems < (int64_t{1} << 29) &&
-                        ((t->lane_enc_bytes + 1023) & ~1023) + EncWaveLds<int32_t>::kBytes <= 160 * 1024;
+                        ((t->lane_enc_bytes + 1023) & ~1023) + EncWaveLds<int32_t>::kBytes <= kLds;
   if (mode == TFC_MODE_AUTO) mode = tfc_get_default_mode();
   if (mode == TFC_MODE_THROUGHPUT && lanes_ok) return kLanes;
   if (mode == TFC_MODE_AUTO && lanes_ok && streams >= 4096) return kLanes;
@@ -943,11 +934,11 @@ int encode_lanes_many(tfc_encoder* const* es, int n, const Src* srcs, const int3
   la.lds_image = (t->lane_enc_bytes + 1023) & ~1023;
   using WaveLds = EncWaveLds<typename Src::raw_type>;
   la.lds_wave = indexed ? WaveLds::kBytes : WaveLds::kIndex;
-  const int block = std::min(lanes_block(streams * n), 64 * ((160 * 1024 - la.lds_image) / la.lds_wave));
+  const int block = std::min(lanes_block(streams * n), 64 * ((kLds - la.lds_image) / la.lds_wave));
   const int lds_bytes = la.lds_image + (block / 64) * la.lds_wave;
   const void* fn = indexed ? reinterpret_cast<const void*>(&enc_lanes_kernel<true, Src>)
                            : reinterpret_cast<const void*>(&enc_lanes_kernel<false, Src>);
-  TFC_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+  if (int rc = allow_dynamic_lds(fn, lds_bytes)) return rc;
   // pipelined launch plan: groups of 64 streams, tiles of kPipeTile symbols; rows (coder calls) per stream: one per
   // symbol, and room for escape codes when the tables have escape rows (half more than the symbols)
   PipeEncArgs pa;
@@ -964,7 +955,7 @@ int encode_lanes_many(tfc_encoder* const* es, int n, const Src* srcs, const int3
   // A launch's chain workgroups must all be resident at once, next to an expansion that needs CUs of its own: a chain
   // workgroup (PipeEncChainLds::kGroups groups) takes a CU's whole LDS, so at most half the CUs go to chains — beyond
   // that the chains starve the expansion they wait for (and time out into the fallback).
-  const int cus_e = pipe_device_info().cus;
+  const int cus_e = device_cus();
   const size_t resident_jobs = std::max<size_t>(1, static_cast<size_t>(cus_e / 2) * PipeEncChainLds::kGroups / std::max(1, pa.groups_per_job));
   const int per_launch = !pipe ? kMaxLaneJobs
                                : static_cast<int>(std::max<size_t>(1, std::min<size_t>(std::min<size_t>(kMaxLaneJobs, resident_jobs),
@@ -1073,7 +1064,7 @@ int encode_lanes_many(tfc_encoder* const* es, int n, const Src* srcs, const int3
         const unsigned cblocks = static_cast<unsigned>(ceil_div(static_cast<int64_t>(groups), cgroups));
         const int clds = cgroups * PipeEncChainLds::kGroup;
         if (large)
-          TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&enc_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, clds));
+          if (int rc = allow_dynamic_lds(reinterpret_cast<const void*>(&enc_chain_kernel), clds)) return rc;
         auto chain = [&] {
           KernelTimer t2("enc_chain", cst);
           if (!large) {
@@ -1291,7 +1282,7 @@ int run_encode(tfc_encoder* e, const int32_t* index, int64_t elems, const Src& s
   p.chunk_off = ch.off.as<long long>();
 
   const int64_t tiles = ceil_div(elems, kCountTile);
-  if (e->streams * tiles >= (int64_t{1} << 31)) return fail("encode call too large for one launch");
+  if (e->streams * tiles > kMaxGridX) return fail("encode call too large for one launch");
   const size_t count_lds = p.tab.ntab <= kCountLdsRows ? sizeof(int) * p.tab.ntab : 0;
   hipLaunchKernelGGL((enc_count_kernel<Src>), dim3(static_cast<unsigned>(e->streams * tiles)),
                      dim3(256), count_lds, st, p, src);
@@ -1344,23 +1335,15 @@ int run_encode(tfc_encoder* e, const int32_t* index, int64_t elems, const Src& s
   const unsigned blocks = static_cast<unsigned>(ceil_div(e->streams, kWavesPerBlock));
   if (e->family == kFast) {
     KernelTimer timer("enc_kernel", st);
-    TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&enc_fast_kernel<Src>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                static_cast<int>(e->fast_lds)));
-    hipLaunchKernelGGL((enc_fast_kernel<Src>),
-                       dim3(static_cast<unsigned>(ceil_div(e->streams, e->fast_waves))),
-                       dim3(64 * e->fast_waves), e->fast_lds, st, p, src);
+    if (int rc = launch(&enc_fast_kernel<Src>, dim3(static_cast<unsigned>(ceil_div(e->streams, e->fast_waves))),
+                        dim3(64 * e->fast_waves), e->fast_lds, st, p, src))
+      return rc;
   } else {
     KernelTimer timer("enc_kernel", st);
-    if (lds) {
-      TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&enc_kernel<true, Src>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-      hipLaunchKernelGGL((enc_kernel<true, Src>), dim3(blocks), dim3(kBlock), lds, st, p, src);
-    } else {
-      hipLaunchKernelGGL((enc_kernel<false, Src>), dim3(blocks), dim3(kBlock), 0, st, p, src);
-    }
+    if (int rc = lds ? launch(&enc_kernel<true, Src>, dim3(blocks), dim3(kBlock), lds, st, p, src)
+                     : launch(&enc_kernel<false, Src>, dim3(blocks), dim3(kBlock), 0, st, p, src))
+      return rc;
   }
-  TFC_HIP(hipGetLastError());
   e->chunks.push_back(std::move(ch));
   return 0;
 }
@@ -1435,9 +1418,9 @@ void plan_encoder(tfc_encoder* e, const tfc_tables* tables, int64_t streams) {
   e->streams = streams;
   const size_t fixed = sizeof(uint16_t) * ((tables->host.size() + 3) & ~size_t{3}) + sizeof(int2) * tables->rows.size();
   const size_t ring = sizeof(unsigned int) * kRingWords;
-  if (!tables->rows.empty() && fixed + ring <= 160 * 1024) {
+  if (!tables->rows.empty() && fixed + ring <= kLdsBytesPerCu) {
     e->fast = true;
-    const size_t fit = (160 * 1024 - fixed) / ring;
+    const size_t fit = (kLdsBytesPerCu - fixed) / ring;
     const size_t want = static_cast<size_t>(waves_wanted(streams));
     e->fast_waves = static_cast<int>(std::min(fit, want));
     e->fast_lds = fixed + ring * e->fast_waves;
@@ -1972,21 +1955,11 @@ int launch_wave_decoder(tfc_decoder* d, const int32_t* index, int64_t elems, con
   const size_t fast_lds = dec_fast_lds(t);
   if (fast_lds) {
     const int waves = static_cast<int>(waves_wanted(d->streams));
-    TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_fast_kernel<Dst>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                static_cast<int>(fast_lds)));
-    hipLaunchKernelGGL((dec_fast_kernel<Dst>),
-                       dim3(static_cast<unsigned>(ceil_div(d->streams, waves))), dim3(64 * waves),
-                       fast_lds, st, p, dst);
-  } else if (lds) {
-    TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_kernel<true, Dst>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    hipLaunchKernelGGL((dec_kernel<true, Dst>), dim3(blocks), dim3(kBlock), lds, st, p, dst);
-  } else {
-    hipLaunchKernelGGL((dec_kernel<false, Dst>), dim3(blocks), dim3(kBlock), 0, st, p, dst);
+    return launch(&dec_fast_kernel<Dst>, dim3(static_cast<unsigned>(ceil_div(d->streams, waves))), dim3(64 * waves), fast_lds,
+                  st, p, dst);
   }
-  TFC_HIP(hipGetLastError());
-  return 0;
+  return lds ? launch(&dec_kernel<true, Dst>, dim3(blocks), dim3(kBlock), lds, st, p, dst)
+             : launch(&dec_kernel<false, Dst>, dim3(blocks), dim3(kBlock), 0, st, p, dst);
 }
 
 // Lane-per-stream family: n handles (same tables, same stream count) decoded by one launch per
@@ -2014,12 +1987,13 @@ int decode_lanes_many(tfc_decoder* const* ds, int n, const Dst* dsts, const int3
   // the lane-per-stream kernel (the pipelined kernels' fallback, or the launch's decoder) needs its image + a wave's
   // staging in a CU's LDS; tables whose image is larger (bls2017's 192 x 128 symbols: 176 KB) have the wave-per-stream
   // kernels as the fallback, handle by handle
-  const bool lanes_fit = la.lds_image + la.lds_wave <= 160 * 1024;
-  const int block = lanes_fit ? std::min(lanes_block(streams * n), 64 * ((160 * 1024 - la.lds_image) / la.lds_wave)) : 64;
+  const bool lanes_fit = la.lds_image + la.lds_wave <= kLds;
+  const int block = lanes_fit ? std::min(lanes_block(streams * n), 64 * ((kLds - la.lds_image) / la.lds_wave)) : 64;
   const int lds_bytes = la.lds_image + (block / 64) * la.lds_wave;
   const void* fn = indexed ? reinterpret_cast<const void*>(&dec_lanes_kernel<true, Dst>)
                            : reinterpret_cast<const void*>(&dec_lanes_kernel<false, Dst>);
-  if (lanes_fit) TFC_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+  if (lanes_fit)
+    if (int rc = allow_dynamic_lds(fn, lds_bytes)) return rc;
   // pipelined launch plan: groups of 64 streams; rows = steps of the chain (one per element, plus the bits of
   // escape codes: a quarter more is planned for when the tables have escape rows)
   PipeDecArgs pa;
@@ -2039,9 +2013,9 @@ int decode_lanes_many(tfc_decoder* const* ds, int n, const Dst* dsts, const int3
   // gives up on groups that do not move), one wave per SIMD at most: the full image where it fits and hosts the call's
   // waves (BASELINE config 2: 150 KB, one wave per CU = 32 batches per launch), else the compact one (92 KB for config 2:
   // four waves per CU, 128 batches per launch; 115 KB for bls2017's tables, whose full image does not fit at all).
-  const int cus_d = pipe_device_info().cus;
+  const int cus_d = device_cus();
   const int64_t waves_call = static_cast<int64_t>(pa.groups_per_job) * std::min(n, kMaxLaneJobs);
-  auto waves_fit = [&](int image_bytes) { return std::max(0, (160 * 1024 - image_bytes) / pla.lds_wave); };
+  auto waves_fit = [&](int image_bytes) { return std::max(0, (kLds - image_bytes) / pla.lds_wave); };
   const int pair_image = (t->pair_dec_bytes + 1023) & ~1023;
   const int fit_full = waves_fit(pla.lds_image), fit_pairs = t->pairs_ok ? waves_fit(pair_image) : 0;
   bool pairs = false;
@@ -2072,7 +2046,7 @@ int decode_lanes_many(tfc_decoder* const* ds, int n, const Dst* dsts, const int3
                     (static_cast<int64_t>(pa.rows) / kParseRows + 1) * pa.groups_per_job * kMaxLaneJobs < (int64_t{1} << 31);
   const int plds = pla.lds_image + (pblock / 64) * pla.lds_wave;
   const size_t chain_wgs_per_job = static_cast<size_t>(ceil_div(pa.groups_per_job, std::max(1, pblock / 64)));
-  const size_t resident_wgs = static_cast<size_t>(cus_d) * std::max<size_t>(1, (160 * 1024) / std::max(1, plds));
+  const size_t resident_wgs = static_cast<size_t>(cus_d) * std::max<size_t>(1, kLds / std::max(1, plds));
   const size_t resident_jobs = std::max<size_t>(1, resident_wgs / std::max<size_t>(1, chain_wgs_per_job));
   const int per_launch = !pipe ? kMaxLaneJobs
                                : static_cast<int>(std::max<size_t>(1, std::min<size_t>(std::min<size_t>(kMaxLaneJobs, resident_jobs),
@@ -2081,7 +2055,7 @@ int decode_lanes_many(tfc_decoder* const* ds, int n, const Dst* dsts, const int3
   if (pipe) {
     pfn = pairs ? (indexed ? reinterpret_cast<const void*>(&dec_chain_kernel<true, true>) : reinterpret_cast<const void*>(&dec_chain_kernel<false, true>))
                 : (indexed ? reinterpret_cast<const void*>(&dec_chain_kernel<true, false>) : reinterpret_cast<const void*>(&dec_chain_kernel<false, false>));
-    TFC_HIP(hipFuncSetAttribute(pfn, hipFuncAttributeMaxDynamicSharedMemorySize, plds));
+    if (int rc = allow_dynamic_lds(pfn, plds)) return rc;
   }
   if (!pipe && !lanes_fit) {
     // neither the pipelined kernels nor the lane-per-stream kernel can take the call: one wave per stream
@@ -2275,8 +2249,8 @@ bool decodes_on_lanes(const tfc_decoder* d, int64_t streams_in_launch, int64_t e
   using WaveLds = DecWaveLds<Elem>;
   const int need = ((t->lane_dec_bytes + 1023) & ~1023) + (indexed ? WaveLds::kBytes : WaveLds::kIndex);
   const int need_pairs = ((t->pair_dec_bytes + 1023) & ~1023) + (indexed ? PipeDecLds::kBytes : PipeDecLds::kRows) + PipeDecLds::kStage;
-  const bool compact_ok = t->pairs_ok && pipe_enabled() && pipe_format() != 1 && need_pairs <= 160 * 1024;
-  return need <= 160 * 1024 || compact_ok;
+  const bool compact_ok = t->pairs_ok && pipe_enabled() && pipe_format() != 1 && need_pairs <= kLds;
+  return need <= kLds || compact_ok;
 }
 
 // One handle that decode_jobs did not batch (checked and touched there)

@@ -458,7 +458,7 @@ struct PipeEncChainLds {
   static constexpr int kExit = 7;           // the chain has left its loop
   static constexpr unsigned int kLast = 0x80000000u, kBail = 0x40000000u;
 };
-static_assert(PipeEncChainLds::kGroups * PipeEncChainLds::kGroup <= 160 * 1024 && PipeEncChainLds::kSlots <= 4, "a chain workgroup's LDS");
+static_assert(PipeEncChainLds::kGroups * PipeEncChainLds::kGroup <= kLdsBytesPerCu && PipeEncChainLds::kSlots <= 4, "a chain workgroup's LDS");
 struct PipeChainJob { uint4* state; uint8_t* chunk; unsigned int* chunk_len; unsigned int* overflow_flag; };
 struct PipeChainJobs {
   int64_t streams;

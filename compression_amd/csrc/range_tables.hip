@@ -10,7 +10,7 @@
 #include <vector>
 
 #include "../../include/tfc_hip.h"
-#include "common.h"
+#include "launch.h"
 #include "range_coder_device.h"
 #include "range_tables.h"
 
@@ -295,7 +295,7 @@ extern "C" int tfc_tables_create(const int32_t* lookup, int rank, int64_t rows, 
     const size_t bits_off = dir_bytes + cdf_bytes;
     const size_t cum_off = bits_off + 8 * bits.size();
     const size_t total = cum_off + ((2 * cum.size() + 15) & ~size_t{15});
-    if (total <= 160 * 1024) {
+    if (total <= kLdsBytesPerCu) {
       std::vector<uint8_t> image(total, 0);
       tfc::LaneRow* dir = reinterpret_cast<tfc::LaneRow*>(image.data());
       auto entry_of = [&](size_t i, unsigned int limit, bool esc, unsigned int esclo, bool binary) {
@@ -362,7 +362,7 @@ TableView view_of(const tfc_tables* t) {
 // LDS bytes of dec_fast_kernel (decoder image + row directory), or 0 where the tables cannot take that kernel.
 size_t dec_fast_lds(const tfc_tables* t) {
   const size_t b = sizeof(int32_t) * ((t->dec_words + 3) & ~3) + sizeof(int4) * t->rows.size();
-  return t->dec_fast_ok && b <= 160 * 1024 ? b : 0;
+  return t->dec_fast_ok && b <= kLdsBytesPerCu ? b : 0;
 }
 
 }  // namespace tfc

@@ -21,7 +21,7 @@
 #include <cstring>
 
 #include "bf16_io.h"
-#include "common.h"
+#include "launch.h"
 #include "../../include/tfc_hip.h"
 
 namespace tfc {
@@ -630,11 +630,6 @@ int check_codes(const char* who, int rl, int mag) {
   return 0;
 }
 
-int64_t env_int(const char* name, int64_t dflt) {
-  const char* e = std::getenv(name);
-  return e && *e ? std::atoll(e) : dflt;
-}
-
 }  // namespace
 }  // namespace tfc
 
@@ -744,7 +739,7 @@ extern "C" int tfc_run_length_decode(const uint8_t* blob, const int64_t* offsets
   p.c = Codes{run_length_code, magnitude_code, nonzero_runs ? 1 : 0};
   p.status = status; p.out = out; p.out_dtype = out_dtype;
   // family: TFC_RL_DECODER = lane | chunk forces one, else chunks when the mean string is long
-  const char* fam = std::getenv("TFC_RL_DECODER");
+  const char* fam = env_str("TFC_RL_DECODER");
   const int64_t total_bits = host_offsets[units] * 8;
   bool chunked = total_bits / units >= env_int("TFC_RL_LONG_BITS", 16384);
   if (fam && !std::strcmp(fam, "lane")) chunked = false;
@@ -757,7 +752,7 @@ extern "C" int tfc_run_length_decode(const uint8_t* blob, const int64_t* offsets
   }
   int64_t B = env_int("TFC_RL_CHUNK_BITS", 1024);
   if (B < 1) B = 1;
-  const int rounds = static_cast<int>(env_int("TFC_RL_SYNC_ROUNDS", 2));
+  const int rounds = env_int("TFC_RL_SYNC_ROUNDS", 2);
   std::vector<int64_t> base(units + 1);
   base[0] = 0;
   for (int64_t u = 0; u < units; ++u) {

@@ -1,5 +1,5 @@
 // Library plumbing of the C ABI that is not a kernel: the last error text, slow-call and kernel timing, the profile
-// table, the process-wide mode switches, and the library's cache of released device memory.
+// table, the process-wide mode switches, the per-device CU count, and the library's cache of released device memory.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -11,9 +11,31 @@
 #include <vector>
 
 #include "../../include/tfc_hip.h"
-#include "common.h"
+#include "launch.h"
 
 namespace tfc {
+
+BlockCache::BlockCache() {
+  const char* e = std::getenv("TFC_CACHE_LIMIT_MB");
+  limit = static_cast<size_t>(e ? std::atoll(e) : 65536) << 20;
+}
+
+// (per device ordinal: a process may drive several devices)
+int device_cus() {
+  constexpr int kMaxDevices = 64;
+  static int cus[kMaxDevices];
+  static std::once_flag once[kMaxDevices];
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  dev = std::min(std::max(dev, 0), kMaxDevices - 1);
+  std::call_once(once[dev], [dev] {
+    if (hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
+      (void)hipGetLastError();
+      cus[dev] = 256;
+    }
+  });
+  return cus[dev];
+}
 
 std::string& last_error() {
   static thread_local std::string e;

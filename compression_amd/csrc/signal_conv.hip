@@ -65,7 +65,7 @@ template <> struct ConvTraits<float> {
 // ---------------------------------------------------------------------------
 // (TFC_CONV_XCD=0 in the environment: workgroup id = work item, for same-box comparisons)
 inline int xcd_blocks() {
-  static const int on = [] { const char* e = std::getenv("TFC_CONV_XCD"); return !(e && e[0] == '0'); }();
+  static const int on = env_switch("TFC_CONV_XCD") != 0;
   return on;
 }
 
@@ -778,51 +778,33 @@ int run_conv(const void* x, const float* w, const float* bias, void* y, ConvGeom
     // second-generation kernel (not for the image layer: its K is only a few dozen steps and the
     // first kernel, which stages all of them at once, is faster there); 2 pixel tiles per wave
     // when that still fills the chip
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const int mt = ceil_div(M, 256) * c.groups >= 2 * cus ? 2 : 1;
-    const long long pb = ceil_div(M, 128 * mt);
-    if (pb * c.groups >= (1ll << 31)) return fail("tfc_conv2d: problem too large for one launch");
-    const dim3 grid2(static_cast<unsigned>(pb * c.groups));
+    const int mt = ceil_div(M, 256) * c.groups >= 2 * device_cus() ? 2 : 1;
+    const long long blocks2 = ceil_div(M, 128 * mt) * c.groups;
+    if (blocks2 > kMaxGridX) return fail("tfc_conv2d: problem too large for one launch");
     const size_t lds2 = static_cast<size_t>(2) * kChunk2 * c.tiles * 64 * 16;
     KernelTimer timer("conv2d", st);
-#define TFC_CONV2_LAUNCH(NT, MTV, FK)                                                              \
-    do {                                                                                           \
-      TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<NT, MTV, FK>),   \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds2))); \
-      hipLaunchKernelGGL((conv_bf16_kernel<NT, MTV, FK>), grid2, dim3(256), lds2, st,              \
-                         static_cast<const __bf16*>(static_cast<const void*>(xin)), packed.p, bias,  \
-                         static_cast<__bf16*>(y), c);                                              \
-    } while (0)
+    // (F32: the kernel writes its float32 accumulators)
+#define TFC_CONV2_LAUNCH(NT, MTV, FK, F32)                                                         \
+    return launch(&conv_bf16_kernel<NT, MTV, FK, F32>, dim3(static_cast<unsigned>(blocks2)), dim3(256), lds2, st,         \
+                  static_cast<const __bf16*>(static_cast<const void*>(xin)), packed.p, bias, static_cast<__bf16*>(y), c)
     // one tap per weight chunk (see the kernel): channel blocks per tap a multiple of the chunk
     const bool fastk = kPF == kChunk2 && (c.Cin / 16) % kChunk2 == 0 && !TFC_CONV_NO_FASTK;
     // (the fp32-output variant is a compile-time property: as a run-time flag in the epilogue it cost the
     // 6-tile kernel 832 bytes of scratch per lane, accumulators spilled inside the K loop)
     // (round 6: with the one-tap-per-chunk K loop too, for the float32 layers that run as six bfloat16 planes — built for
     // the 128- and 192-column groups, the widths of the models' layers)
-#define TFC_CONV2_LAUNCH_F32K(NT, MTV, FK)                                                         \
-    do {                                                                                           \
-      TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<NT, MTV, FK, true>), \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds2))); \
-      hipLaunchKernelGGL((conv_bf16_kernel<NT, MTV, FK, true>), grid2, dim3(256), lds2, st,        \
-                         static_cast<const __bf16*>(static_cast<const void*>(xin)), packed.p, bias,  \
-                         static_cast<__bf16*>(y), c);                                              \
-    } while (0)
 #define TFC_CONV2_LAUNCH_F32(NT, MTV)                                                              \
     do {                                                                                           \
       if constexpr (NT == 6 || NT == 4) {                                                          \
-        if (fastk) TFC_CONV2_LAUNCH_F32K(NT, MTV, true); else TFC_CONV2_LAUNCH_F32K(NT, MTV, false); \
-      } else {                                                                                     \
-        TFC_CONV2_LAUNCH_F32K(NT, MTV, false);                                                     \
+        if (fastk) TFC_CONV2_LAUNCH(NT, MTV, true, true);                                          \
       }                                                                                            \
+      TFC_CONV2_LAUNCH(NT, MTV, false, true);                                                      \
     } while (0)
 #define TFC_CONV2_CASE(NT)                                                                         \
     case NT:                                                                                       \
       if (c.out_f32) { if (mt == 2) TFC_CONV2_LAUNCH_F32(NT, 2); else TFC_CONV2_LAUNCH_F32(NT, 1); } \
-      else if (mt == 2) { if (fastk) TFC_CONV2_LAUNCH(NT, 2, true); else TFC_CONV2_LAUNCH(NT, 2, false); } \
-      else { if (fastk) TFC_CONV2_LAUNCH(NT, 1, true); else TFC_CONV2_LAUNCH(NT, 1, false); }      \
-      break
+      else if (mt == 2) { if (fastk) TFC_CONV2_LAUNCH(NT, 2, true, false); else TFC_CONV2_LAUNCH(NT, 2, false, false); } \
+      else { if (fastk) TFC_CONV2_LAUNCH(NT, 1, true, false); else TFC_CONV2_LAUNCH(NT, 1, false, false); }
     switch (c.tiles) {
       TFC_CONV2_CASE(1);
       TFC_CONV2_CASE(2);
@@ -835,21 +817,12 @@ int run_conv(const void* x, const float* w, const float* bias, void* y, ConvGeom
 #undef TFC_CONV2_CASE
 #undef TFC_CONV2_LAUNCH
 #undef TFC_CONV2_LAUNCH_F32
-#undef TFC_CONV2_LAUNCH_F32K
-    TFC_HIP(hipGetLastError());
-    return 0;
   }
-  const long long pblocks = ceil_div(M, 32 * kConvWaves);
-  if (pblocks * c.groups >= (1ll << 31)) return fail("tfc_conv2d: problem too large for one launch");
-  const dim3 grid(static_cast<unsigned>(pblocks * c.groups));
+  const long long blocks = ceil_div(M, 32 * kConvWaves) * c.groups;
+  if (blocks > kMaxGridX) return fail("tfc_conv2d: problem too large for one launch");
   KernelTimer timer("conv2d", st);
-#define TFC_CONV_CASE(NT)                                                                        \
-  case NT:                                                                                       \
-    TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_kernel<T, NT>),              \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds))); \
-    hipLaunchKernelGGL((conv_kernel<T, NT>), grid, dim3(64 * kConvWaves), lds, st, xin, packed.p, \
-                       bias, static_cast<T*>(y), c);                                             \
-    break
+#define TFC_CONV_CASE(NT) \
+  case NT: return launch(&conv_kernel<T, NT>, dim3(static_cast<unsigned>(blocks)), dim3(64 * kConvWaves), lds, st, xin, packed.p, bias, static_cast<T*>(y), c)
   switch (c.tiles) {
     TFC_CONV_CASE(1);
     TFC_CONV_CASE(2);
@@ -860,8 +833,6 @@ int run_conv(const void* x, const float* w, const float* bias, void* y, ConvGeom
       TFC_CONV_CASE(6);
   }
 #undef TFC_CONV_CASE
-  TFC_HIP(hipGetLastError());
-  return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -1152,7 +1123,7 @@ int route_image(const ConvCall& k) {
   // (patch | weight fragments | the epilogue's staging area: 4 waves x 32 pixels x 144 bytes)
   const size_t lds = static_cast<size_t>(g.PH) * g.RS * 2 + static_cast<size_t>(k.kh) * g.ksr * tiles * 64 * 16 + 4 * 32 * 144;
   g.items = 8;
-  if (lds > 160 * 1024 || k.n * g.BXn * g.BYn >= (1ll << 31)) return -1;
+  if (lds > kLdsBytesPerCu || k.n * g.BXn * g.BYn > kMaxGridX) return -1;
   // image rows and patch rows on 4-byte boundaries (x itself is: torch allocations are 256-byte aligned, and a slice
   // of a batch starts at a whole image)
   g.pairs = (g.W * g.Cin) % 2 == 0 && (g.px0 * g.Cin) % 2 == 0 && (g.H * g.W * g.Cin) % 2 == 0 &&
@@ -1165,12 +1136,8 @@ int route_image(const ConvCall& k) {
   KernelTimer timer("conv2d", st);
   const dim3 grid(static_cast<unsigned>(ceil_div(k.n * g.BXn * g.BYn, g.items)));
   auto* kernel = tiles == 6 ? conv_image_kernel<6> : conv_image_kernel<4>;
-  TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              static_cast<int>(lds)));
-  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, static_cast<const __bf16*>(k.x), wpk.as<bf16x8>(), k.bias,
-                     static_cast<__bf16*>(k.y), g);
-  TFC_HIP(hipGetLastError());
-  return 0;
+  return launch(kernel, grid, dim3(256), lds, st, static_cast<const __bf16*>(k.x), wpk.as<bf16x8>(), k.bias,
+                static_cast<__bf16*>(k.y), g);
 }
 
 // ---------------------------------------------------------------------------
@@ -1441,30 +1408,20 @@ int route_image_direct(const ConvCall& k) {
   constexpr int tiles = 6;
   const size_t lds = (gdn ? static_cast<size_t>(tiles) * 2 * tiles * 64 * 16 + tiles * 32 * 4 : 0) + tiles * 32 * 4 +
                      static_cast<size_t>(nk) * tiles * 64 * 16 + 8 * 32 * 144;
-  if (lds > 160 * 1024) return -1;
+  if (lds > kLdsBytesPerCu) return -1;
   DevBuf wpk_local;
   DevView wpk;
   const int frags = nk * tiles * 64;
   if (const int rc = image_weights(k, g, tiles, frags, wpk_local, &wpk)) return rc;
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   const long long ntiles = k.n * g.OH * (g.OW / 32);
-  const unsigned grid = static_cast<unsigned>(std::min<long long>(cus, ceil_div(ntiles, 8)));
+  const unsigned grid = static_cast<unsigned>(std::min<long long>(device_cus(), ceil_div(ntiles, 8)));
   KernelTimer timer("conv2d", st);
-#define TFC_IMAGE_DIRECT_LAUNCH(...)                                                                              \
-  do {                                                                                                           \
-    TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_image_direct_kernel<__VA_ARGS__>),           \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));             \
-    hipLaunchKernelGGL((conv_image_direct_kernel<__VA_ARGS__>), dim3(grid), dim3(512), lds, st,                   \
-                       static_cast<const __bf16*>(k.x), wpk.as<bf16x8>(), k.bias, gdn ? gdn->image.p : nullptr,     \
-                       static_cast<__bf16*>(k.y), g);                                                            \
-  } while (0)
-  if (k5 && gdn) TFC_IMAGE_DIRECT_LAUNCH(6, 5, 5, 2, true);
-  else if (k5) TFC_IMAGE_DIRECT_LAUNCH(6, 5, 5, 2, false);
-  else TFC_IMAGE_DIRECT_LAUNCH(6, 9, 9, 4, false);
-#undef TFC_IMAGE_DIRECT_LAUNCH
-  TFC_HIP(hipGetLastError());
+  auto* kernel = k5 && gdn ? conv_image_direct_kernel<6, 5, 5, 2, true>
+                 : k5      ? conv_image_direct_kernel<6, 5, 5, 2, false>
+                           : conv_image_direct_kernel<6, 9, 9, 4, false>;
+  if (int rc = launch(kernel, dim3(grid), dim3(512), lds, st, static_cast<const __bf16*>(k.x), wpk.as<bf16x8>(), k.bias,
+                      gdn ? gdn->image.p : nullptr, static_cast<__bf16*>(k.y), g))
+    return rc;
   if (gdn) {
     const_cast<tfc_gdn_params*>(gdn)->image.touch(st);
     *k.gdn_fused = 1;
@@ -1855,7 +1812,7 @@ __global__ void __launch_bounds__(512, 2) conv_up_phase_kernel(const __bf16* x, 
 int route_up_phase(const ConvCall& k) {
   if (!k.up || k.dtype != 1 || k.cout != 3 || k.out_f32) return -1;
   hipStream_t st = k.stream;
-  static const bool off = [] { const char* e = std::getenv("TFC_CONV_UP_PHASE"); return e && e[0] == '0'; }();
+  static const bool off = env_switch("TFC_CONV_UP_PHASE") == 0;
   if (off || k.cin % 32 || k.kh != k.kw) return -1;
   const bool k5 = k.kh == 5 && k.stride == 2, k9 = k.kh == 9 && k.stride == 4;
   if (!k5 && !k9) return -1;
@@ -1866,13 +1823,13 @@ int route_up_phase(const ConvCall& k) {
   g.N = k.n; g.H = static_cast<int>(k.h); g.W = static_cast<int>(k.wd); g.Cin = static_cast<int>(k.cin);
   g.activation = k.activation; g.nchunk = static_cast<int>(k.cin / 32);
   const long long blocks = k.n * ((g.H + kPhaseRows - 1) / kPhaseRows) * ((g.W + 31) / 32);
-  if (blocks >= (1ll << 31)) return -1;
+  if (blocks > kMaxGridX) return -1;
   const int frags_per_chunk = k9 ? UpPhase<9, 4>::FRAGS : UpPhase<5, 2>::FRAGS;
   const int frags = g.nchunk * frags_per_chunk * 64;
   const int cps = k9 ? UpPhase<9, 4>::CPS : UpPhase<5, 2>::CPS, pxs = k9 ? UpPhase<9, 4>::PXS : UpPhase<5, 2>::PXS;
   if (g.nchunk % cps) return -1;
   const size_t lds = static_cast<size_t>(kPhaseTilePix) * pxs + static_cast<size_t>(cps) * frags_per_chunk * 1024;
-  auto launch = [&](auto weights_kernel, auto kernel) -> int {
+  auto run = [&](auto weights_kernel, auto kernel) -> int {
     DevBuf wpk_local;
     DevView wpk;
     const int rc = packed_weights(k.weights_key, 5, {k.kh, k.kw, k.cin, k.cout, k.stride}, static_cast<size_t>(frags) * 16, st,
@@ -1883,15 +1840,11 @@ int route_up_phase(const ConvCall& k) {
     });
     if (rc) return rc;
     KernelTimer timer("conv2d", st);
-    TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                static_cast<int>(lds)));
-    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(512), lds, st, static_cast<const __bf16*>(k.x),
-                       wpk.as<bf16x8>(), k.bias, static_cast<__bf16*>(k.y), g);
-    TFC_HIP(hipGetLastError());
-    return 0;
+    return launch(kernel, dim3(static_cast<unsigned>(blocks)), dim3(512), lds, st, static_cast<const __bf16*>(k.x),
+                  wpk.as<bf16x8>(), k.bias, static_cast<__bf16*>(k.y), g);
   };
-  return k9 ? launch(conv_up_phase_weights_kernel<9, 4>, conv_up_phase_kernel<9, 4>)
-            : launch(conv_up_phase_weights_kernel<5, 2>, conv_up_phase_kernel<5, 2>);
+  return k9 ? run(conv_up_phase_weights_kernel<9, 4>, conv_up_phase_kernel<9, 4>)
+            : run(conv_up_phase_weights_kernel<5, 2>, conv_up_phase_kernel<5, 2>);
 }
 
 }  // namespace tfc
@@ -1932,6 +1885,10 @@ __global__ void __launch_bounds__(256) conv_split_x_kernel(const float* x, long 
   *reinterpret_cast<bf16x8*>(row + 4 * C) = p2;
   *reinterpret_cast<bf16x8*>(row + 5 * C) = p3;
 }
+void launch_conv_split_x(const float* x, long long pixels, int C, __bf16* xs, hipStream_t st) {
+  hipLaunchKernelGGL(conv_split_x_kernel, dim3(static_cast<unsigned>(ceil_div(pixels * (C / 8), 256))), dim3(256), 0, st, x,
+                     pixels, C, xs);
+}
 // w float32 [taps, C, Cout] -> w6 float32 [taps, 6 C, Cout] holding the planes [w1 | w2 | w3 | w1 | w2 | w1] as float32
 // values (each exactly a bfloat16: the packing kernels' rounding leaves them as they are)
 __global__ void __launch_bounds__(256) conv_split_w_kernel(const float* w, long long taps, int C, int Cout, float* w6) {
@@ -1952,13 +1909,12 @@ __global__ void __launch_bounds__(256) conv_split_w_kernel(const float* w, long 
 
 // (read per call: the tests compare the two in one process)
 static bool conv_f32_split_enabled() {
-  const char* e = std::getenv("TFC_CONV_F32");
+  const char* e = env_str("TFC_CONV_F32");
   return !(e && std::strcmp(e, "native") == 0);
 }
 
-// The planes of the input are 3x its bytes: images go through in chunks of ~2 GB of planes (bmshj2018's first 192 -> 192
-// layer at 128 x 768x512 would need 29 GB at once), each chunk split and convolved before the next — the kernel's six
-// planes are made and packed once, under the key derived from the caller's or a key of this call's own.
+// The input's planes go through in chunks of images (conv_f32_chunks), each chunk split and convolved before the next —
+// the kernel's six planes are made and packed once, under the key derived from the caller's or a key of this call's own.
 int route_f32_planes(const ConvCall& k) {
   if (k.dtype != 0 || !conv_f32_split_enabled() || k.cin % 16 || k.cout % 4 || k.gdn ||
       6 * k.cin * static_cast<int64_t>(k.kh) * k.kw >= (int64_t{1} << 24))
@@ -1966,37 +1922,25 @@ int route_f32_planes(const ConvCall& k) {
   hipStream_t st = k.stream;
   const int64_t cin = k.cin, cout = k.cout;
   const long long taps = static_cast<long long>(k.kh) * k.kw;
-  const long long pix_image = static_cast<long long>(k.h) * k.wd;
-  const size_t plane_bytes_image = static_cast<size_t>(pix_image) * 6 * cin * sizeof(__bf16);
-  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(k.n, static_cast<int64_t>(conv_f32_chunk_bytes() / std::max<size_t>(plane_bytes_image, 1))));
-  DevBuf xs, w6;
-  TFC_HIP(xs.alloc(plane_bytes_image * static_cast<size_t>(chunk), st));
+  DevBuf w6;
   TFC_HIP(w6.alloc(static_cast<size_t>(taps) * 6 * cin * cout * sizeof(float), st));
   const long long wthreads = taps * cin * cout;
-  if (ceil_div(pix_image * chunk * (cin / 8), 256) >= (1ll << 31)) return fail("tfc_conv2d: problem too large for one launch");
   hipLaunchKernelGGL(conv_split_w_kernel, dim3(static_cast<unsigned>(ceil_div(wthreads, 256))), dim3(256), 0, st,
                      k.w, taps, static_cast<int>(cin), static_cast<int>(cout), w6.as<float>());
   static std::atomic<unsigned long long> own_keys{0};
   // one bfloat16 convolution per chunk: six times the channels, float32 out, the planes' key
   ConvCall planes = k;
-  planes.x = xs.p; planes.w = w6.as<float>(); planes.dtype = 1; planes.cin = 6 * cin; planes.out_f32 = true;
+  planes.w = w6.as<float>(); planes.dtype = 1; planes.cin = 6 * cin; planes.out_f32 = true;
   planes.weights_key = k.weights_key ? (k.weights_key ^ kPlanesKey)
                                      : (0xf32c000000000000ull | own_keys.fetch_add(1, std::memory_order_relaxed));
   const long long out_image = (k.up ? static_cast<long long>(k.h) * k.stride * k.wd * k.stride
                                     : static_cast<long long>((k.h + k.stride - 1) / k.stride) * ((k.wd + k.stride - 1) / k.stride)) * cout;
-  int rc = 0;
-  for (int64_t n0 = 0; n0 < k.n && rc == 0; n0 += chunk) {
-    planes.n = std::min<int64_t>(chunk, k.n - n0);
+  const int rc = conv_f32_chunks("tfc_conv2d", "conv2d", static_cast<const float*>(k.x), k.n, static_cast<long long>(k.h) * k.wd,
+                                 cin, st, [&](int64_t n0, int64_t images, const __bf16* xs) {
+    planes.x = xs; planes.n = images;
     planes.y = static_cast<float*>(k.y) + n0 * out_image;
-    const long long pixels = pix_image * planes.n;
-    {
-      KernelTimer timer("conv2d", st);
-      hipLaunchKernelGGL(conv_split_x_kernel, dim3(static_cast<unsigned>(ceil_div(pixels * (cin / 8), 256))), dim3(256), 0, st,
-                         static_cast<const float*>(k.x) + n0 * pix_image * cin, pixels, static_cast<int>(cin), xs.as<__bf16>());
-    }
-    rc = conv_entry(planes);
-  }
-  TFC_HIP(hipGetLastError());
+    return conv_entry(planes);
+  });
   if (!k.weights_key) (void)tfc_conv2d_drop_weights(planes.weights_key);
   return rc;
 }
@@ -2018,27 +1962,18 @@ int route_up_fused(const ConvCall& k) {
   if (g.NC > kUpZStride) return -1;
   const int tiles = (g.PH * g.PW + 31) / 32;
   const size_t lds = static_cast<size_t>(tiles) * 32 * kUpZStride * 4 + static_cast<size_t>(k.cin / 16) * kUpColTiles * 64 * 16;
-  if (lds > 160 * 1024 || k.n * g.BXn * g.BYn >= (1ll << 31)) return -1;
+  if (lds > kLdsBytesPerCu || k.n * g.BXn * g.BYn > kMaxGridX) return -1;
   DevBuf wpk;
   const int frags = static_cast<int>(k.cin / 16) * kUpColTiles * 64;
   TFC_HIP(wpk.alloc(static_cast<size_t>(frags) * 16, st));
   hipLaunchKernelGGL(conv_up_fused_weights_kernel, dim3((frags + 255) / 256), dim3(256), 0, st, k.w, k.kh, k.kw,
                      static_cast<int>(k.cin), static_cast<int>(k.cout), wpk.as<bf16x8>());
   KernelTimer timer("conv2d", st);
-#define TFC_UP_FUSED_LAUNCH(...)                                                                              \
-  do {                                                                                                       \
-    TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up_fused_kernel<__VA_ARGS__>),           \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));         \
-    hipLaunchKernelGGL((conv_up_fused_kernel<__VA_ARGS__>), dim3(static_cast<unsigned>(k.n * g.BXn * g.BYn)),   \
-                       dim3(kUpThreads), lds, st, static_cast<const __bf16*>(k.x), wpk.as<bf16x8>(), k.bias,     \
-                       static_cast<__bf16*>(k.y), g);                                                          \
-  } while (0)
-  if (k.kh == 5 && k.kw == 5 && k.stride == 2 && k.cout == 3) TFC_UP_FUSED_LAUNCH(5, 5, 2, 3);          // bmshj2018
-  else if (k.kh == 9 && k.kw == 9 && k.stride == 4 && k.cout == 3) TFC_UP_FUSED_LAUNCH(9, 9, 4, 3);     // bls2017
-  else TFC_UP_FUSED_LAUNCH(0, 0, 0, 0);
-#undef TFC_UP_FUSED_LAUNCH
-  TFC_HIP(hipGetLastError());
-  return 0;
+  auto* kernel = k.kh == 5 && k.kw == 5 && k.stride == 2 && k.cout == 3   ? conv_up_fused_kernel<5, 5, 2, 3>      // bmshj2018
+                 : k.kh == 9 && k.kw == 9 && k.stride == 4 && k.cout == 3 ? conv_up_fused_kernel<9, 9, 4, 3>      // bls2017
+                                                                          : conv_up_fused_kernel<0, 0, 0, 0>;
+  return launch(kernel, dim3(static_cast<unsigned>(k.n * g.BXn * g.BYn)), dim3(kUpThreads), lds, st,
+                static_cast<const __bf16*>(k.x), wpk.as<bf16x8>(), k.bias, static_cast<__bf16*>(k.y), g);
 }
 
 // The 1x1 product and the gather as two kernels: what route_up_fused has left.
@@ -2063,7 +1998,7 @@ int route_up_gather(const ConvCall& k) {
   prod.out_f32 = true; prod.stream = st; prod.weights_key = 0;
   if (int rc = conv_entry(prod)) return rc;
   const long long outs = k.n * k.h * k.stride * k.wd * k.stride;
-  if (ceil_div(outs, 256) >= (1ll << 31)) return fail("tfc_conv2d_up: problem too large for one launch");
+  if (ceil_div(outs, 256) > kMaxGridX) return fail("tfc_conv2d_up: problem too large for one launch");
   KernelTimer timer("conv2d", st);
   hipLaunchKernelGGL(conv_up_gather_kernel, dim3(static_cast<unsigned>(ceil_div(outs, 256))), dim3(256), 0, st,
                      z.as<float>(), k.bias, static_cast<__bf16*>(k.y), static_cast<long long>(k.n), static_cast<int>(k.h),

@@ -25,8 +25,7 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kTile = 128;                     // output samples per workgroup (4 waves x 32)
-constexpr size_t kLdsBytes = 160 * 1024;
-constexpr size_t kHalfLds = kLdsBytes / 2;     // two workgroups per CU where the stage fits in half
+constexpr size_t kHalfLds = kLdsBytesPerCu / 2;     // two workgroups per CU where the stage fits in half
 
 struct C3Geom {
   long long N;
@@ -169,26 +168,6 @@ __global__ void __launch_bounds__(kThreads, 2) conv3d_fwd_kernel(const __bf16* _
   }
 }
 
-// x float32 [pixels, C] -> bfloat16 [pixels, 6 C] planes [x1 | x1 | x1 | x2 | x2 | x3]; C % 8 == 0
-__global__ void __launch_bounds__(256) conv3d_split_x_kernel(const float* x, long long pixels, int C, __bf16* xs) {
-  const int per = C / 8;
-  const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-  if (i >= pixels * per) return;
-  const long long pix = i / per;
-  const int c0 = static_cast<int>(i - pix * per) * 8;
-  const f32x4 lo = *reinterpret_cast<const f32x4*>(x + pix * C + c0), hi = *reinterpret_cast<const f32x4*>(x + pix * C + c0 + 4);
-  bf16x8 p[3];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    __bf16 a, b, c;
-    split3(e < 4 ? lo[e] : hi[e - 4], &a, &b, &c);
-    p[0][e] = a; p[1][e] = b; p[2][e] = c;
-  }
-  __bf16* row = xs + pix * 6 * C + c0;
-#pragma unroll
-  for (int q = 0; q < 6; ++q) *reinterpret_cast<bf16x8*>(row + q * C) = p[x_plane(q)];
-}
-
 // ---- weight gradient ----------------------------------------------------------------------------------------------
 // G[t][ca][cb] = sum_{n,q} A[n, q o s + t - k/2, ca] B[n, q, cb]: per tap a GEMM whose K is B's pixels.  A workgroup
 // computes a 64 x 64 (ca, cb) block of one tap over one chunk of B's pixels, 64 pixels per LDS stage with both operands
@@ -304,8 +283,6 @@ __global__ void __launch_bounds__(256) conv3d_wgrad_sum_kernel(const float* part
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------
-constexpr long long kMaxGrid = (1ll << 31) - 1;
-
 // NT (32-column tiles per workgroup) for Cout: the fewest padded columns, then the widest tile
 int pick_nt(int64_t cout) {
   int best = 1;
@@ -381,9 +358,9 @@ int conv3d_plan(const char* name, int up, const int64_t in[3], int64_t cout, con
   while (NT > 1 && lds_of(TW, NT, nullptr) > kHalfLds) --NT;
   while (TW > 32 && lds_of(TW, NT, nullptr) > kHalfLds) TW /= 2;
   plan->lds = lds_of(TW, NT, &plan->patch_pieces);
-  if (plan->lds > kLdsBytes) return fail("%s: kernel support too large for one workgroup's LDS (%zu bytes)", name, plan->lds);
+  if (plan->lds > kLdsBytesPerCu) return fail("%s: kernel support too large for one workgroup's LDS (%zu bytes)", name, plan->lds);
   plan->nblk = static_cast<int>(ceil_div(cout, 32 * NT));
-  if (plan->nblk > 65535) return fail("%s: too many output channels for one launch", name);
+  if (plan->nblk > kMaxGridYZ) return fail("%s: too many output channels for one launch", name);
   plan->TW = TW; plan->TH = kTile / TW; plan->NT = NT;
   plan->tiles_w = static_cast<int>(ceil_div(phases[0].OD[2], TW));          // every phase has the same output grid
   plan->tiles_h = static_cast<int>(ceil_div(phases[0].OD[1], plan->TH));
@@ -419,7 +396,7 @@ int conv3d_bf16(const char* name, const __bf16* x, const float* w, int planes, c
       for (int a = 0; a < 3; ++a) { pa.T[a] = f.T[a]; pa.A[a] = f.A[a]; pa.B[a] = f.B[a]; }
       const long long pieces = (p + 1 < nph ? wofs[p + 1] : wtotal) - wofs[p];
       if (pieces == 0) continue;
-      if (ceil_div(pieces, 256) > kMaxGrid) return fail("%s: kernel too large for one launch", name);
+      if (ceil_div(pieces, 256) > kMaxGridX) return fail("%s: kernel too large for one launch", name);
       hipLaunchKernelGGL(conv3d_pack_kernel, dim3(static_cast<unsigned>(ceil_div(pieces, 256))), dim3(256), 0, st, w, pa,
                          wpk.as<bf16x8>() + wofs[p]);
     }
@@ -445,24 +422,14 @@ int conv3d_bf16(const char* name, const __bf16* x, const float* w, int planes, c
     g.patch_pieces = static_cast<int>(patch_pieces);
     g.activation = activation;
     const long long blocks = n * g.OD * g.tiles_h * static_cast<long long>(g.tiles_w);
-    if (blocks > kMaxGrid) return fail("%s: problem too large for one launch (%lld tiles)", name, blocks);
+    if (blocks > kMaxGridX) return fail("%s: problem too large for one launch (%lld tiles)", name, blocks);
     if (blocks == 0) continue;
-#define TFC_C3_LAUNCH(NTV)                                                                                          \
-  do {                                                                                                              \
-    auto kern = out_f32 ? conv3d_fwd_kernel<NTV, true> : conv3d_fwd_kernel<NTV, false>;                           \
-    TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                                static_cast<int>(lds)));                                                            \
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks), static_cast<unsigned>(nblk)), dim3(kThreads), lds, st, \
-                       x, wpk.as<bf16x8>(), bias, y, g);                                                            \
-  } while (0)
-    switch (NT) {
-      case 1: TFC_C3_LAUNCH(1); break;
-      case 2: TFC_C3_LAUNCH(2); break;
-      case 3: TFC_C3_LAUNCH(3); break;
-      default: TFC_C3_LAUNCH(4); break;
-    }
-#undef TFC_C3_LAUNCH
-    TFC_HIP(hipGetLastError());
+#define TFC_C3_KERNEL(NTV) (out_f32 ? conv3d_fwd_kernel<NTV, true> : conv3d_fwd_kernel<NTV, false>)
+    auto* kern = NT == 1 ? TFC_C3_KERNEL(1) : NT == 2 ? TFC_C3_KERNEL(2) : NT == 3 ? TFC_C3_KERNEL(3) : TFC_C3_KERNEL(4);
+#undef TFC_C3_KERNEL
+    if (int rc = launch(kern, dim3(static_cast<unsigned>(blocks), static_cast<unsigned>(nblk)), dim3(kThreads), lds, st, x,
+                        wpk.as<bf16x8>(), bias, y, g))
+      return rc;
   }
   return 0;
 }
@@ -498,30 +465,14 @@ int conv3d_entry(const char* name, const void* x, const void* w, const float* bi
   if (dtype == 1)
     return conv3d_bf16(name, static_cast<const __bf16*>(x), static_cast<const float*>(w), 1, bias, y, false, n, in, cin,
                        cin, cout, k, s, activation, up, st);
-  // float32: six bfloat16 planes (split3) through the same kernel, float32 out; images in chunks of ~2 GB of planes
-  // (conv_f32_chunk_bytes: TFC_CONV_F32_CHUNK_BYTES, as the rank-2 path)
-  const long long pix_image = d * h * wd;
-  const size_t plane_bytes = static_cast<size_t>(pix_image) * 6 * cin * sizeof(__bf16);
-  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, static_cast<int64_t>(conv_f32_chunk_bytes() / plane_bytes)));
-  if (ceil_div(pix_image * chunk * (cin / 8), 256) > kMaxGrid) return fail("%s: problem too large for one launch", name);
-  DevBuf xs;
-  TFC_HIP(xs.alloc(plane_bytes * static_cast<size_t>(chunk), st));
+  // float32: six bfloat16 planes (split3) through the same kernel, float32 out, a chunk of images at a time
   long long out_image = cout;
   for (int a = 0; a < 3; ++a) out_image *= up ? in[a] * s[a] : ceil_div(in[a], s[a]);
-  for (int64_t n0 = 0; n0 < n; n0 += chunk) {
-    const int64_t nc = std::min<int64_t>(chunk, n - n0);
-    const long long pixels = pix_image * nc;
-    {
-      KernelTimer timer("conv3d", st);
-      hipLaunchKernelGGL(conv3d_split_x_kernel, dim3(static_cast<unsigned>(ceil_div(pixels * (cin / 8), 256))), dim3(256), 0,
-                         st, static_cast<const float*>(x) + n0 * pix_image * cin, pixels, static_cast<int>(cin), xs.as<__bf16>());
-      TFC_HIP(hipGetLastError());
-    }
-    if (int rc = conv3d_bf16(name, xs.as<__bf16>(), static_cast<const float*>(w), 6, bias,
-                             static_cast<float*>(y) + n0 * out_image, true, nc, in, 6 * cin, cin, cout, k, s, activation, up, st))
-      return rc;
-  }
-  return 0;
+  return conv_f32_chunks(name, "conv3d", static_cast<const float*>(x), n, d * h * wd, cin, st,
+                         [&](int64_t n0, int64_t images, const __bf16* xs) {
+    return conv3d_bf16(name, xs, static_cast<const float*>(w), 6, bias, static_cast<float*>(y) + n0 * out_image, true,
+                       images, in, 6 * cin, cin, cout, k, s, activation, up, st);
+  });
 }
 
 // the scalar arguments of a weight gradient call, as tfc_conv3d_wgrad and tfc_conv3d_wgrad_plan both demand them
@@ -551,13 +502,13 @@ int conv3d_wgrad_plan(const char* name, long long P, long long taps, int64_t ca,
   plan->tiles_ca = ceil_div(ca, 64);
   plan->tiles_cb = ceil_div(cb, 64);
   const long long tiles = plan->tiles_ca * plan->tiles_cb;
-  if (tiles > 65535 || taps > kMaxGrid) return fail("%s: problem too large for one launch", name);
+  if (tiles > kMaxGridYZ || taps > kMaxGridX) return fail("%s: problem too large for one launch", name);
   // chunks of B's pixels: about 4096 workgroups in all, and at most 256 MB of partials
   const long long per_chunk = taps * ca * cb;
   const long long steps = ceil_div(P, 64);
   long long chunks = std::min<long long>(steps, std::max<long long>(1, ceil_div(4096, taps * tiles)));
   chunks = std::max<long long>(1, std::min<long long>(chunks, static_cast<long long>((size_t{256} << 20) / (static_cast<size_t>(per_chunk) * 4))));
-  chunks = std::min<long long>(chunks, 65535);
+  chunks = std::min<long long>(chunks, kMaxGridYZ);
   plan->chunk_steps = ceil_div(steps, chunks);
   plan->chunks = ceil_div(steps, plan->chunk_steps);
   return 0;
@@ -620,7 +571,7 @@ extern "C" int tfc_conv3d_wgrad(const void* a, const void* b, float* dw, int dty
     hipLaunchKernelGGL(conv3d_wgrad_kernel<float>, grid, dim3(256), 0, st, static_cast<const float*>(a),
                        static_cast<const float*>(b), part.as<float>(), g);
   TFC_HIP(hipGetLastError());
-  if (ceil_div(per_chunk, 256) > kMaxGrid) return fail("%s: problem too large for one launch", name);
+  if (ceil_div(per_chunk, 256) > kMaxGridX) return fail("%s: problem too large for one launch", name);
   hipLaunchKernelGGL(conv3d_wgrad_sum_kernel, dim3(static_cast<unsigned>(ceil_div(per_chunk, 256))), dim3(256), 0, st,
                      part.as<float>(), per_chunk, static_cast<int>(chunks), static_cast<int>(ca), static_cast<int>(cb),
                      transpose, dw);

@@ -381,7 +381,7 @@ inline int tiles_of(int64_t c) { return c <= 4 ? 1 : static_cast<int>(c / 32); }
 
 // TFC_WGRAD_TR = 0 (read once per process): the transpose by hand (the round-5 staging) for every bfloat16 pair
 inline bool wgrad_tr_enabled() {
-  static const bool tr_on = [] { const char* e = std::getenv("TFC_WGRAD_TR"); return !(e && e[0] == '0'); }();
+  static const bool tr_on = env_switch("TFC_WGRAD_TR") != 0;
   return tr_on;
 }
 
@@ -431,20 +431,13 @@ int launch_wgrad(WgradGeom g, const WgradPlan& plan, int transpose, float* dw, h
   fast_div_setup(static_cast<unsigned int>(g.HB), &g.hb_mul, &g.hb_sh);
   {
     KernelTimer timer("conv2d_wgrad", st);
+    auto run = [&](auto kernel) { return launch(kernel, dim3(static_cast<unsigned>(taps * g.chunks)), dim3(256), lds, st, g); };
+    int rc = 0;
     if constexpr (sizeof(T) == 2) {
-      if (g.tr) {
-        TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<T, KTA, KTB, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-        hipLaunchKernelGGL((conv_wgrad_kernel<T, KTA, KTB, true>), dim3(static_cast<unsigned>(taps * g.chunks)), dim3(256),
-                           lds, st, g);
-      }
+      if (g.tr) rc = run(&conv_wgrad_kernel<T, KTA, KTB, true>);
     }
-    if (!g.tr) {
-      TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<T, KTA, KTB>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-      hipLaunchKernelGGL((conv_wgrad_kernel<T, KTA, KTB>), dim3(static_cast<unsigned>(taps * g.chunks)), dim3(256),
-                         lds, st, g);
-    }
+    if (!g.tr) rc = run(&conv_wgrad_kernel<T, KTA, KTB>);
+    if (rc) return rc;
   }
   const long long n = static_cast<long long>(taps) * g.CA * g.CB;
   hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3(static_cast<unsigned>(ceil_div(n, 256))), dim3(256), 0, st,
@@ -479,11 +472,8 @@ extern "C" int tfc_conv2d_wgrad(const void* a, const void* b, float* dw, int dty
   g.HA = static_cast<int>(ha); g.WA = static_cast<int>(wa); g.CA = static_cast<int>(ca);
   g.HB = static_cast<int>(hb); g.WB = static_cast<int>(wb); g.CB = static_cast<int>(cb);
   g.kh = kh; g.kw = kw; g.stride = stride;
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   WgradPlan plan;
-  if (int rc = conv2d_wgrad_plan(name, dtype, n * hb * wb, kh * kw, ca, cb, cus, &plan)) return rc;
+  if (int rc = conv2d_wgrad_plan(name, dtype, n * hb * wb, kh * kw, ca, cb, device_cus(), &plan)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   return dtype == 1 ? dispatch_wgrad<__bf16>(g, plan, transpose, dw, st) : dispatch_wgrad<float>(g, plan, transpose, dw, st);
 }

@@ -44,7 +44,7 @@
 
 #include "../../include/tfc_hip.h"
 #include "bf16_io.h"
-#include "common.h"
+#include "launch.h"
 #include "reduce_rows.h"
 
 namespace tfc {
@@ -501,24 +501,18 @@ void ssim_fill(SsimParams& p, const void* x, const void* y, int64_t height, int6
 
 template <typename T, int TILE, int NT>
 int ssim_launch_fwd(const SsimParams& p, dim3 grid, size_t lds, hipStream_t st) {
-  TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ssim_fwd_kernel<T, TILE, NT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-  hipLaunchKernelGGL((ssim_fwd_kernel<T, TILE, NT>), grid, dim3(256), lds, st, p);
-  return 0;
+  return launch(&ssim_fwd_kernel<T, TILE, NT>, grid, dim3(256), lds, st, p);
 }
 
 template <typename T, int TILE, int NT>
 int ssim_launch_bwd(const SsimParams& p, dim3 grid, size_t lds, hipStream_t st) {
-  TFC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ssim_bwd_kernel<T, TILE, NT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-  hipLaunchKernelGGL((ssim_bwd_kernel<T, TILE, NT>), grid, dim3(256), lds, st, p);
-  return 0;
+  return launch(&ssim_bwd_kernel<T, TILE, NT>, grid, dim3(256), lds, st, p);
 }
 
 // The window of the models (11 taps) has kernels of its own with the tap count a compile-time constant; every other
 // filter_size, or TFC_SSIM_RUNTIME_TAPS=1 in the environment (for a same-process comparison), takes the general ones.
 bool ssim_fixed_taps(int n) {
-  const char* e = std::getenv("TFC_SSIM_RUNTIME_TAPS");
+  const char* e = env_str("TFC_SSIM_RUNTIME_TAPS");
   return n == 11 && !(e && e[0] == '1');
 }
 

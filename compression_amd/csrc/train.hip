@@ -13,7 +13,7 @@
 //     (the first chunk of every tensor) travel in the kernel arguments, so a launch needs no upload; a workgroup looks
 //     its chunk up and streams p, g, m, v in 16-byte accesses: 16 bytes read and 12 written per parameter.
 // No LDS, no atomics, no scratch.
-#include "common.h"
+#include "launch.h"
 #include "../../include/tfc_hip.h"
 
 namespace tfc {
@@ -265,7 +265,7 @@ extern "C" int tfc_keras_adam(void* const* params, const void* const* grads, voi
     a.t[k].numel = numels[k];
     a.first[k] = static_cast<unsigned>(chunks);
     chunks += ceil_div(numels[k], ADAM_CHUNK);
-    if (chunks >= (1ll << 31)) return fail("tfc_keras_adam: more than 2^31 chunks in one launch");
+    if (chunks > kMaxGridX) return fail("tfc_keras_adam: more than 2^31 chunks in one launch");
   }
   for (int k = count; k <= ADAM_CAP; ++k) a.first[k] = static_cast<unsigned>(chunks);
   if (chunks == 0) return 0;

@@ -8,7 +8,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-HOT = ["conv3d_fwd_kernel", "conv3d_wgrad_kernel", "conv3d_pack_kernel", "conv3d_split_x_kernel", "conv3d_wgrad_sum_kernel"]
+HOT = ["conv3d_fwd_kernel", "conv3d_wgrad_kernel", "conv3d_pack_kernel", "conv_split_x_kernel", "conv3d_wgrad_sum_kernel"]
 
 
 def test_conv3d_kernels_do_not_spill():

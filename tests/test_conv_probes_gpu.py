@@ -71,7 +71,7 @@ def test_float32_rank2_equals_the_oracle_on_plane_probes(c, probe):
     check_probe(c, probe)
 
 
-# conv3d_entry runs every float32 call as six planes (conv3d_split_x_kernel by x_plane, conv3d_pack_kernel by w_plane with
+# conv3d_entry runs every float32 call as six planes (the 2-D layer's conv_split_x_kernel, conv3d_pack_kernel by w_plane with
 # planes == 6): supports (3, 3, 3) and (1, 1, 5), strides (1, 1, 1) and (1, 2, 2), both directions; the transposed
 # (1, 2, 2) case has four phases with their own tap sets, the (1, 1, 5) rows are wider than one 32-sample tile row.
 @pytest.mark.parametrize("probe", PROBES)
