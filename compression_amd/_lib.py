@@ -187,6 +187,8 @@ SIGNATURES = {
     "tfc_layer_norm_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, C.c_float, _vp]),
     "tfc_gelu_forward": (_int, [_vp, _vp, _int, _i64, _vp]),
     "tfc_gelu_backward": (_int, [_vp, _vp, _vp, _int, _i64, _vp]),
+    "tfc_integer_conv2d": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int,
+                                  _int, _vp]),
 }
 
 # the dtype argument of the C ABI: entries on float32 / bfloat16 tensors, and those that take float16 as well

@@ -10,6 +10,8 @@ from .train_ops import scale_crop_patches, scale_crop_patches_reference  # noqa:
 from .video_ops import (pack_frames, pack_frames_reference, rgb_to_ycbcr, rgb_to_ycbcr_reference,  # noqa: F401
                         unpack_frames, unpack_frames_reference, ycbcr_to_rgb, ycbcr_to_rgb_reference)
 from . import scctx_ops  # noqa: E402
+from . import integer_ops  # noqa: E402
+from .integer_ops import integer_conv2d, integer_conv2d_reference  # noqa: F401,E402
 from . import attention_ops  # noqa: E402
 from .attention_ops import (gelu, gelu_reference, layer_norm, layer_norm_reference, window_attention,  # noqa: F401,E402
                             window_attention_reference)

@@ -1233,6 +1233,28 @@ int tfc_gelu_forward(const void* x, void* y, int dtype, int64_t count, void* str
 /* Its backward: dx = g (0.5 (1 + erf(x / sqrt 2)) + x exp(-x^2 / 2) / sqrt(2 pi)). */
 int tfc_gelu_backward(const void* x, const void* g, void* dx, int dtype, int64_t count, void* stream);
 
+/* The integer convolution layer of an integer network ("Integer Networks for Data Compression with Latent-Variable
+ * Models", Balle, Johnston and Minnen, ICLR 2019, sections 2-3).  The definition is this library's own; parity with
+ * anyone's checkpoints is not pinned.  NHWC; the geometry is exactly tfc_conv2d_down's (up = 0: zero padding (k / 2,
+ * (k - 1) / 2), out = ceil(in / stride)) or tfc_conv2d_up's (up = 1: y[q s + phi] = sum_i x[i] w[phi + (q - i) s +
+ * k / 2], out = in * stride), zeros outside the image, stride 1 or 2, any kh x kw from 1 to 9.
+ *   v[n,p,o] = bias[o] + sum over taps t and i < cin of W[t,i,o] * x[n, src(p,t), i]        (exact, in int32)
+ *   y[n,p,o] = min(max(floor((v + floor(c[o] / 2)) / c[o]), 0), out_max)                   (stored as uint8)
+ * Both clamps are at or above 0: a negative v gives 0 and the division is only ever one of non-negative integers.
+ *   x DEV [n, h, wd, cin]: int8 -128 ... 127 (x_unsigned = 0) or uint8 0 ... 255 (x_unsigned = 1)
+ *   w DEV int8 [kh, kw, cout, cin] -128 ... 127: the layer's HWIO kernel with its last two axes swapped, so that the
+ *     cin bytes of one (tap, output channel) are contiguous
+ *   bias DEV int32 [cout], |bias| <= 2^29;  divisor DEV int32 [cout], 1 <= c <= 2^24 (the caller's duty: the values
+ *     are not read on the host);  out_max 1 ... 255;  y DEV uint8 [n, oh, ow, cout], WRITTEN
+ * cin must be a multiple of 32 and kh * kw * cin at most 32768: then 32768 * 128 * 255 < 2^30 and no intermediate
+ * leaves int32, in any order of summation: the result is the same bytes on every device, build and tiling.  The kernel
+ * (csrc/integer_conv.hip) sums on v_mfma_i32_16x16x64_i8, carries uint8 activations as a - 128 (zeros outside the
+ * image included) with 128 * sum(W) added back, and divides with the exact unsigned division.  Every scalar argument
+ * is checked on the host before the device is touched.  x and w 16-byte aligned; y 4-byte aligned where cout % 4 == 0. */
+int tfc_integer_conv2d(const void* x, int x_unsigned, const int8_t* w, const int32_t* bias, const int32_t* divisor,
+                       uint8_t* y, int64_t n, int64_t h, int64_t wd, int64_t cin, int64_t cout, int kh, int kw,
+                       int stride, int up, int out_max, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
