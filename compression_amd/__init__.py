@@ -30,6 +30,8 @@ from .ops.checkerboard_ops import (CHECKER_TAPS, CheckerboardParams, Checkerboar
 from .ops.scctx_ops import (SpaceChannelParams, SpaceChannelScan, scctx_decode, scctx_encode,  # noqa: F401
                             scctx_parameters, scctx_parameters_reference, scctx_place, scctx_scan,
                             scctx_scan_reference)
+from .ops.mixture_ops import (mixture_bits, mixture_bits_reference, mixture_cdf, mixture_cdf_reference,  # noqa: F401
+                              mixture_decode, mixture_encode, MixtureStrings)
 from .ops.round_ops import round_st, soft_round, soft_round_conditional_mean, soft_round_inverse  # noqa: F401
 from .datasets import *  # noqa: F401,F403
 from .datasets.clip_dataset import ClipDataset  # noqa: F401

@@ -189,6 +189,13 @@ SIGNATURES = {
     "tfc_gelu_backward": (_int, [_vp, _vp, _vp, _int, _i64, _vp]),
     "tfc_integer_conv2d": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int,
                                   _int, _vp]),
+    "tfc_mixture_cdf": (_int, [_vp, _vp, _vp, _int, _i64, _int, _int, _vp, _vp]),
+    "tfc_mixture_blob_capacity": (_i64, [_i64, _i64, _i64]),
+    "tfc_mixture_encode": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tfc_mixture_decode": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp,
+                                  _vp]),
+    "tfc_mixture_bits_forward": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _int, _i64, _i64, _vp, _vp]),
+    "tfc_mixture_bits_backward": (_int, [_vp, _vp, _vp, _vp, _int, _int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 # the dtype argument of the C ABI: entries on float32 / bfloat16 tensors, and those that take float16 as well

@@ -22,25 +22,10 @@
 #include "bf16_io.h"
 #include "bits_common.h"
 #include "laplace_tail.h"
+#include "normal_log_cdf.h"
 
 namespace tfc {
 namespace {
-
-constexpr float kInvSqrt2 = 0.70710678118654752f;
-constexpr float kLogSqrt2Pi = 0.91893853320467274f;
-
-__device__ inline float log_ndtr(float z) {
-  if (z < -1.f) return __logf(0.5f * erfcxf(-z * kInvSqrt2)) - 0.5f * z * z;
-  return log1pf(-0.5f * erfcf(z * kInvSqrt2));
-}
-
-// log( Phi(zu) - Phi(zl) ), zu > zl
-__device__ inline float log_interval_normal(float zu, float zl) {
-  const bool right = zu > 0.f;                         // logsf(zu) < logcdf(zu)
-  const float big = right ? log_ndtr(-zl) : log_ndtr(zu);
-  const float small = right ? log_ndtr(-zu) : log_ndtr(zl);
-  return log1pf(-__expf(small - big)) + big;
-}
 
 struct NnParams {
   const void* y;

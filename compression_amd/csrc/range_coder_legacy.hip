@@ -37,28 +37,6 @@ __device__ inline long long cdf_row_of(const Broadcast& b, long long k) {
   return off;
 }
 
-// RangeEncoder::Finalize (cc/lib/range_coder.cc:266-307) behind the digits already stored:
-// returns the stream length.  One lane.
-__device__ inline unsigned int finalize_bytes(const EncoderState& st, const DigitSink& o, uint8_t* out) {
-  unsigned int n = o.nbytes;
-  uint8_t* dst = out + n;
-  if (st.pend_digit != 0) {
-    dst[0] = (st.pend_digit >> 8) & 0xFF; ++n;
-    if ((st.pend_digit & 0xFF) != 0) { dst[1] = st.pend_digit & 0xFF; ++n; }
-  } else if (st.base != 0) {
-    const unsigned int top = st.base + st.span_m1;
-    const unsigned int r24 = ((st.base - 1) >> 24) + 1;
-    if (r24 <= (top >> 24)) {
-      dst[0] = r24 & 0xFF; ++n;
-    } else {
-      const unsigned int r16 = ((st.base - 1) >> 16) + 1;
-      dst[0] = (r16 >> 8) & 0xFF; ++n;
-      if ((r16 & 0xFF) != 0) { dst[1] = r16 & 0xFF; ++n; }
-    }
-  }
-  return n;
-}
-
 struct LegacyEncParams {
   const int16_t* data;
   const int32_t* cdf;

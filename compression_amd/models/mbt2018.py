@@ -177,6 +177,33 @@ class HyperpriorContextModel(torch.nn.Module):
         """The flat y strings of `decompress` -> y_hat; raises when their count is not the scheme's."""
         raise NotImplementedError
 
+    # --- the three places where the context scheme meets the entropy model; a scheme whose likelihood is not
+    # (mu, indexes) over the table set (models/cstk2020.py) overrides these and `_models` instead of the four above ------
+    def _rate_context(self, em_y, y, psi, training):
+        """(y_bits, y_hat) of `forward` with the context model."""
+        if training:
+            # one noise sample: the same y + u feeds the context convolution, the rate and the synthesis
+            u = torch.rand_like(y) - 0.5
+            y_tilde = y + u
+            mu, indexes = self._training_parameters(y_tilde, psi)
+            _, y_bits = em_y(y.float(), indexes.float(), loc=mu.float(), training=True, noise=u.float())
+            return y_bits, y_tilde
+        scan = self._scan(y.float(), psi.float(), self.context_params())
+        _, y_bits = em_y(y.float(), scan.index_float, loc=scan.mu, training=False)
+        return y_bits, scan.y_hat.to(self.compute_dtype)
+
+    def _compress_context(self, y, psi):
+        """(y_strings, y_hat, extras) of `compress`: `extras` is a tuple of further int32 container entries, stored
+        between the shapes and the strings and handed back to `_decompress_context`."""
+        y = y.float().contiguous()
+        scan = self._scan(y, psi.float(), self.context_params())
+        return self._write_strings(y, scan), scan.y_hat, ()
+
+    def _decompress_context(self, y_strings, psi, batch, y_shape, extras):
+        """y_hat of `decompress` from the y strings as the container holds them."""
+        y_strings = np.asarray(y_strings, dtype=object).reshape(-1)
+        return self._read_strings(y_strings, psi.float(), batch, y_shape)
+
     # ------------------------------------------------------------------------------------------------------------------
     def forward(self, x, training=True, return_y_hat=False):
         """x [B, H, W, 3] on the 0...255 scale -> (loss, bpp, mse) (and y_hat on request)."""
@@ -195,17 +222,8 @@ class HyperpriorContextModel(torch.nn.Module):
             means, indexes = psi[..., :M].contiguous(), psi[..., M:].contiguous()
             _, y_bits = em_y(y, indexes, loc=means, training=training)
             y_hat = em_y.quantize(y, loc=means).to(self.compute_dtype)
-        elif training:
-            # one noise sample: the same y + u feeds the context convolution, the rate and the synthesis
-            u = torch.rand_like(y) - 0.5
-            y_tilde = y + u
-            mu, indexes = self._training_parameters(y_tilde, psi)
-            _, y_bits = em_y(y.float(), indexes.float(), loc=mu.float(), training=True, noise=u.float())
-            y_hat = y_tilde
         else:
-            scan = self._scan(y.float(), psi.float(), self.context_params())
-            _, y_bits = em_y(y.float(), scan.index_float, loc=scan.mu, training=False)
-            y_hat = scan.y_hat.to(self.compute_dtype)
+            y_bits, y_hat = self._rate_context(em_y, y, psi, training)
         x_hat = self.synthesis_transform(y_hat)[:, :x.shape[1], :x.shape[2], :]
         bpp = (y_bits.sum() + z_bits.sum()) / num_pixels
         mse = torch.mean((x.float() - x_hat.float()) ** 2).to(bpp.dtype)
@@ -234,21 +252,22 @@ class HyperpriorContextModel(torch.nn.Module):
         # the closed loop uses quantize() in place of a decode of the string (as ms2020's compress does)
         z_hat = self.em_z.quantize(z).to(self.compute_dtype)
         psi = self._psi(z_hat, y_shape)
+        extras = ()
         if self.context:
-            y = y.float().contiguous()
-            scan = self._scan(y, psi.float(), self.context_params())
-            y_strings = self._write_strings(y, scan)
-            y_hat = scan.y_hat
+            y_strings, y_hat, extras = self._compress_context(y, psi)
         else:
             means, indexes = psi[..., :M].contiguous(), psi[..., M:].contiguous()
             y_strings = self.em_y.compress(y, indexes, loc=means)
             y_hat = self.em_y.quantize(y, loc=means)
-        packed = (x_shape, y_shape, z_shape, z_string, y_strings)
+        packed = (x_shape, y_shape, z_shape) + tuple(extras) + (z_string, y_strings)
         return packed + (self._reconstruct(y_hat, x_shape),) if return_reconstruction else packed
 
-    @torch.no_grad()
     def decompress(self, x_shape, y_shape, z_shape, z_string, y_strings):
         """The arguments `compress` returned -> uint8 [B, H, W, 3]."""
+        return self._decompress(x_shape, y_shape, z_shape, z_string, y_strings, ())
+
+    @torch.no_grad()
+    def _decompress(self, x_shape, y_shape, z_shape, z_string, y_strings, extras):
         if self.em_y is None:
             raise RuntimeError("decompress needs init_compression()")
         x_shape, y_shape, z_shape = (tuple(int(v) for v in s) for s in (x_shape, y_shape, z_shape))
@@ -258,10 +277,10 @@ class HyperpriorContextModel(torch.nn.Module):
         z_hat = self.em_z.decompress(z_string, z_shape).to(self.compute_dtype)
         batch = z_hat.shape[0]
         psi = self._psi(z_hat, y_shape)
-        y_strings = np.asarray(y_strings, dtype=object).reshape(-1)
         if self.context:
-            y_hat = self._read_strings(y_strings, psi.float(), batch, y_shape)
+            y_hat = self._decompress_context(y_strings, psi, batch, y_shape, extras)
         else:
+            y_strings = np.asarray(y_strings, dtype=object).reshape(-1)
             means, indexes = psi[..., :M].contiguous(), psi[..., M:].contiguous()
             y_hat = self.em_y.decompress(y_strings, indexes, loc=means)
         return self._reconstruct(y_hat, x_shape)

@@ -1255,6 +1255,69 @@ int tfc_integer_conv2d(const void* x, int x_unsigned, const int8_t* w, const int
                        uint8_t* y, int64_t n, int64_t h, int64_t wd, int64_t cin, int64_t cout, int kh, int kw,
                        int stride, int up, int out_max, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Gaussian-mixture entropy model: CDFs evaluated where they are coded      */
+/* ------------------------------------------------------------------------ */
+/* The discretized Gaussian mixture likelihood of "Learned Image Compression with Discretized Gaussian Mixture
+ * Likelihoods and Attention Modules" (Cheng, Sun, Takeuchi, Katto, CVPR 2020): every element has K weights (as
+ * logits), K means and K scales, K in [1, 4].  No table set spans that, so these entries take the parameters
+ * themselves.  The definition (csrc/mixture_cdf.h) is this library's own; parity with anyone's
+ * checkpoints is not pinned.  Symbols are rint(y) (no mean is subtracted), coded inside a window [lo, lo + L - 1],
+ * 1 <= L <= 4096, |lo| <= 2^22, at precision 16:
+ *   c_0 = 0,  c_L = 65536,  c_b = 2 b + floor(F(lo + b - 1/2) (65536 - 2 L)),  F(t) = sum_k softmax(logits)_k
+ *   Phi((t - loc_k) / scale_k), F in float32 in one fixed operation order and clamped to [0, 1].
+ * The parameters are DEV float32 PLANES [K][n]: plane k holds component k of every element.  scale > 0 and finite is
+ * the caller's duty; any such value is safe.  One call takes at most 2^23 streams (or strings).  Strings decode on the
+ * build and device kind that encoded them. */
+
+/* The table the coder uses, dumped: cdf DEV int32 [n, L + 1].  Replaces a host-built table per element (the
+ * reference has none: its conditional models index a fixed table set, python/entropy_models/continuous_indexed.py). */
+int tfc_mixture_cdf(const float* logits, const float* loc, const float* scale, int k, int64_t n, int lo, int len,
+                    int32_t* cdf, void* stream);
+
+/* Bytes of the `blob` tfc_mixture_encode needs (every stream's worst case); -1 and tfc_last_error on bad sizes. */
+int64_t tfc_mixture_blob_capacity(int64_t batch, int64_t elems, int64_t stream_symbols);
+
+/* sym DEV int32 [batch, elems] (absolute symbols; one outside its entry's window is coded as the nearest end), cut
+ * into ceil(elems / stream_symbols) streams per batch entry, the last one shorter where it has to be; parameter
+ * planes [K][batch * elems]; lo, len DEV int32 [batch].  One wave per stream.  Writes the strings back to back into
+ * blob DEV (tfc_mixture_blob_capacity bytes) and offsets DEV int64 [streams + 1], as tfc_encoder_result describes the
+ * batched encoders' output; *overflow DEV uint32 is 0 unless a stream outgrew its slab (an internal error).  Enqueues
+ * only.  Stands in for RangeEncode over a per-element table (cc/kernels/range_coding_kernels.cc:60-379): the strings
+ * are those of tfc_range_encode(sym - lo, tfc_mixture_cdf(...), 16), byte for byte. */
+int tfc_mixture_encode(const int32_t* sym, const float* logits, const float* loc, const float* scale, int k,
+                       int64_t batch, int64_t elems, int64_t stream_symbols, const int32_t* lo, const int32_t* len,
+                       uint8_t* blob, int64_t* offsets, uint32_t* overflow, void* stream);
+
+/* The inverse: string j (blob, offsets DEV int64 [nstrings + 1]) is stream stream_index[j] of the layout above
+ * (stream_index DEV int32 [nstrings], or NULL when nstrings is the number of streams and string j is stream j), so a
+ * subset of the streams, or the streams in another order, can be decoded (no stream twice: the caller's duty); the symbols of a decoded stream go to its
+ * place in out DEV int32 [batch, elems], the rest of out is left alone.  ok DEV uint8 [nstrings]: RangeDecoder::
+ * Finalize's verdict (cc/lib/range_coder.h:144-169), and 0 as well where the string ends before digits the decoder
+ * consumed while no carry was pending, or stream_index[j] names no stream.  The decoder reads zeros behind the end of
+ * a string and every symbol it writes is inside the window, whatever the bytes are.  Stands in for RangeDecode
+ * (range_coding_kernels.cc:232-379) over a per-element table. */
+int tfc_mixture_decode(const uint8_t* blob, const int64_t* offsets, const int32_t* stream_index, int64_t nstrings,
+                       const float* logits, const float* loc, const float* scale, int k, int64_t batch, int64_t elems,
+                       int64_t stream_symbols, const int32_t* lo, const int32_t* len, int32_t* out, uint8_t* ok,
+                       void* stream);
+
+/* The training-time likelihood of the same mixture, fused — python/distributions/uniform_noise.py:117-156
+ * (UniformNoiseAdapter) over a MixtureSameFamily of normals, i.e. NoisyNormalMixture:
+ *   y_hat = y + noise (noise NULL: y itself);  lp_k = log(Phi((y_hat + .5 - loc_k) / scale_k) - Phi((y_hat - .5 -
+ *   loc_k) / scale_k));  log p = logsumexp_k(log_softmax(logits)_k + lp_k);  bits[unit] = -sum log p / ln 2,
+ * summed in a fixed order.  y, noise, y_hat DEV [units, elems] dtype (0 f32, 1 bf16); parameter planes DEV f32
+ * [K][units * elems]; bits DEV f32 [units].  No Laplace tail, no expected gradients. */
+int tfc_mixture_bits_forward(const void* y, const void* noise, const float* logits, const float* loc,
+                             const float* scale, int k, void* y_hat, int dtype, int64_t units, int64_t elems,
+                             float* bits, void* stream);
+/* Its gradients in one launch, through the responsibilities softmax_k(logits_k + lp_k): dy DEV [units, elems] dtype
+ * (through the likelihood; the caller adds the straight path), dlogits, dloc, dscale DEV f32 planes [K][units * elems],
+ * all overwritten. */
+int tfc_mixture_bits_backward(const void* y_hat, const float* logits, const float* loc, const float* scale, int k,
+                              int dtype, int64_t units, int64_t elems, const float* gbits, void* dy, float* dlogits,
+                              float* dloc, float* dscale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
