@@ -37,7 +37,8 @@
 //
 // The taps arrive at run time (n <= 31), in the kernel arguments: a wave-uniform index into them is a scalar load.
 // T = 32 for n <= 11 (forward 36 KB, backward 63 KB of LDS), 16 above (backward up to 103 KB).  n = 11, the window of
-// every model, also has kernels with the tap count as a compile-time constant (see ssim_fwd_kernel).
+// every model, also has kernels with the tap count as a compile-time constant (see ssim_fwd_kernel).  These numbers
+// are the constants of ssim_params.h, which the tests read to place their shapes on the tile seams.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -46,11 +47,12 @@
 #include "bf16_io.h"
 #include "launch.h"
 #include "reduce_rows.h"
+#include "ssim_params.h"
 
 namespace tfc {
 namespace {
 
-constexpr int kSsimMaxTaps = 31;
+constexpr int kSsimMaxTaps = SSIM_MAX_TAPS;
 
 struct SsimParams {
   const void* x;
@@ -149,7 +151,9 @@ __host__ __device__ constexpr int ssim_fwd_stride(int n) {
 template <typename T, int TILE, int NT>
 __global__ void __launch_bounds__(256) ssim_fwd_kernel(SsimParams p) {
   extern __shared__ __attribute__((aligned(16))) float ssim_lds[];
-  static_assert(NT == 0 || TILE == 32, "the blocked passes map 256 threads onto a 32 x 32 tile");
+  static_assert(NT == 0 || (TILE == SSIM_TILE_SMALL_N && TILE * TILE == 4 * 256),
+                "the blocked passes map 256 threads onto a 32 x 32 tile");
+  static_assert(SSIM_FIXED_TAPS <= SSIM_TILE_SMALL_N_MAX, "the unrolled kernels run on the tile of the small windows");
   const int n = NT ? NT : p.n, IW = TILE + n - 1; // the staged tile is IW x IW, its rows IWP apart
   const int IWP = ssim_fwd_stride<TILE, NT>(n);
   float* sx = ssim_lds;
@@ -454,10 +458,10 @@ __global__ void __launch_bounds__(256) ssim_bwd_kernel(SsimParams p) {
   }
 }
 
-int ssim_tile(int n) { return n <= 11 ? 32 : 16; }
+int ssim_tile(int n) { return n <= SSIM_TILE_SMALL_N_MAX ? SSIM_TILE_SMALL_N : SSIM_TILE_LARGE_N; }
 
 size_t ssim_fwd_lds(int n, int tile, bool fixed) {
-  const size_t iw = tile + n - 1, iwp = fixed ? ssim_fwd_stride<32, 11>(n) : iw;
+  const size_t iw = tile + n - 1, iwp = fixed ? ssim_fwd_stride<SSIM_TILE_SMALL_N, SSIM_FIXED_TAPS>(n) : iw;
   return sizeof(float) * (2 * iw * iwp + 4 * iw * tile + 4);
 }
 
@@ -481,8 +485,8 @@ int ssim_validate(const char* name, const void* x, const void* y, int dtype, int
   if (height > (1 << 20) || width > (1 << 20)) return fail("%s: height and width must be at most 2^20", name);
   if (!std::isfinite(c1) || !std::isfinite(c2) || c1 < 0.f || c2 <= 0.f)
     return fail("%s: c1 must be finite and non-negative, c2 finite and positive", name);
-  // (16 x 16 is the smallest tile)
-  if (ceil_div(height, 16) * ceil_div(width, 16) * channels * batch > 0x7fffffffll)
+  // (the smaller tile bounds the count)
+  if (ceil_div(height, SSIM_TILE_LARGE_N) * ceil_div(width, SSIM_TILE_LARGE_N) * channels * batch > 0x7fffffffll)
     return fail("%s: batch x channels x tiles exceeds the 2^31 - 1 workgroups of a launch", name);
   if (!x || !y) return fail("%s: x and y must not be null", name);
   return 0;
@@ -513,7 +517,7 @@ int ssim_launch_bwd(const SsimParams& p, dim3 grid, size_t lds, hipStream_t st) 
 // filter_size, or TFC_SSIM_RUNTIME_TAPS=1 in the environment (for a same-process comparison), takes the general ones.
 bool ssim_fixed_taps(int n) {
   const char* e = env_str("TFC_SSIM_RUNTIME_TAPS");
-  return n == 11 && !(e && e[0] == '1');
+  return n == SSIM_FIXED_TAPS && !(e && e[0] == '1');
 }
 
 #define TFC_SSIM_DISPATCH_T(LAUNCH, TILE, NT, ...)                                          \
@@ -521,12 +525,13 @@ bool ssim_fixed_taps(int n) {
    : dtype == 1 ? LAUNCH<unsigned short, TILE, NT>(__VA_ARGS__)                             \
    : dtype == 2 ? LAUNCH<_Float16, TILE, NT>(__VA_ARGS__)                                   \
                 : LAUNCH<unsigned char, TILE, NT>(__VA_ARGS__))
-#define TFC_SSIM_DISPATCH(LAUNCH, ...)                                                      \
-  do {                                                                                      \
-    const int rc__ = fixed       ? TFC_SSIM_DISPATCH_T(LAUNCH, 32, 11, __VA_ARGS__)         \
-                     : tile == 32 ? TFC_SSIM_DISPATCH_T(LAUNCH, 32, 0, __VA_ARGS__)         \
-                                  : TFC_SSIM_DISPATCH_T(LAUNCH, 16, 0, __VA_ARGS__);        \
-    if (rc__) return rc__;                                                                  \
+#define TFC_SSIM_DISPATCH(LAUNCH, ...)                                                                \
+  do {                                                                                                \
+    const int rc__ =                                                                                  \
+        fixed                       ? TFC_SSIM_DISPATCH_T(LAUNCH, SSIM_TILE_SMALL_N, SSIM_FIXED_TAPS, __VA_ARGS__) \
+        : tile == SSIM_TILE_SMALL_N ? TFC_SSIM_DISPATCH_T(LAUNCH, SSIM_TILE_SMALL_N, 0, __VA_ARGS__)  \
+                                    : TFC_SSIM_DISPATCH_T(LAUNCH, SSIM_TILE_LARGE_N, 0, __VA_ARGS__); \
+    if (rc__) return rc__;                                                                            \
   } while (0)
 
 }  // namespace

@@ -7,7 +7,8 @@ is unpinned against TensorFlow itself.
 `ssim` / `ssim_multiscale` run one launch of csrc/ssim.hip per scale, forward and backward, on device tensors of dtype
 uint8, float32, bfloat16 or float16.  `ssim_reference` / `ssim_multiscale_reference` are the same functions composed op
 by op from torch's conv2d, pad and avg_pool2d, on any device, in float32 or float64: the yardstick of the accuracy
-tests and of the timing, used by no model path."""
+tests and of the timing, used by no model path.  `scale_reference` is that composition for one scale pass, in the layout
+of `scale_forward`; `SSIM_CONSTANTS` are the kernels' tile sides and tap limits, read from csrc/ssim_params.h."""
 from __future__ import annotations
 
 import ctypes as C
@@ -20,10 +21,12 @@ import torch
 from .. import _lib
 from .._lib import ptr as _ptr
 
-__all__ = ["ssim", "ssim_multiscale", "ssim_reference", "ssim_multiscale_reference", "MSSSIM_POWER_FACTORS"]
+__all__ = ["ssim", "ssim_multiscale", "ssim_reference", "ssim_multiscale_reference", "scale_reference",
+           "MSSSIM_POWER_FACTORS", "SSIM_CONSTANTS"]
 
 MSSSIM_POWER_FACTORS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
-MAX_FILTER_SIZE = 31                      # csrc/ssim.hip: the taps travel in the kernel arguments
+SSIM_CONSTANTS = _lib.kernel_constants("ssim_params.h", ("SSIM",))
+MAX_FILTER_SIZE = SSIM_CONSTANTS["SSIM_MAX_TAPS"]       # csrc/ssim.hip: the taps travel in the kernel arguments
 
 _DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 3}
 
@@ -99,6 +102,24 @@ def _downsample_reference(t):
     if h % 2 or w % 2:
         t = torch.nn.functional.pad(t, (0, w % 2, 0, h % 2), mode="replicate")
     return torch.nn.functional.avg_pool2d(t, 2)
+
+
+def scale_reference(x, y, taps, c1, c2, pool):
+    """The tensor-op twin of `scale_forward`: x, y [B, H, W, C] -> (means [B * C, 2], pooled_x, pooled_y) in its layout
+    (the pooled pair [B * C, ceil(H / 2), ceil(W / 2), 1], or None without `pool`).  Any device; float64 inputs stay
+    float64, anything else is computed in float32.  Differentiable in both images."""
+    ft = torch.float64 if x.dtype == torch.float64 else torch.float32
+    b, h, w, c = x.shape
+    px, _ = _planes_nchw(x, ft)
+    py, _ = _planes_nchw(y, ft)
+    g = torch.tensor([float(v) for v in taps], dtype=torch.float64)
+    kernel = torch.outer(g, g).to(ft)[None, None].repeat(c, 1, 1, 1).to(x.device)
+    value, cs = _scale_reference(px, py, kernel, c1, c2)
+    means = torch.stack((value, cs), dim=-1).reshape(b * c, 2)
+    if not pool:
+        return means, None, None
+    halved = lambda t: _downsample_reference(t).reshape(b * c, (h + 1) // 2, (w + 1) // 2, 1)      # noqa: E731
+    return means, halved(px), halved(py)
 
 
 def ssim_reference(img1, img2, max_val, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03):

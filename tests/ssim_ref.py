@@ -1,5 +1,6 @@
 """Float64 NumPy oracle of SSIM and multiscale SSIM, written from the definition in DESIGN.md (TensorFlow's
-`tf.image.ssim` / `tf.image.ssim_multiscale`, restated there) and from nothing in the package, plus the image-like
+`tf.image.ssim` / `tf.image.ssim_multiscale`, restated there) and from nothing in the package, one scale pass of it with
+its closed-form gradient (`scale_pass`, `scale_pass_gradients`: what one kernel launch computes), plus the image-like
 test inputs the SSIM tests share.  Not a test module."""
 import numpy as np
 
@@ -20,14 +21,19 @@ def valid_filter(a, g):
     return sum(g[k] * rows[..., :, k:k + w - n + 1] for k in range(n))
 
 
-def scale_maps(x, y, max_val, g, k1=0.01, k2=0.03):
-    """x, y [..., H, W] float64 -> (ssim_plane, cs_plane), each [...]."""
-    c1, c2 = (k1 * max_val) ** 2, (k2 * max_val) ** 2
+def position_maps(x, y, g, c1, c2):
+    """x, y [..., H, W] float64 -> (l cs, cs) at the valid positions, each [..., H - n + 1, W - n + 1]."""
     mu1, mu2 = valid_filter(x, g), valid_filter(y, g)
     s, p = valid_filter(x * x + y * y, g), valid_filter(x * y, g)
     lum = (2 * mu1 * mu2 + c1) / (mu1 ** 2 + mu2 ** 2 + c1)
     cs = (2 * p - 2 * mu1 * mu2 + c2) / (s - (mu1 ** 2 + mu2 ** 2) + c2)        # symmetric in x, y to the bit
-    return (lum * cs).mean(axis=(-2, -1)), cs.mean(axis=(-2, -1))
+    return lum * cs, cs
+
+
+def scale_maps(x, y, max_val, g, k1=0.01, k2=0.03):
+    """x, y [..., H, W] float64 -> (ssim_plane, cs_plane), each [...]."""
+    lcs, cs = position_maps(x, y, g, (k1 * max_val) ** 2, (k2 * max_val) ** 2)
+    return lcs.mean(axis=(-2, -1)), cs.mean(axis=(-2, -1))
 
 
 def halve(a):
@@ -38,6 +44,70 @@ def halve(a):
     if w % 2:
         a = np.concatenate([a, a[..., :, -1:]], axis=-1)
     return 0.25 * (a[..., 0::2, 0::2] + a[..., 0::2, 1::2] + a[..., 1::2, 0::2] + a[..., 1::2, 1::2])
+
+
+def scale_pass(x, y, taps, c1, c2):
+    """One scale of DESIGN.md §13 on planes x, y [planes, H, W]: -> (means [planes, 2] = (ssim_plane, cs_plane), halved x,
+    halved y [planes, ceil(H / 2), ceil(W / 2)]).  The arithmetic of `scale_maps`, with C1 and C2 given."""
+    x, y, g = np.asarray(x, np.float64), np.asarray(y, np.float64), np.asarray(taps, np.float64)
+    lcs, cs = position_maps(x, y, g, c1, c2)
+    return np.stack([lcs.mean(axis=(-2, -1)), cs.mean(axis=(-2, -1))], axis=-1), halve(x), halve(y)
+
+
+def full_correlation(a, g):
+    """The adjoint of `valid_filter`: a [..., OH, OW] -> [..., OH + n - 1, OW + n - 1], out[i, j] = sum g[k] g[l] a[i - k, j - l]."""
+    n = len(g)
+    oh, ow = a.shape[-2:]
+    rows = np.zeros(a.shape[:-2] + (oh + n - 1, ow))
+    for k in range(n):
+        rows[..., k:k + oh, :] += g[k] * a
+    out = np.zeros(a.shape[:-2] + (oh + n - 1, ow + n - 1))
+    for k in range(n):
+        out[..., :, k:k + ow] += g[k] * rows
+    return out
+
+
+def halve_adjoint(gp, h, w):
+    """The adjoint of `halve` for an H x W plane: a quarter of gp[i // 2, j // 2], twice that on the last row / column of
+    an odd side (the repeated one folds back onto it)."""
+    up = np.repeat(np.repeat(np.asarray(gp, np.float64), 2, axis=-2), 2, axis=-1)[..., :h, :w] * 0.25
+    if h % 2:
+        up[..., -1, :] *= 2.0
+    if w % 2:
+        up[..., :, -1] *= 2.0
+    return up
+
+
+def scale_pass_gradients(x, y, taps, c1, c2, g_means, g_px=None, g_py=None):
+    """(dx, dy) of  sum(g_means * means) + sum(g_px * halved x) + sum(g_py * halved y)  for `scale_pass`, in closed form:
+    with V = (g0 l cs + g1 cs) / positions at every position, a1 = dV/dmu1, a2 = dV/dmu2, b = dV/dS, c = dV/dP and F' the
+    full correlation with the window,
+        dx = F'(a1) + 2 x F'(b) + y F'(c),   dy = F'(a2) + 2 y F'(b) + x F'(c),
+    plus the adjoint of the pool where g_px / g_py is given."""
+    x, y, g = np.asarray(x, np.float64), np.asarray(y, np.float64), np.asarray(taps, np.float64)
+    g_means = np.asarray(g_means, np.float64)
+    h, w = x.shape[-2:]
+    mu1, mu2 = valid_filter(x, g), valid_filter(y, g)
+    s, p = valid_filter(x * x + y * y, g), valid_filter(x * y, g)
+    count = mu1.shape[-2] * mu1.shape[-1]
+    ld = mu1 ** 2 + mu2 ** 2 + c1
+    lum = (2 * mu1 * mu2 + c1) / ld
+    cd = s - (mu1 ** 2 + mu2 ** 2) + c2
+    cs = (2 * p - 2 * mu1 * mu2 + c2) / cd
+    wa, wb = g_means[..., 0, None, None] / count, g_means[..., 1, None, None] / count
+    v_l, v_cs = wa * cs, wa * lum + wb                                           # dV/dl, dV/dcs
+    a1 = v_l * (2 * mu2 - 2 * mu1 * lum) / ld + v_cs * (2 * mu1 * cs - 2 * mu2) / cd
+    a2 = v_l * (2 * mu1 - 2 * mu2 * lum) / ld + v_cs * (2 * mu2 * cs - 2 * mu1) / cd
+    b = -v_cs * cs / cd
+    c = 2 * v_cs / cd
+    fb, fc = full_correlation(b, g), full_correlation(c, g)
+    dx = full_correlation(a1, g) + 2 * x * fb + y * fc
+    dy = full_correlation(a2, g) + 2 * y * fb + x * fc
+    if g_px is not None:
+        dx = dx + halve_adjoint(g_px, h, w)
+    if g_py is not None:
+        dy = dy + halve_adjoint(g_py, h, w)
+    return dx, dy
 
 
 def _planes(img):
