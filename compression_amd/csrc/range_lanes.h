@@ -294,26 +294,26 @@ struct EncWaveLds {
 // ripple through) and lanes that come in with such a run (RN != 0, tested by the caller).
 // Fixed temporaries v140-v175:
 // v[124:139] the block's values, v[148:149] / v[150:151] rows (cdf - 2, info), v[152:153] v[154:155] /
-// v[156:157] v[158:159] (lo, 0) (hi, 0) of even / odd steps.
+// v[156:157] v[158:159] / v[176:177] v[178:179] (lo << 16, 0) (hi << 16, 0) of the three rotating sets: the cdf entries are
+// read into the upper halves (ds_read_u16_d16_hi; the block's head zeroes all twelve registers), so that the upper dword
+// of (c << 16) S + (c << 16) is the bound (c (S + 1)) >> 16 itself — one v_mad_u64_u32 per bound and no shift behind it.
 #define TFC_LENC_A(VAL, R0, R1, LO, HI, NEXTROW, NP)                                        \
   NEXTROW                                                                                 \
   "v_and_b32 v171, 0x7fffffff, v" #R1 "\n\t"                                              \
   "v_cmp_ge_u32 " NP(VAL)                                                                 \
   "v_min_u32 v172, v" #VAL ", v171\n\t"                                                   \
   "v_lshl_add_u32 v172, v172, 1, v" #R0 "\n\t"                                            \
-  "ds_read_u16 v" #LO ", v172 offset:2\n\t"                                               \
-  "ds_read_u16 v" #HI ", v172 offset:4\n\t"
+  "ds_read_u16_d16_hi v" #LO ", v172 offset:2\n\t"                                        \
+  "ds_read_u16_d16_hi v" #HI ", v172 offset:4\n\t"
 #define TFC_LENC_B(LO, LOH, HI, HIH, PRE)                                                 \
   PRE                                                                                     \
   "v_mad_u64_u32 v[160:161], s[52:53], v" #LO ", %[S], v[" #LO ":" #LOH "]\n\t"             \
   "v_mad_u64_u32 v[162:163], s[52:53], v" #HI ", %[S], v[" #HI ":" #HIH "]\n\t"             \
-  "v_alignbit_b32 v160, v161, v160, 16\n\t"                                               \
-  "v_alignbit_b32 v162, v163, v162, 16\n\t"                                               \
-  "v_add_u32 v162, -1, v162\n\t"                                                          \
-  "v_min_u32 v162, v162, %[S]\n\t"                                                        \
-  "v_add_co_u32 v164, vcc, %[BASE], v160\n\t"                                             \
+  "v_add_u32 v163, -1, v163\n\t"                                                          \
+  "v_min_u32 v163, v163, %[S]\n\t"                                                        \
+  "v_add_co_u32 v164, vcc, %[BASE], v161\n\t"                                             \
   "v_addc_co_u32 v167, vcc, 0, %[H], vcc\n\t"                                             \
-  "v_sub_u32 v165, v162, v160\n\t"                                                        \
+  "v_sub_u32 v165, v163, v161\n\t"                                                        \
   "v_sub_u32 v173, v167, %[H]\n\t"                                                        \
   "v_cmp_gt_u32 vcc, %[K64K], v165\n\t"                                                   \
   "v_cndmask_b32 v174, 0, 1, vcc\n\t"                                                     \
@@ -357,8 +357,9 @@ struct EncWaveLds {
   "ds_read2_b32 v[136:137], %[VP] offset0:12 offset1:13\n\t" \
   "ds_read2_b32 v[138:139], %[VP] offset0:14 offset1:15\n\t" \
   TFC_LENC_ROW_A(0) \
-  "v_mov_b32 v153, 0\n\tv_mov_b32 v155, 0\n\tv_mov_b32 v157, 0\n\tv_mov_b32 v159, 0\n\t" \
-  "v_mov_b32 v177, 0\n\tv_mov_b32 v179, 0\n\t" \
+  "v_mov_b32 v152, 0\n\tv_mov_b32 v153, 0\n\tv_mov_b32 v154, 0\n\tv_mov_b32 v155, 0\n\t" \
+  "v_mov_b32 v156, 0\n\tv_mov_b32 v157, 0\n\tv_mov_b32 v158, 0\n\tv_mov_b32 v159, 0\n\t" \
+  "v_mov_b32 v176, 0\n\tv_mov_b32 v177, 0\n\tv_mov_b32 v178, 0\n\tv_mov_b32 v179, 0\n\t" \
   "s_waitcnt lgkmcnt(0)\n\t" \
   TFC_LENC_A(124, 148, 149, 152, 154, TFC_LENC_ROW_B(16), NP0) \
   "s_waitcnt lgkmcnt(2)\n\t" \
@@ -837,7 +838,8 @@ struct DecWaveLds {
 // LDS operands are absolute LDS addresses (the kernel's dynamic LDS starts at 0, checked by the
 // caller).  Temporaries are the fixed registers v100-v132 (register pairs and the 4-register row
 // buffers need known numbers): v[100:103] / v[104:107] rows (cdf - 2, info, bits, cum), v[120:121] = -1,
-// v[122:123] = (lo, 0), v[124:125] = (hi, 0).
+// v[122:123] = (lo << 16, 0), v[124:125] = (hi << 16, 0): the entries are read into the upper halves of v122 / v124 (the
+// block's head zeroes them), and the upper dwords v127 / v129 of the two v_mad_u64_u32 are the bounds (TFC_LENC_B).
 #define TFC_LDEC_STEP(ROW0, ROW1, ROW2, ROW3, PREFETCH, OUTOFF, ESC1, ESC2)                \
   PREFETCH                                                                                \
   "ds_read_u16 v109, %[CP]\n\t"                                                           \
@@ -860,8 +862,8 @@ struct DecWaveLds {
   "v_bcnt_u32_b32 v116, v118, v116\n\t"                                                   \
   "v_bcnt_u32_b32 v117, v119, v116\n\t"                                                   \
   "v_lshl_add_u32 v112, v117, 1, v" #ROW0 "\n\t"                                          \
-  "ds_read_u16 v122, v112 offset:2\n\t"                                                   \
-  "ds_read_u16 v124, v112 offset:4\n\t"                                                   \
+  "ds_read_u16_d16_hi v122, v112 offset:2\n\t"                                            \
+  "ds_read_u16_d16_hi v124, v112 offset:4\n\t"                                            \
   "v_xad_u32 v113, v117, v" #ROW1 ", %[K31]\n\t"                                          \
   ESC1                                                                                    \
   "ds_write_b32 %[OQ], v117 offset:" #OUTOFF "\n\t"                                       \
@@ -869,12 +871,10 @@ struct DecWaveLds {
   "s_waitcnt lgkmcnt(1)\n\t"                                                              \
   "v_mad_u64_u32 v[126:127], vcc, v122, %[S], v[122:123]\n\t"                             \
   "v_mad_u64_u32 v[128:129], vcc, v124, %[S], v[124:125]\n\t"                             \
-  "v_alignbit_b32 v126, v127, v126, 16\n\t"                                               \
-  "v_alignbit_b32 v128, v129, v128, 16\n\t"                                               \
-  "v_add_u32 v128, -1, v128\n\t"                                                          \
-  "v_min_u32 v128, v128, %[S]\n\t"                                                        \
-  "v_sub_u32 v130, %[D], v126\n\t"                                                        \
-  "v_sub_u32 v131, v128, v126\n\t"                                                        \
+  "v_add_u32 v129, -1, v129\n\t"                                                          \
+  "v_min_u32 v129, v129, %[S]\n\t"                                                        \
+  "v_sub_u32 v130, %[D], v127\n\t"                                                        \
+  "v_sub_u32 v131, v129, v127\n\t"                                                        \
   "v_cmp_gt_u32 vcc, v130, v131\n\t"                                                      \
   "v_addc_co_u32 %[FLAG], vcc, 0, %[FLAG], vcc\n\t"                                       \
   "v_cmp_gt_u32 vcc, %[K64K], v131\n\t"                                                   \
@@ -898,7 +898,7 @@ struct DecWaveLds {
 #define TFC_LDEC_BLOCK(ESC1, ESC2, PARKPRE)                                               \
   "s_mov_b64 s[56:57], exec\n\t"                                                          \
   PARKPRE                                                                                 \
-  "v_mov_b32 v123, 0\n\tv_mov_b32 v125, 0\n\t"                                           \
+  "v_mov_b32 v122, 0\n\tv_mov_b32 v123, 0\n\tv_mov_b32 v124, 0\n\tv_mov_b32 v125, 0\n\t"       \
   TFC_LDEC_READ_A(0) "s_waitcnt lgkmcnt(0)\n\t"                                           \
   TFC_LDEC_STEP(100, 101, 102, 103, TFC_LDEC_READ_B(16), 0, ESC1, ESC2)                   \
   TFC_LDEC_STEP(104, 105, 106, 107, TFC_LDEC_READ_A(32), 4, ESC1, ESC2)                   \

@@ -345,13 +345,15 @@ __global__ void __launch_bounds__(kExpandThreads, 4) enc_expand_kernel(const Enc
 // ---------------------------------------------------------------------------------------------
 
 // One row: a lane whose word is "no call" leaves EXEC for the rest of the block (a stream's calls are the first rows
-// of its last block, so nothing follows a "no call" inside a block); the call word is unpacked into the (lo, 0) /
-// (hi, 0) register pairs TFC_LENC_B multiplies from.
+// of its last block, so nothing follows a "no call" inside a block); the call word lo | hi << 16 is unpacked into the
+// (lo << 16, 0) / (hi << 16, 0) register pairs — W << 16 and W & 0xFFFF0000 — that the bounds multiply from: the product
+// (c << 16) S + (c << 16) = (c (S + 1)) << 16 is below 2^64 and its UPPER dword is the bound (c (S + 1)) >> 16, exactly
+// (c < 2^16, S < 2^32) — one v_mad_u64_u32 per bound, no shift behind it.  hi = 2^16 is stored as 0: 0 - 1 -> min(.., S).
 // (TFC_LENC_B of range_lanes.h with its temporaries at v100-v119: a chain workgroup is eight waves (sixteen before round 5), two per SIMD,
 // 128 registers each)
 // Three forms of the row's last part:
 //  * TFC_PENC_STEP (enc_chain_direct_kernel): the digit is stored big-endian, FLAG counts the steps that leave 0xFFFF held;
-//  * TFC_PENC_STEP_H (enc_chain_kernel, round 5): 23 instructions instead of 30 — the digit goes to LDS as it is (the storer
+//  * TFC_PENC_STEP_H (enc_chain_kernel, round 5): 21 instructions instead of 28 — the digit goes to LDS as it is (the storer
 //    wave swaps the bytes of what it copies); the new held digit is selected out of bs's upper half by the v_cndmask itself
 //    (SDWA); a lane that holds 0xFFFF or more after a step leaves EXEC like one that meets "no call" (the caller looks at H
 //    behind the block: the wave repeats the block call by call either way); and a carry does not push the held digit out
@@ -361,17 +363,15 @@ __global__ void __launch_bounds__(kExpandThreads, 4) enc_expand_kernel(const Enc
 //    bookkeeping: emit = r & held, held' = held | r, with `held` kept as 0 / 2 (the cursor's increment; v119 = 2).
 #define TFC_PENC_ROW(W)                                                                    \
   "v_cmpx_ne_u32 vcc, %[NOCALL], %[" #W "]\n\t"                                            \
-  "v_and_b32 v100, %[KFFFF], %[" #W "]\n\t"                                                \
-  "v_lshrrev_b32 v102, 16, %[" #W "]\n\t"                                                  \
+  "v_lshlrev_b32 v100, 16, %[" #W "]\n\t"                                                  \
+  "v_and_b32 v102, %[KHI16], %[" #W "]\n\t"                                                \
   "v_mad_u64_u32 v[104:105], s[52:53], v100, %[S], v[100:101]\n\t"                         \
   "v_mad_u64_u32 v[106:107], s[52:53], v102, %[S], v[102:103]\n\t"                         \
-  "v_alignbit_b32 v104, v105, v104, 16\n\t"                                               \
-  "v_alignbit_b32 v106, v107, v106, 16\n\t"                                               \
-  "v_add_u32 v106, -1, v106\n\t"                                                          \
-  "v_min_u32 v106, v106, %[S]\n\t"                                                        \
-  "v_add_co_u32 v108, vcc, %[BASE], v104\n\t"                                             \
+  "v_add_u32 v107, -1, v107\n\t"                                                          \
+  "v_min_u32 v107, v107, %[S]\n\t"                                                        \
+  "v_add_co_u32 v108, vcc, %[BASE], v105\n\t"                                             \
   "v_addc_co_u32 v111, vcc, 0, %[H], vcc\n\t"                                             \
-  "v_sub_u32 v109, v106, v104\n\t"                                                        \
+  "v_sub_u32 v109, v107, v105\n\t"                                                        \
   "v_sub_u32 v117, v111, %[H]\n\t"                                                        \
   "v_cmp_gt_u32 vcc, %[K64K], v109\n\t"                                                   \
   "v_cndmask_b32 v118, 0, 1, vcc\n\t"
@@ -394,17 +394,15 @@ __global__ void __launch_bounds__(kExpandThreads, 4) enc_expand_kernel(const Enc
   "v_addc_co_u32 %[FLAG], vcc, 0, %[FLAG], vcc\n\t"
 #define TFC_PENC_STEP_H(W)                                                                 \
   "v_cmpx_ne_u32 vcc, %[NOCALL], %[" #W "]\n\t"                                            \
-  "v_and_b32 v100, %[KFFFF], %[" #W "]\n\t"                                                \
-  "v_lshrrev_b32 v102, 16, %[" #W "]\n\t"                                                  \
+  "v_lshlrev_b32 v100, 16, %[" #W "]\n\t"                                                  \
+  "v_and_b32 v102, %[KHI16], %[" #W "]\n\t"                                                \
   "v_mad_u64_u32 v[104:105], s[52:53], v100, %[S], v[100:101]\n\t"                         \
   "v_mad_u64_u32 v[106:107], s[52:53], v102, %[S], v[102:103]\n\t"                         \
-  "v_alignbit_b32 v104, v105, v104, 16\n\t"                                               \
-  "v_alignbit_b32 v106, v107, v106, 16\n\t"                                               \
-  "v_add_u32 v106, -1, v106\n\t"                                                          \
-  "v_min_u32 v106, v106, %[S]\n\t"                                                        \
-  "v_add_co_u32 v108, vcc, %[BASE], v104\n\t"                                             \
+  "v_add_u32 v107, -1, v107\n\t"                                                          \
+  "v_min_u32 v107, v107, %[S]\n\t"                                                        \
+  "v_add_co_u32 v108, vcc, %[BASE], v105\n\t"                                             \
   "v_addc_co_u32 v111, vcc, 0, %[H], vcc\n\t"                                             \
-  "v_sub_u32 v109, v106, v104\n\t"                                                        \
+  "v_sub_u32 v109, v107, v105\n\t"                                                        \
   "v_cmp_gt_u32 vcc, %[K64K], v109\n\t"                                                   \
   "ds_write_b16 %[NA], v111\n\t"                                                          \
   "v_cndmask_b32 v112, 0, %[HAD], vcc\n\t"                                                \
@@ -704,7 +702,7 @@ __global__ void __launch_bounds__(1024) enc_chain_kernel(const PipeChainJobs job
         "s_mov_b64 exec, s[56:57]\n\t"
         "s_waitcnt lgkmcnt(0)\n\t"
         : [BASE] "+v"(base), [S] "+v"(s1), [H] "+v"(hd), [HAD] "+v"(had2), [NA] "+v"(na)
-        : [NOCALL] "s"(kPipeNoCall), [K64K] "s"(0x10000u), [KFFFF] "s"(0xFFFFu),
+        : [NOCALL] "s"(kPipeNoCall), [K64K] "s"(0x10000u), [KFFFF] "s"(0xFFFFu), [KHI16] "s"(0xFFFF0000u),
           [W0] "v"(ww[0]), [W1] "v"(ww[1]), [W2] "v"(ww[2]), [W3] "v"(ww[3]), [W4] "v"(ww[4]), [W5] "v"(ww[5]),
           [W6] "v"(ww[6]), [W7] "v"(ww[7]), [W8] "v"(ww[8]), [W9] "v"(ww[9]), [W10] "v"(ww[10]), [W11] "v"(ww[11]),
           [W12] "v"(ww[12]), [W13] "v"(ww[13]), [W14] "v"(ww[14]), [W15] "v"(ww[15])
@@ -982,7 +980,7 @@ __global__ void __launch_bounds__(64) enc_chain_direct_kernel(const PipeChainJob
         "s_mov_b64 exec, s[56:57]\n\t"
         "s_waitcnt lgkmcnt(0)\n\t"
         : [BASE] "+v"(base), [S] "+v"(s1), [H] "+v"(hd), [HAD] "+v"(had), [NA] "+v"(na), [FLAG] "+v"(flag)
-        : [NOCALL] "s"(kPipeNoCall), [K64K] "s"(0x10000u), [KFFFF] "s"(0xFFFFu), [PERM] "s"(0x0c0c0001u),
+        : [NOCALL] "s"(kPipeNoCall), [K64K] "s"(0x10000u), [KFFFF] "s"(0xFFFFu), [KHI16] "s"(0xFFFF0000u), [PERM] "s"(0x0c0c0001u),
           [W0] "v"(w0), [W1] "v"(w1), [W2] "v"(w2), [W3] "v"(w3), [W4] "v"(w4), [W5] "v"(w5),
           [W6] "v"(w6), [W7] "v"(w7), [W8] "v"(w8), [W9] "v"(w9), [W10] "v"(w10), [W11] "v"(w11),
           [W12] "v"(w12), [W13] "v"(w13), [W14] "v"(w14), [W15] "v"(w15)
@@ -1168,7 +1166,8 @@ struct PipeDecLds {
 // element's directory entry; with M' != 0 the next row is the built-in binary row.  Every step writes its raw entry
 // (pipe_raw_entry: the symbol, or 0x8000 | bit on the binary row) to row K of the wave's staging area.  FLAG: the
 // verification failed (estimate one off, ~1e-6, or damaged input) — the caller then repeats the block from its saved
-// state step by step.  Fixed temporaries v104-v142; v123 = v125 = 0.
+// state step by step.  Fixed temporaries v104-v142; v[122:123] = (lo << 16, 0), v[124:125] = (hi << 16, 0): the low halves of
+// v122 / v124 and v123 / v125 are zeroed in the block's head and nothing in a step writes them.
 // TFC_PDEC_ABL (build switch, bits, timing experiments only — results are wrong): 1 the step stores nothing, 2 one load per
 // window request instead of five, 4 no flush of the raw rows
 #ifndef TFC_PDEC_ABL
@@ -1232,6 +1231,14 @@ struct PipeDecLds {
 // Measured and dropped: 1 / S issued four instructions early (no gain: nothing waits for v_rcp_f32), the two bounds as
 // three v_mad_u32_u16 / shift / v_mad_u32_u16 each instead of v_mad_u64_u32 + v_alignbit (+8 cycles: the 64-bit multiply
 // costs one slot like everything else).
+// The bounds from the multiply's upper half: the two cdf entries are read into the UPPER halves of v122 / v124
+// (ds_read_u16_d16_hi; the block's head zeroes the registers, so the low halves are zero whether the load keeps or clears
+// them — the compact image's SDWA selects write WORD_1 and pad with zeros), operand and addend of the v_mad_u64_u32 are
+// c << 16, the product (c (S + 1)) << 16 < 2^64, and its upper dword v127 / v129 is (c (S + 1)) >> 16 exactly: no
+// v_alignbit_b32 behind either multiply.  A step is  quotient 11 + rank 6 + bounds 11  instructions (the compact image's 9
+// more), 42 in all against 44: measured 261.0 cycles per row inside the blocks against 268.5 in the same job
+// (profiles/step_bounds.md).  The next row's ds_read_b128 has two instructions less cover and it does not show: the 7.5
+// cycles are the two instructions' worth, so the schedule stays as it was.
 // TFC_PDEC_PAD = 1 .. 4 (build switch, tools/r05_step_pad.sh): two extra instructions in the quotient part, the first
 // shadow, the second shadow, the bounds part of every step — which parts of a step are bound by instruction issue
 #ifndef TFC_PDEC_PAD
@@ -1262,7 +1269,7 @@ struct PipeDecLds {
 #endif
 // Registers across steps: v104-v107 the row, v135 = M - 1, v136 = -[M = 0], v130 / v131 the previous step's pending
 // verification, s[56:57] its "renormalised" condition (the code cursor moves on in the next step's first shadow, which has
-// two slots to spare; the bounds part has none); v123 = v125 = 0.
+// two slots to spare; the bounds part has none); v123 = v125 = 0 and the low halves of v122 / v124 are 0.
 #define TFC_PDEC_STEP(KOFF, MI, MO, AHEAD, NEXT, PWSTEP)                                    \
   "v_cvt_f32_u32 v111, %[S]\n\t"                                                          \
   "v_add_f32 v111, 1.0, v111\n\t"                                                         \
@@ -1293,8 +1300,8 @@ struct PipeDecLds {
   "v_bcnt_u32_b32 v116, v118, v116\n\t"                                                   \
   "v_bcnt_u32_b32 v117, v119, v116\n\t"                                                   \
   "v_lshl_add_u32 v112, v117, 1, v104\n\t"                                                \
-  "ds_read_u16 v122, v112 offset:2\n\t"                                                   \
-  "ds_read_u16 v124, v112 offset:4\n\t"                                                   \
+  "ds_read_u16_d16_hi v122, v112 offset:2\n\t"                                            \
+  "ds_read_u16_d16_hi v124, v112 offset:4\n\t"                                            \
   TFC_PDEC_PAD_C                                                                          \
   TFC_PDEC_STORE(KOFF)                                                                    \
   "v_subrev_co_u32 v135, vcc, 1, " MO "\n\t"                                              \
@@ -1307,15 +1314,13 @@ struct PipeDecLds {
   TFC_PDEC_PAD_D                                                                          \
   "v_mad_u64_u32 v[126:127], s[52:53], v122, %[S], v[122:123]\n\t"                        \
   "v_mad_u64_u32 v[128:129], s[52:53], v124, %[S], v[124:125]\n\t"                        \
-  "v_alignbit_b32 v126, v127, v126, 16\n\t"                                               \
-  "v_alignbit_b32 v128, v129, v128, 16\n\t"                                               \
-  "v_add_u32 v128, -1, v128\n\t"                                                          \
-  "v_min_u32 v128, v128, %[S]\n\t"                                                        \
-  "v_sub_u32 v131, v128, v126\n\t"                                                        \
+  "v_add_u32 v129, -1, v129\n\t"                                                          \
+  "v_min_u32 v129, v129, %[S]\n\t"                                                        \
+  "v_sub_u32 v131, v129, v127\n\t"                                                        \
   "v_cmp_gt_u32_e64 s[56:57], %[K64K], v131\n\t"                                          \
   "v_lshl_or_b32 v132, v131, 16, %[KFFFF]\n\t"                                            \
   "v_cndmask_b32_e64 %[S], v131, v132, s[56:57]\n\t"                                      \
-  "v_sub_u32 v130, %[D], v126\n\t"                                                        \
+  "v_sub_u32 v130, %[D], v127\n\t"                                                        \
   "v_perm_b32 v132, v130, v109, %[PERM]\n\t"                                              \
   "v_cndmask_b32_e64 %[D], v130, v132, s[56:57]\n\t"
 // Round 6: the same step on the COMPACT image (tfc_tables_create, "Compact image"): the bitmaps mark every SECOND bound of
@@ -1371,25 +1376,23 @@ struct PipeDecLds {
   "ds_read_b128 v[104:107], v142\n\t"                                                     \
   "s_waitcnt lgkmcnt(1)\n\t"                                                              \
   "v_cmp_ge_u32_sdwa vcc, v141, v144 src0_sel:DWORD src1_sel:WORD_1\n\t"                  \
-  "v_cndmask_b32_sdwa v122, v144, v144, vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_1\n\t" \
-  "v_cndmask_b32_sdwa v124, v144, v145, vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+  "v_cndmask_b32_sdwa v122, v144, v144, vcc dst_sel:WORD_1 dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_1\n\t" \
+  "v_cndmask_b32_sdwa v124, v144, v145, vcc dst_sel:WORD_1 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
   "v_addc_co_u32_e64 v117, s[58:59], v117, v117, vcc\n\t"                                 \
   "v_cmp_ge_u32_sdwa vcc, v141, v145 src0_sel:DWORD src1_sel:WORD_0\n\t"                  \
-  "v_cndmask_b32_sdwa v122, v122, v145, vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0\n\t" \
-  "v_cndmask_b32_sdwa v124, v124, v145, vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1\n\t" \
+  "v_cndmask_b32_sdwa v122, v122, v145, vcc dst_sel:WORD_1 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+  "v_cndmask_b32_sdwa v124, v124, v145, vcc dst_sel:WORD_1 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1\n\t" \
   "v_addc_co_u32_e64 v117, s[58:59], v117, v123, vcc\n\t"                                 \
   TFC_PDEC_STORE(KOFF)                                                                    \
   "v_mad_u64_u32 v[126:127], s[52:53], v122, %[S], v[122:123]\n\t"                        \
   "v_mad_u64_u32 v[128:129], s[52:53], v124, %[S], v[124:125]\n\t"                        \
-  "v_alignbit_b32 v126, v127, v126, 16\n\t"                                               \
-  "v_alignbit_b32 v128, v129, v128, 16\n\t"                                               \
-  "v_add_u32 v128, -1, v128\n\t"                                                          \
-  "v_min_u32 v128, v128, %[S]\n\t"                                                        \
-  "v_sub_u32 v131, v128, v126\n\t"                                                        \
+  "v_add_u32 v129, -1, v129\n\t"                                                          \
+  "v_min_u32 v129, v129, %[S]\n\t"                                                        \
+  "v_sub_u32 v131, v129, v127\n\t"                                                        \
   "v_cmp_gt_u32_e64 s[56:57], %[K64K], v131\n\t"                                          \
   "v_lshl_or_b32 v132, v131, 16, %[KFFFF]\n\t"                                            \
   "v_cndmask_b32_e64 %[S], v131, v132, s[56:57]\n\t"                                      \
-  "v_sub_u32 v130, %[D], v126\n\t"                                                        \
+  "v_sub_u32 v130, %[D], v127\n\t"                                                        \
   "v_perm_b32 v132, v130, v109, %[PERM]\n\t"                                              \
   "v_cndmask_b32_e64 %[D], v130, v132, s[56:57]\n\t"
 // channel mode: the next element's entry is the one behind the current (PW + 16); index mode: its address comes out
@@ -1403,7 +1406,7 @@ struct PipeDecLds {
 #define TFC_PDEC_STEP2(STEP, K0, K1) STEP(K0, "%[M]", "v138") STEP(K1, "v138", "%[M]")
 #define TFC_PDEC_BLOCK_HEAD                                                               \
   "v_mov_b32 v104, %[R0]\n\tv_mov_b32 v105, %[R1]\n\tv_mov_b32 v106, %[R2]\n\tv_mov_b32 v107, %[R3]\n\t" \
-  "v_mov_b32 v123, 0\n\tv_mov_b32 v125, 0\n\t"                                           \
+  "v_mov_b32 v122, 0\n\tv_mov_b32 v123, 0\n\tv_mov_b32 v124, 0\n\tv_mov_b32 v125, 0\n\t"       \
   "v_mov_b32 v130, 0\n\tv_mov_b32 v131, 0\n\ts_mov_b64 s[56:57], 0\n\t"                   \
   "v_subrev_co_u32 v135, vcc, 1, %[M]\n\tv_cndmask_b32_e64 v136, 0, -1, vcc\n\t"           \
   "s_mov_b64 s[54:55], exec\n\tv_mov_b32 %[FLAG], 1\n\t"

@@ -51,8 +51,9 @@ for q in range(N // 2):
     lds.append("val")
 emit("TFC_LENC_ROW_A(0)")
 lds.append("row0")
-emit('"v_mov_b32 v153, 0\\n\\tv_mov_b32 v155, 0\\n\\tv_mov_b32 v157, 0\\n\\tv_mov_b32 v159, 0\\n\\t"')
-emit('"v_mov_b32 v177, 0\\n\\tv_mov_b32 v179, 0\\n\\t"')
+# (lo << 16, 0) / (hi << 16, 0): the entries arrive by high-half loads, so the low halves are zeroed here as well
+for lo, loh, hi, hih in SETS:
+    emit(f'"v_mov_b32 v{lo}, 0\\n\\tv_mov_b32 v{loh}, 0\\n\\tv_mov_b32 v{hi}, 0\\n\\tv_mov_b32 v{hih}, 0\\n\\t"')
 next_a = 0
 for k in range(N):
     while next_a <= min(N - 1, k + AHEAD):
