@@ -40,6 +40,7 @@
 #include "../../include/tfc_hip.h"
 #include "launch.h"
 #include "range_coder_device.h"
+#include "range_plan.h"
 #include "range_tables.h"
 #include "range_wave.h"
 
@@ -707,6 +708,28 @@ inline int side_stream(hipStream_t st, SideStream* out) {
   *out = f->second;
   return 0;
 }
+// Work beside the caller's stream `st`: after fork(), what goes to `stream` runs on the library's own stream, behind what
+// `st` holds so far; join() puts `st` behind it again.  Without a fork `stream` is the caller's and join() does nothing.
+struct SideFork {
+  hipStream_t st, stream;
+  SideStream side;
+  bool forked = false;
+  explicit SideFork(hipStream_t caller) : st(caller), stream(caller) {}
+  int fork() {
+    if (side_stream(st, &side)) return 1;
+    TFC_HIP(hipEventRecord(side.fork, st));
+    TFC_HIP(hipStreamWaitEvent(side.stream, side.fork, 0));
+    stream = side.stream;
+    forked = true;
+    return 0;
+  }
+  int join() {
+    if (!forked) return 0;
+    TFC_HIP(hipEventRecord(side.join, side.stream));
+    TFC_HIP(hipStreamWaitEvent(st, side.join, 0));
+    return 0;
+  }
+};
 // Temporaries of one pipelined launch (call words / raw rows: ~150 / ~125 MB per 512-stream job of BASELINE config 2) are
 // bounded: more jobs than fit go out as several launches, one behind the other.  6 GB, at most an eighth of the device's
 // memory; TFC_PIPE_TEMP_MB overrides.  Measured (round 5, bench.py `saturation`, profiles/r05_notes.md): a launch takes
@@ -742,6 +765,65 @@ inline const PipeDeviceInfo& pipe_device_info() {
   return info[dev];
 }
 inline size_t pipe_temp_bytes() { return pipe_device_info().temp_bytes; }
+
+// The facts the lane path's plans (range_plan.h) are functions of: the tables', the device's and the switches', and the
+// kernels' compile-time sizes (WaveLds / kMaxJobs: of the lane kernel that is planned — EncWaveLds, EncLaneJobs or the
+// decoder's).
+inline plan::TableFacts table_facts(const tfc_tables* t) {
+  plan::TableFacts f;
+  f.lane_enc_bytes = t->lane_enc_bytes;
+  f.lane_dec_bytes = t->lane_dec_bytes;
+  f.pair_dec_bytes = t->pair_dec_bytes;
+  f.pairs_ok = t->pairs_ok;
+  f.any_escape = t->any_escape;
+  f.lane_precision = t->lane_precision;
+  f.entries = t->host.size();
+  f.ntab = static_cast<int>(t->rows.size());
+  return f;
+}
+inline plan::DeviceFacts device_facts() {
+  plan::DeviceFacts f;
+  f.cus = device_cus();
+  f.lds_bytes = kLds;
+  f.temp_bytes = pipe_temp_bytes();
+  f.pipe_enabled = pipe_enabled();
+  f.format = pipe_format();
+  f.waves_override = pipe_waves_env();
+  f.overlap = pipe_overlap();
+  f.chip_shared = chip_shared();
+  return f;
+}
+template <typename WaveLds, int kMaxJobs>
+constexpr plan::KernelFacts kernel_facts() {
+  plan::KernelFacts f;
+  f.lane_wave_indexed = WaveLds::kBytes;
+  f.lane_wave_plain = WaveLds::kIndex;
+  f.dec_lds_bytes = PipeDecLds::kBytes;
+  f.dec_lds_rows = PipeDecLds::kRows;
+  f.dec_lds_stage = PipeDecLds::kStage;
+  f.enc_chain_groups = PipeEncChainLds::kGroups;
+  f.enc_chain_group = PipeEncChainLds::kGroup;
+  f.enc_chain_rows = PipeEncChainLds::kRows;
+  f.pipe_tile = kPipeTile;
+  f.pipe_block = kPipeBlock;
+  f.parse_rows = kParseRows;
+  f.expand_tab_bytes = kExpandTabBytes;
+  f.max_jobs = kMaxJobs;
+  return f;
+}
+static_assert(sizeof(uint4) == plan::kStateBytes && sizeof(uint2) == plan::kStageOutBytes);      // range_plan.h's element sizes
+
+// Kernel variants: run-time switches (index mode, the compact image, the staged tables) as std::bool_constant arguments
+// of a generic lambda, which names the instantiation.  (Two flags: the first is the outer choice.  The variants are
+// instantiated in that order, which is their order in the code object — tools/kernel_diff.py sees a swap as moved code.)
+template <typename F>
+auto with_flags(bool a, F&& f) {
+  return a ? f(std::true_type{}) : f(std::false_type{});
+}
+template <typename F>
+auto with_flags(bool a, bool b, F&& f) {
+  return with_flags(a, [&](auto A) { return with_flags(b, [&](auto B) { return f(A, B); }); });
+}
 
 }  // namespace
 
@@ -824,7 +906,7 @@ int select_family(const tfc_tables* t, int mode, int64_t streams, int64_t elems,
   // the lane kernels address a stream's bytes with 32 bits, and their LDS plan (image + one wave's
   // staging planes, any variant of the encoder) has to fit the CU
   const bool lanes_ok = t->lanes_ok && elems < (int64_t{1} << 29) &&
-                        ((t->lane_enc_bytes + 1023) & ~1023) + EncWaveLds<int32_t>::kBytes <= kLds;
+                        plan::lanes_fit(t->lane_enc_bytes, EncWaveLds<int32_t>::kBytes, kLds);
   if (mode == TFC_MODE_AUTO) mode = tfc_get_default_mode();
   if (mode == TFC_MODE_THROUGHPUT && lanes_ok) return kLanes;
   if (mode == TFC_MODE_AUTO && lanes_ok && streams >= 4096) return kLanes;
@@ -838,14 +920,6 @@ int select_family(const tfc_tables* t, int mode, int64_t streams, int64_t elems,
 // Blocks a wave of the lane kernels lets lanes wait in front of an escape code before it takes the codes of all
 // waiting lanes together (LaneArgs::defer; measured in round 3: 3).
 inline int lanes_escape_defer() { return 3; }
-
-// Streams per workgroup of the lane kernels: one wave (64 streams) until the launch fills the chip,
-// so that a 512-stream call spreads over eight CUs (and XCDs), then more waves behind each LDS image.
-inline int lanes_block(int64_t streams) {
-  const int64_t waves = ceil_div(streams, 64);
-  const int64_t per = std::min<int64_t>(8, std::max<int64_t>(1, waves / 256));
-  return static_cast<int>(64 * per);
-}
 
 // Slab bytes per stream that a lane-encoder call can never exceed, from the table headers alone (no
 // counting pass, no read-back).  A call emits at most one 16-bit digit; and a call of probability P
@@ -910,6 +984,117 @@ int encoder_error(tfc_encoder* e, const unsigned long long* host_status) {
                           ch, static_cast<int32_t>(static_cast<long long>(host_status[1])));
 }
 
+// What a lane kernel is told of the tables and its LDS plan; `bytes`: of the direction's image (cap: the encoder's)
+inline LaneArgs lane_args(const tfc_tables* t, int bytes, const plan::LanePlan& lanes) {
+  LaneArgs la;
+  la.image = t->d_lane_image.as<uint32_t>();
+  la.bytes = bytes;
+  la.ntab = static_cast<int>(t->rows.size());
+  la.precision = t->lane_precision;
+  la.cap = 0;
+  la.defer = lanes_escape_defer();
+  la.guard = nullptr;
+  la.lds_image = lanes.lds_image;
+  la.lds_wave = lanes.lds_wave;
+  return la;
+}
+
+// The regions of a pipelined encode launch's workspace at `base`
+inline void bind_workspace(PipeEncArgs* pa, uint8_t* base, const plan::EncLayout& lay, size_t groups) {
+  pa->calls = reinterpret_cast<unsigned int*>(base + lay.calls);
+  pa->stage_state = reinterpret_cast<uint4*>(base + lay.stage_state);
+  pa->stage_out = reinterpret_cast<uint2*>(base + lay.stage_out);
+  pa->status = reinterpret_cast<unsigned int*>(base + lay.status);
+  pa->done = reinterpret_cast<unsigned int*>(base + lay.done);
+  pa->fallback = reinterpret_cast<unsigned int*>(base + lay.fallback);
+  pa->started = reinterpret_cast<unsigned int*>(base + lay.started);
+  pa->groups = static_cast<int>(groups);
+}
+
+// The pipelined kernels of one encode launch (pa bound to its zeroed workspace): expansion, chain, commit.
+// A large launch: the chain (workgroups of PipeEncChainLds::kGroups groups, helper waves: range_pipe.h) on the library's own stream
+// next to the expansion.  A small one — a model step's few groups, next to other steps' convolutions — one-wave
+// chain workgroups behind the expansion on the caller's stream: measured on bmshj2018 with steps in flight, the
+// second stream, its events and the large workgroups cost more (45 against 36 ms per step) than the overlap of
+// two short kernels gives.
+template <typename Src>
+int launch_enc_pipe(const EncLaneJobs<Src>& jobs, const PipeEncArgs& pa, const plan::EncPipePlan& pipe,
+                    const plan::DeviceFacts& dev, bool indexed, hipStream_t st) {
+  const size_t groups = static_cast<size_t>(pa.groups);
+  const bool large = plan::large_launch(groups);
+  const int overlap = plan::launch_overlap(dev, groups);
+  PipeChainJobs cj;
+  cj.streams = jobs.streams;
+  for (int k = 0; k < jobs.n; ++k)
+    cj.job[k] = PipeChainJob{jobs.job[k].state, jobs.job[k].chunk, jobs.job[k].chunk_len, jobs.job[k].overflow_flag};
+  SideFork side(st);
+  if (overlap && side.fork()) return 1;
+  const hipStream_t cst = side.stream;
+  const dim3 xgrid(static_cast<unsigned>(groups * pa.nt));
+  auto expand = [&] {
+    KernelTimer t2("enc_expand", st);
+    with_flags(indexed, pa.tab_entries != 0, [&](auto I, auto T) {
+      hipLaunchKernelGGL((enc_expand_kernel<decltype(I)::value, Src, decltype(T)::value>), xgrid, dim3(kExpandThreads), 0, st, jobs, pa);
+    });
+  };
+  const int cgroups = PipeEncChainLds::kGroups;
+  const unsigned cblocks = static_cast<unsigned>(ceil_div(static_cast<int64_t>(groups), cgroups));
+  if (large)
+    if (int rc = allow_dynamic_lds(reinterpret_cast<const void*>(&enc_chain_kernel), pipe.chain_lds)) return rc;
+  auto chain = [&] {
+    KernelTimer t2("enc_chain", cst);
+    if (!large) {
+      hipLaunchKernelGGL(enc_chain_direct_kernel, dim3(static_cast<unsigned>(groups)), dim3(64), 0, cst, cj, pa);
+      return;
+    }
+    hipLaunchKernelGGL(enc_chain_kernel, dim3(cblocks), dim3(256 * cgroups), pipe.chain_lds, cst, cj, pa);
+    // (the expansion behind the chain's workgroups, not in their way)
+    if (overlap == 2)
+      hipLaunchKernelGGL(enc_gate_kernel, dim3(1), dim3(1), 0, st, pa.started, cblocks, static_cast<long long>(20000));
+  };
+  if (overlap == 2) { chain(); expand(); }
+  else { expand(); chain(); }
+  if (int rc = side.join()) return rc;
+  hipLaunchKernelGGL(enc_commit_kernel, dim3(static_cast<unsigned>(groups)), dim3(64), 0, st, cj, pa);
+  return 0;
+}
+
+template <typename Src>
+int encode_lanes_many(tfc_encoder* const* es, int n, const Src* srcs, const int32_t* const* indexes,
+                      int64_t elems, hipStream_t st, bool worst_case_slab);
+
+// Behind the launches of an encode call: the handles that want their range errors now are read back, and one whose
+// stream outgrew the speculative slab (`backups`: the pre-call coder states, per handle) is coded again.
+template <typename Src>
+int settle_eager_encoders(tfc_encoder* const* es, int n, const Src* srcs, const int32_t* const* indexes, int64_t elems,
+                          hipStream_t st, bool speculative, const DevBuf* backups) {
+  const bool indexed = indexes && indexes[0];
+  bool any_eager = false;
+  for (int k = 0; k < n; ++k) any_eager |= !es[k]->deferred;
+  if (!any_eager) return 0;
+  TFC_HIP(hipStreamSynchronize(st));
+  for (int k = 0; k < n; ++k) {
+    tfc_encoder* e = es[k];
+    if (e->deferred) continue;
+    unsigned long long host_status[4];
+    TFC_HIP(hipMemcpy(host_status, e->status.p, sizeof(host_status), hipMemcpyDeviceToHost));
+    if (host_status[0] != ~0ull) return encoder_error(e, host_status);
+    if (!speculative) continue;
+    unsigned int oflag = 0;
+    TFC_HIP(hipMemcpy(&oflag, e->oflag.p, sizeof(oflag), hipMemcpyDeviceToHost));
+    if (oflag) {
+      // a stream outgrew the speculative slab: back to the pre-call state, code again with the bound
+      // that cannot be exceeded
+      TFC_HIP(hipMemcpyAsync(e->state.p, backups[k].p, sizeof(uint4) * e->streams, hipMemcpyDeviceToDevice, st));
+      TFC_HIP(hipMemsetAsync(e->oflag.p, 0, sizeof(unsigned int), st));
+      e->chunks.pop_back();
+      const int32_t* ix = indexed ? indexes[k] : nullptr;
+      if (encode_lanes_many(&es[k], 1, &srcs[k], &ix, elems, st, true)) return 1;
+    }
+  }
+  return 0;
+}
+
 // Lane-per-stream family: n handles (same tables, same stream count) coded by one launch per
 // kMaxLaneJobs of them; no counting pass, no read-back unless a handle wants its range errors now.
 // Where the geometry allows, the pipelined kernels (range_pipe.h: parallel expansion into call words, then the
@@ -917,56 +1102,39 @@ int encoder_error(tfc_encoder* e, const unsigned long long* host_status) {
 template <typename Src>
 int encode_lanes_many(tfc_encoder* const* es, int n, const Src* srcs, const int32_t* const* indexes,
                       int64_t elems, hipStream_t st, bool worst_case_slab) {
-  constexpr int kMaxLaneJobs = EncLaneJobs<Src>::kMax;
   const tfc_tables* t = es[0]->tables;
   const int64_t streams = es[0]->streams;
   const bool indexed = indexes && indexes[0];
-  LaneArgs la;
-  la.image = t->d_lane_image.as<uint32_t>();
-  la.bytes = t->lane_enc_bytes;
-  la.ntab = static_cast<int>(t->rows.size());
-  la.precision = t->lane_precision;
+  // the facts, and the plans made of them (range_plan.h)
+  const plan::TableFacts tf = table_facts(t);
+  const plan::DeviceFacts dev = device_facts();
+  constexpr plan::KernelFacts kf = kernel_facts<EncWaveLds<typename Src::raw_type>, EncLaneJobs<Src>::kMax>();
+  const plan::LanePlan lanes = plan::lane_plan(tf.lane_enc_bytes, kf, dev, streams * n, indexed);
+  const plan::EncPipePlan pipe = plan::enc_pipe_plan(tf, dev, kf, streams, elems);
+  LaneArgs la = lane_args(t, t->lane_enc_bytes, lanes);
   la.cap = lanes_slab_bytes(t, elems, worst_case_slab);
-  la.defer = lanes_escape_defer();
-  la.guard = nullptr;
   const bool speculative = t->any_escape && !worst_case_slab;
   std::vector<DevBuf> backups(speculative ? n : 0);     // pre-call coder states of the handles that can retry
-  la.lds_image = (t->lane_enc_bytes + 1023) & ~1023;
-  using WaveLds = EncWaveLds<typename Src::raw_type>;
-  la.lds_wave = indexed ? WaveLds::kBytes : WaveLds::kIndex;
-  const int block = std::min(lanes_block(streams * n), 64 * ((kLds - la.lds_image) / la.lds_wave));
-  const int lds_bytes = la.lds_image + (block / 64) * la.lds_wave;
-  const void* fn = indexed ? reinterpret_cast<const void*>(&enc_lanes_kernel<true, Src>)
-                           : reinterpret_cast<const void*>(&enc_lanes_kernel<false, Src>);
-  if (int rc = allow_dynamic_lds(fn, lds_bytes)) return rc;
-  // pipelined launch plan: groups of 64 streams, tiles of kPipeTile symbols; rows (coder calls) per stream: one per
-  // symbol, and room for escape codes when the tables have escape rows (half more than the symbols)
+  const void* fn = with_flags(indexed, [](auto I) { return reinterpret_cast<const void*>(&enc_lanes_kernel<decltype(I)::value, Src>); });
+  if (int rc = allow_dynamic_lds(fn, lanes.lds_bytes)) return rc;
   PipeEncArgs pa;
-  pa.nt = static_cast<int>(ceil_div(elems, kPipeTile));
-  const int64_t rows64 = elems + (t->any_escape ? elems / 2 + 64 : 0);
-  pa.rows = static_cast<int>(std::min<int64_t>((rows64 + 31) / 32 * 32, int64_t{1} << 30));
-  pa.groups_per_job = static_cast<int>(ceil_div(streams, 64));
+  pa.nt = pipe.nt;
+  pa.rows = pipe.rows;
+  pa.groups_per_job = pipe.groups_per_job;
   pa.poll_ticks = pipe_poll_ticks();
-  const size_t group_bytes = static_cast<size_t>(pa.rows) * 256 + (sizeof(unsigned int) * 65 * pa.nt) + 64 * (sizeof(uint4) + sizeof(uint2));
-  const size_t job_bytes = group_bytes * pa.groups_per_job;
-  const size_t kPipeTempBytes = pipe_temp_bytes();
-  const bool pipe = pipe_enabled() && rows64 + 2048 < (int64_t{1} << 30) && job_bytes <= kPipeTempBytes && t->host.size() <= 65536 &&
-                    static_cast<int64_t>(pa.nt) * pa.groups_per_job * kMaxLaneJobs < (int64_t{1} << 31);
-  // A launch's chain workgroups must all be resident at once, next to an expansion that needs CUs of its own: a chain
-  // workgroup (PipeEncChainLds::kGroups groups) takes a CU's whole LDS, so at most half the CUs go to chains — beyond
-  // that the chains starve the expansion they wait for (and time out into the fallback).
-  const int cus_e = device_cus();
-  const size_t resident_jobs = std::max<size_t>(1, static_cast<size_t>(cus_e / 2) * PipeEncChainLds::kGroups / std::max(1, pa.groups_per_job));
-  const int per_launch = !pipe ? kMaxLaneJobs
-                               : static_cast<int>(std::max<size_t>(1, std::min<size_t>(std::min<size_t>(kMaxLaneJobs, resident_jobs),
-                                                                                      kPipeTempBytes / std::max<size_t>(job_bytes, 1))));
-  for (int g0 = 0; g0 < n; g0 += per_launch) {
-    const int gn = std::min(per_launch, n - g0);
+  pa.fast16 = t->d_fast.as<uint16_t>();
+  pa.rows_fast = t->d_rows_fast.as<int2>();
+  pa.ntab = la.ntab;
+  pa.tab_entries = pipe.tab_entries;
+  pa.cap = la.cap;
+  for (int g0 = 0; g0 < n; g0 += pipe.per_launch) {
+    const int gn = std::min(pipe.per_launch, n - g0);
+    // 1. the jobs
     EncLaneJobs<Src> jobs;
     EncErrJobs<Src> errs;
     jobs.streams = streams;
     jobs.elems = elems;
-    jobs.blocks_per_job = static_cast<int>(ceil_div(streams, block));
+    jobs.blocks_per_job = static_cast<int>(ceil_div(streams, lanes.block));
     jobs.n = gn;
     errs.elems = elems;
     errs.ntab = la.ntab;
@@ -999,126 +1167,39 @@ int encode_lanes_many(tfc_encoder* const* es, int n, const Src* srcs, const int3
     }
     {
       KernelTimer timer("enc_kernel", st);
+      // 2. the workspace of the pipelined kernels
       DevBuf temp;
-      bool piped = pipe;
+      const size_t groups = static_cast<size_t>(pipe.groups_per_job) * gn;
+      const plan::EncLayout lay = plan::enc_layout(pipe, kf, groups);
+      bool piped = pipe.enabled;
       la.guard = nullptr;
-      if (pipe) do {
-        const size_t groups = static_cast<size_t>(pa.groups_per_job) * gn;
-        // (room behind the last group: the one-wave chain requests an iteration's rows ahead)
-        const size_t calls_bytes = (groups * 64 * pa.rows + 64 * PipeEncChainLds::kRows) * sizeof(unsigned int);
-        const size_t stage_bytes = groups * 64 * (sizeof(uint4) + sizeof(uint2));
-        const size_t status_bytes = groups * pa.nt * 64 * sizeof(unsigned int);
-        const size_t done_bytes = (groups * pa.nt * sizeof(unsigned int) + 255) & ~size_t{255};
-        if (temp.alloc(calls_bytes + stage_bytes + status_bytes + done_bytes + 512, st) != hipSuccess) {
-          // no room for the call words (a smaller or busier device): the lane-per-stream kernel codes this launch
-          (void)hipGetLastError();
-          temp.p = nullptr;
-          piped = false;
-          break;
-        }
-        uint8_t* base = temp.as<uint8_t>();
-        pa.calls = reinterpret_cast<unsigned int*>(base);
-        pa.stage_state = reinterpret_cast<uint4*>(base + calls_bytes);
-        pa.stage_out = reinterpret_cast<uint2*>(base + calls_bytes + groups * 64 * sizeof(uint4));
-        pa.status = reinterpret_cast<unsigned int*>(base + calls_bytes + stage_bytes);
-        pa.done = reinterpret_cast<unsigned int*>(base + calls_bytes + stage_bytes + status_bytes);
-        pa.fallback = reinterpret_cast<unsigned int*>(base + calls_bytes + stage_bytes + status_bytes + done_bytes);
-        pa.started = pa.fallback + 64;          // (behind the 64 jobs' flags)
-        pa.groups = static_cast<int>(groups);
-        pipe_launches().fetch_add(1, std::memory_order_relaxed);
-        pa.fast16 = t->d_fast.as<uint16_t>();
-        pa.rows_fast = t->d_rows_fast.as<int2>();
-        pa.ntab = la.ntab;
-        pa.tab_entries = t->host.size() * 2 <= static_cast<size_t>(kExpandTabBytes) ? static_cast<int>(t->host.size()) : 0;
-        pa.cap = la.cap;
+      if (piped && temp.alloc(lay.total, st) != hipSuccess) {
+        // no room for the call words (a smaller or busier device): the lane-per-stream kernel codes this launch
+        (void)hipGetLastError();
+        temp.p = nullptr;
+        piped = false;
+      }
+      if (piped) {
+        bind_workspace(&pa, temp.as<uint8_t>(), lay, groups);
         // nothing known about any tile, no tile released, no fallback
-        TFC_HIP(hipMemsetAsync(pa.status, 0, status_bytes + done_bytes + 512, st));
-        PipeChainJobs cj;
-        cj.streams = streams;
-        for (int k = 0; k < gn; ++k)
-          cj.job[k] = PipeChainJob{jobs.job[k].state, jobs.job[k].chunk, jobs.job[k].chunk_len, jobs.job[k].overflow_flag};
-        // A large launch: the chain (workgroups of PipeEncChainLds::kGroups groups, helper waves: range_pipe.h) on the library's own stream
-        // next to the expansion.  A small one — a model step's few groups, next to other steps' convolutions — one-wave
-        // chain workgroups behind the expansion on the caller's stream: measured on bmshj2018 with steps in flight, the
-        // second stream, its events and the large workgroups cost more (45 against 36 ms per step) than the overlap of
-        // two short kernels gives.
-        const bool large = groups >= 64;
-        const int overlap = large ? pipe_overlap() : 0;
-        SideStream side;
-        if (overlap) {
-          if (side_stream(st, &side)) return 1;
-          TFC_HIP(hipEventRecord(side.fork, st));
-          TFC_HIP(hipStreamWaitEvent(side.stream, side.fork, 0));
-        }
-        const hipStream_t cst = overlap ? side.stream : st;
-        const dim3 xgrid(static_cast<unsigned>(groups * pa.nt));
-        auto expand = [&] {
-          KernelTimer t2("enc_expand", st);
-          const bool tlds = pa.tab_entries != 0;
-          if (indexed && tlds) hipLaunchKernelGGL((enc_expand_kernel<true, Src, true>), xgrid, dim3(kExpandThreads), 0, st, jobs, pa);
-          else if (indexed) hipLaunchKernelGGL((enc_expand_kernel<true, Src, false>), xgrid, dim3(kExpandThreads), 0, st, jobs, pa);
-          else if (tlds) hipLaunchKernelGGL((enc_expand_kernel<false, Src, true>), xgrid, dim3(kExpandThreads), 0, st, jobs, pa);
-          else hipLaunchKernelGGL((enc_expand_kernel<false, Src, false>), xgrid, dim3(kExpandThreads), 0, st, jobs, pa);
-        };
-        const int cgroups = PipeEncChainLds::kGroups;
-        const unsigned cblocks = static_cast<unsigned>(ceil_div(static_cast<int64_t>(groups), cgroups));
-        const int clds = cgroups * PipeEncChainLds::kGroup;
-        if (large)
-          if (int rc = allow_dynamic_lds(reinterpret_cast<const void*>(&enc_chain_kernel), clds)) return rc;
-        auto chain = [&] {
-          KernelTimer t2("enc_chain", cst);
-          if (!large) {
-            hipLaunchKernelGGL(enc_chain_direct_kernel, dim3(static_cast<unsigned>(groups)), dim3(64), 0, cst, cj, pa);
-            return;
-          }
-          hipLaunchKernelGGL(enc_chain_kernel, dim3(cblocks), dim3(256 * cgroups), clds, cst, cj, pa);
-          // (the expansion behind the chain's workgroups, not in their way)
-          if (overlap == 2)
-            hipLaunchKernelGGL(enc_gate_kernel, dim3(1), dim3(1), 0, st, pa.started, cblocks, static_cast<long long>(20000));
-        };
-        if (overlap == 2) { chain(); expand(); }
-        else { expand(); chain(); }
-        if (overlap) {
-          TFC_HIP(hipEventRecord(side.join, side.stream));
-          TFC_HIP(hipStreamWaitEvent(st, side.join, 0));
-        }
-        hipLaunchKernelGGL(enc_commit_kernel, dim3(static_cast<unsigned>(groups)), dim3(64), 0, st, cj, pa);
+        TFC_HIP(hipMemsetAsync(temp.as<uint8_t>() + lay.zero_offset, 0, lay.zero_bytes, st));
+        // 3. the launches: expansion, chain, commit
+        pipe_launches().fetch_add(1, std::memory_order_relaxed);
+        if (int rc = launch_enc_pipe(jobs, pa, pipe, dev, indexed, st)) return rc;
+        // 4. ... and the lane-per-stream kernel behind them for the jobs they gave up on
         la.guard = pa.fallback;
-      } while (false);
+      }
       const dim3 grid(static_cast<unsigned>(jobs.blocks_per_job * gn));
       if (piped && !pipe_fallback_launch()) {}
-      else if (indexed) hipLaunchKernelGGL((enc_lanes_kernel<true, Src>), grid, dim3(block), lds_bytes, st, jobs, la);
-      else hipLaunchKernelGGL((enc_lanes_kernel<false, Src>), grid, dim3(block), lds_bytes, st, jobs, la);
+      else with_flags(indexed, [&](auto I) {
+        hipLaunchKernelGGL((enc_lanes_kernel<decltype(I)::value, Src>), grid, dim3(lanes.block), lanes.lds_bytes, st, jobs, la);
+      });
       // `temp` goes back to the library's cache in stream order, behind these launches
     }
     hipLaunchKernelGGL((enc_error_kernel<Src>), dim3(1), dim3(64), 0, st, errs);
     TFC_HIP(hipGetLastError());
   }
-  bool any_eager = false;
-  for (int k = 0; k < n; ++k) any_eager |= !es[k]->deferred;
-  if (any_eager) {
-    TFC_HIP(hipStreamSynchronize(st));
-    for (int k = 0; k < n; ++k) {
-      tfc_encoder* e = es[k];
-      if (e->deferred) continue;
-      unsigned long long host_status[4];
-      TFC_HIP(hipMemcpy(host_status, e->status.p, sizeof(host_status), hipMemcpyDeviceToHost));
-      if (host_status[0] != ~0ull) return encoder_error(e, host_status);
-      if (!speculative) continue;
-      unsigned int oflag = 0;
-      TFC_HIP(hipMemcpy(&oflag, e->oflag.p, sizeof(oflag), hipMemcpyDeviceToHost));
-      if (oflag) {
-        // a stream outgrew the speculative slab: back to the pre-call state, code again with the bound
-        // that cannot be exceeded
-        TFC_HIP(hipMemcpyAsync(e->state.p, backups[k].p, sizeof(uint4) * streams, hipMemcpyDeviceToDevice, st));
-        TFC_HIP(hipMemsetAsync(e->oflag.p, 0, sizeof(unsigned int), st));
-        e->chunks.pop_back();
-        const int32_t* ix = indexed ? indexes[k] : nullptr;
-        if (encode_lanes_many(&es[k], 1, &srcs[k], &ix, elems, st, true)) return 1;
-      }
-    }
-  }
-  return 0;
+  return settle_eager_encoders(es, n, srcs, indexes, elems, st, speculative, backups.data());
 }
 
 // Deferred-error handles, wave-per-stream families: the counting pass's first error goes to the handle's
@@ -1962,6 +2043,81 @@ int launch_wave_decoder(tfc_decoder* d, const int32_t* index, int64_t elems, con
              : launch(&dec_kernel<false, Dst>, dim3(blocks), dim3(kBlock), 0, st, p, dst);
 }
 
+// The regions of a pipelined decode launch's workspace at `base`
+inline void bind_workspace(PipeDecArgs* pa, uint8_t* base, const plan::DecLayout& lay, size_t groups) {
+  pa->raw = reinterpret_cast<unsigned short*>(base + lay.raw);
+  pa->posrec = reinterpret_cast<unsigned int*>(base + lay.posrec);
+  pa->state_out = reinterpret_cast<uint4*>(base + lay.state_out);
+  pa->kend = reinterpret_cast<unsigned int*>(base + lay.kend);
+  pa->rowaddr = reinterpret_cast<unsigned short*>(base + lay.rowaddr);
+  pa->fallback = reinterpret_cast<unsigned int*>(base + lay.fallback);
+  pa->started = reinterpret_cast<unsigned int*>(base + lay.started);
+  pa->progress = reinterpret_cast<unsigned int*>(base + lay.progress);
+  pa->tile_done = reinterpret_cast<unsigned int*>(base + lay.tile_done);
+  pa->groups = static_cast<int>(groups);
+}
+
+// The pipelined kernels of one decode launch (pa bound to its zeroed workspace; pla: the chain's image).
+// The chain on the library's own stream, the parse next to it on the caller's: tiles of raw rows are turned
+// into elements as the chain releases them, and a second pass behind the chain takes what the first left
+// (the last rows, tiles it did not get in time) and commits the successor states.
+// (a large launch only: see launch_enc_pipe)
+template <typename Dst>
+int launch_dec_pipe(const DecLaneJobs<Dst>& jobs, PipeDecArgs pa, const LaneArgs& pla, const plan::DecPipePlan& pipe,
+                    const plan::DeviceFacts& dev, const tfc_tables* t, bool indexed, hipStream_t st) {
+  const int gn = jobs.n;
+  const size_t groups = static_cast<size_t>(pa.groups);
+  const int overlap = plan::launch_overlap(dev, groups);
+  PipeDecJobs cj;
+  cj.streams = jobs.streams;
+  cj.elems = jobs.elems;
+  cj.blocks_per_job = static_cast<int>(ceil_div(pa.groups_per_job, pipe.pblock / 64));
+  cj.n = gn;
+  for (int k = 0; k < gn; ++k) cj.job[k] = PipeDecJob{jobs.job[k].blob, jobs.job[k].off, jobs.job[k].state};
+  if (indexed) {
+    PipeRowJobs rj;
+    rj.per_job = jobs.streams * jobs.elems;
+    rj.ntab = pla.ntab;
+    rj.n = gn;
+    for (int k = 0; k < gn; ++k) { rj.job[k].index = jobs.job[k].index; rj.job[k].first_error = jobs.job[k].first_error; }
+    hipLaunchKernelGGL(dec_rows_kernel, dim3(static_cast<unsigned>(ceil_div(rj.per_job, 1024)), static_cast<unsigned>(gn)),
+                       dim3(256), 0, st, rj, const_cast<unsigned short*>(pa.rowaddr));
+  }
+  SideFork side(st);
+  if (overlap && side.fork()) return 1;
+  const hipStream_t cst = side.stream;
+  const dim3 cgrid(static_cast<unsigned>(cj.blocks_per_job * gn));
+  const dim3 pgrid(static_cast<unsigned>(groups * pipe.tiles));
+  const dim3 pgrid_next(static_cast<unsigned>(groups * pipe.ctiles));      // (the tiles every stream is sure to reach)
+  {
+    KernelTimer t2("dec_chain", cst);
+    with_flags(pipe.pairs, indexed, [&](auto P, auto I) {
+      hipLaunchKernelGGL((dec_chain_kernel<decltype(I)::value, decltype(P)::value>), cgrid, dim3(pipe.pblock), pipe.plds, cst, cj, pla, pa);
+    });
+  }
+  const PipePairMap pm{t->d_pair_adjust.as<int>()};
+  auto parse = [&](int concurrent) {
+    pa.concurrent = concurrent;
+    const dim3 g = concurrent ? pgrid_next : pgrid;
+    const DecRow* dd = t->d_dec_dir.as<DecRow>();
+    with_flags(pipe.pairs, indexed, [&](auto P, auto I) {
+      hipLaunchKernelGGL((dec_parse_kernel<decltype(I)::value, decltype(P)::value, Dst>), g, dim3(256), 0, st, jobs, pa, dd, pla.ntab, pm);
+    });
+  };
+  if (overlap) {
+    KernelTimer t2("dec_parse_next", st);      // (next to the chain: as long as the chain, by construction)
+    // (the chain's workgroups first: where one takes a CU's whole LDS it cannot be placed next to parse workgroups)
+    hipLaunchKernelGGL(enc_gate_kernel, dim3(1), dim3(1), 0, st, pa.started, cgrid.x, static_cast<long long>(20000));
+    parse(1);
+  }
+  if (int rc = side.join()) return rc;
+  {
+    KernelTimer t2("dec_parse", st);           // behind the chain: what the first pass left
+    parse(0);
+  }
+  return 0;
+}
+
 // Lane-per-stream family: n handles (same tables, same stream count) decoded by one launch per
 // kMaxLaneJobs of them.  Where the geometry allows, the pipelined kernels of range_pipe.h take the launch (chain into
 // raw rows, then the parallel parse into `dsts`) and the lane-per-stream kernel behind them only decodes the jobs
@@ -1969,95 +2125,39 @@ int launch_wave_decoder(tfc_decoder* d, const int32_t* index, int64_t elems, con
 template <typename Dst>
 int decode_lanes_many(tfc_decoder* const* ds, int n, const Dst* dsts, const int32_t* const* indexes,
                       int64_t elems, hipStream_t st) {
-  constexpr int kMaxLaneJobs = DecLaneJobs<Dst>::kMax;
   const tfc_tables* t = ds[0]->tables;
   const int64_t streams = ds[0]->streams;
   const bool indexed = indexes && indexes[0];
-  LaneArgs la;
-  la.image = t->d_lane_image.as<uint32_t>();
-  la.bytes = t->lane_dec_bytes;
-  la.ntab = static_cast<int>(t->rows.size());
-  la.precision = t->lane_precision;
-  la.cap = 0;
-  la.defer = lanes_escape_defer();
-  la.guard = nullptr;
-  la.lds_image = (t->lane_dec_bytes + 1023) & ~1023;
-  using WaveLds = DecWaveLds<typename Dst::elem>;
-  la.lds_wave = indexed ? WaveLds::kBytes : WaveLds::kIndex;
-  // the lane-per-stream kernel (the pipelined kernels' fallback, or the launch's decoder) needs its image + a wave's
-  // staging in a CU's LDS; tables whose image is larger (bls2017's 192 x 128 symbols: 176 KB) have the wave-per-stream
-  // kernels as the fallback, handle by handle
-  const bool lanes_fit = la.lds_image + la.lds_wave <= kLds;
-  const int block = lanes_fit ? std::min(lanes_block(streams * n), 64 * ((kLds - la.lds_image) / la.lds_wave)) : 64;
-  const int lds_bytes = la.lds_image + (block / 64) * la.lds_wave;
-  const void* fn = indexed ? reinterpret_cast<const void*>(&dec_lanes_kernel<true, Dst>)
-                           : reinterpret_cast<const void*>(&dec_lanes_kernel<false, Dst>);
-  if (lanes_fit)
-    if (int rc = allow_dynamic_lds(fn, lds_bytes)) return rc;
-  // pipelined launch plan: groups of 64 streams; rows = steps of the chain (one per element, plus the bits of
-  // escape codes: a quarter more is planned for when the tables have escape rows)
-  PipeDecArgs pa;
-  LaneArgs pla = la;
-  pa.groups_per_job = static_cast<int>(ceil_div(streams, 64));
-  // (+ the blocks lanes sit out or spend finishing an escape code before the wave's tail pass, and the tail pass)
-  const int64_t rows64 = ((elems + (t->any_escape ? elems / 4 + 64 + 24 * kPipeBlock : 2 * kPipeBlock)) + kPipeBlock - 1) / kPipeBlock * kPipeBlock;
-  pa.rows = static_cast<int>(std::min<int64_t>(rows64, (int64_t{1} << 30)));
-  const size_t raw_bytes = static_cast<size_t>(pa.rows) * 128;      // 16-bit entries, 64 lanes
-  const size_t rec_bytes = (static_cast<size_t>(pa.rows) / kPipeBlock + 1) * 256;
-  const size_t group_bytes = raw_bytes + rec_bytes + 64 * sizeof(uint4) + sizeof(unsigned int);
-  const size_t job_bytes = group_bytes * pa.groups_per_job + (indexed ? 2 * static_cast<size_t>(streams) * elems : 0);
-  pla.lds_wave = (indexed ? PipeDecLds::kBytes : PipeDecLds::kRows) + PipeDecLds::kStage;
-  const size_t kPipeTempBytes = pipe_temp_bytes();
-  // Which image the chain runs on, and how many chain waves share a workgroup's copy of it.  A launch's chain
-  // workgroups must all be resident at once (a second round doubles the launch's time and the parse next to the chain
-  // gives up on groups that do not move), one wave per SIMD at most: the full image where it fits and hosts the call's
-  // waves (BASELINE config 2: 150 KB, one wave per CU = 32 batches per launch), else the compact one (92 KB for config 2:
-  // four waves per CU, 128 batches per launch; 115 KB for bls2017's tables, whose full image does not fit at all).
-  const int cus_d = device_cus();
-  const int64_t waves_call = static_cast<int64_t>(pa.groups_per_job) * std::min(n, kMaxLaneJobs);
-  auto waves_fit = [&](int image_bytes) { return std::max(0, (kLds - image_bytes) / pla.lds_wave); };
-  const int pair_image = (t->pair_dec_bytes + 1023) & ~1023;
-  const int fit_full = waves_fit(pla.lds_image), fit_pairs = t->pairs_ok ? waves_fit(pair_image) : 0;
-  bool pairs = false;
-  switch (pipe_format()) {
-    case 1: pairs = false; break;
-    case 2: pairs = fit_pairs >= 1; break;
-    // (beyond three quarters of the CUs under full-image chain workgroups — each fills its CU's LDS — the parse next to the
-    // chain finds no room and runs behind it: 32 batches of config 2 decode in 10.1 ms on the full image, 9.1 on the
-    // compact one, whose workgroups leave 50 KB of every CU to two parse workgroups)
-    default: pairs = fit_pairs >= 1 && (fit_full < 1 || 4 * waves_call > 3 * static_cast<int64_t>(cus_d) * std::min(fit_full, 4));
+  // the facts, and the plans made of them (range_plan.h)
+  const plan::TableFacts tf = table_facts(t);
+  const plan::DeviceFacts dev = device_facts();
+  constexpr plan::KernelFacts kf = kernel_facts<DecWaveLds<typename Dst::elem>, DecLaneJobs<Dst>::kMax>();
+  const plan::LanePlan lanes = plan::lane_plan(tf.lane_dec_bytes, kf, dev, streams * n, indexed);
+  const plan::DecPipePlan pipe = plan::dec_pipe_plan(tf, dev, kf, streams, elems, n, indexed);
+  LaneArgs la = lane_args(t, t->lane_dec_bytes, lanes);
+  if (lanes.fits) {
+    const void* fn = with_flags(indexed, [](auto I) { return reinterpret_cast<const void*>(&dec_lanes_kernel<decltype(I)::value, Dst>); });
+    if (int rc = allow_dynamic_lds(fn, lanes.lds_bytes)) return rc;
   }
-  if (pairs) {
+  // the chain's view of the tables: the full image (the lane kernels') or the compact one
+  LaneArgs pla = la;
+  pla.lds_wave = pipe.lds_wave;
+  pla.lds_image = pipe.lds_image;
+  if (pipe.pairs) {
     pla.image = t->d_pair_image.as<uint32_t>();
     pla.bytes = t->pair_dec_bytes;
-    pla.lds_image = pair_image;
   }
-  const int fit = pairs ? fit_pairs : fit_full;
-  // waves per workgroup: as few as host the call on the chip's CUs (a chain wave wants a SIMD to itself); under
-  // tfc_set_chip_shared — other kernels beside the coder's — four, so that the chains hold few CUs' LDS
-  int per = static_cast<int>(std::min<int64_t>(8, std::max<int64_t>(1, ceil_div(waves_call, static_cast<int64_t>(cus_d)))));
-  if (chip_shared()) per = std::max(per, static_cast<int>(std::min<int64_t>(4, pa.groups_per_job)));
-  if (pipe_waves_env() > 0) per = pipe_waves_env();
-  per = std::min(per, std::min(fit, pa.groups_per_job));
-  const int pblock = 64 * std::max(per, 0);
-  // (precision 16: a quotient can equal the "no escape symbol" mark of dec_chain_kernel's directory, 0xFFFF)
-  const bool pipe = pipe_enabled() && pblock >= 64 && rows64 < (int64_t{1} << 30) && job_bytes <= kPipeTempBytes &&
-                    (!indexed || la.ntab < 4096) && t->lane_precision <= 15 &&
-                    (static_cast<int64_t>(pa.rows) / kParseRows + 1) * pa.groups_per_job * kMaxLaneJobs < (int64_t{1} << 31);
-  const int plds = pla.lds_image + (pblock / 64) * pla.lds_wave;
-  const size_t chain_wgs_per_job = static_cast<size_t>(ceil_div(pa.groups_per_job, std::max(1, pblock / 64)));
-  const size_t resident_wgs = static_cast<size_t>(cus_d) * std::max<size_t>(1, kLds / std::max(1, plds));
-  const size_t resident_jobs = std::max<size_t>(1, resident_wgs / std::max<size_t>(1, chain_wgs_per_job));
-  const int per_launch = !pipe ? kMaxLaneJobs
-                               : static_cast<int>(std::max<size_t>(1, std::min<size_t>(std::min<size_t>(kMaxLaneJobs, resident_jobs),
-                                                                                      kPipeTempBytes / std::max<size_t>(job_bytes, 1))));
-  const void* pfn = nullptr;
-  if (pipe) {
-    pfn = pairs ? (indexed ? reinterpret_cast<const void*>(&dec_chain_kernel<true, true>) : reinterpret_cast<const void*>(&dec_chain_kernel<false, true>))
-                : (indexed ? reinterpret_cast<const void*>(&dec_chain_kernel<true, false>) : reinterpret_cast<const void*>(&dec_chain_kernel<false, false>));
-    if (int rc = allow_dynamic_lds(pfn, plds)) return rc;
+  PipeDecArgs pa;
+  pa.groups_per_job = pipe.groups_per_job;
+  pa.rows = pipe.rows;
+  pa.poll_ticks = 200000;         // 2 ms: the chain releases rows every ~0.2 ms
+  if (pipe.enabled) {
+    const void* pfn = with_flags(pipe.pairs, indexed, [](auto P, auto I) {
+      return reinterpret_cast<const void*>(&dec_chain_kernel<decltype(I)::value, decltype(P)::value>);
+    });
+    if (int rc = allow_dynamic_lds(pfn, pipe.plds)) return rc;
   }
-  if (!pipe && !lanes_fit) {
+  if (!pipe.enabled && !lanes.fits) {
     // neither the pipelined kernels nor the lane-per-stream kernel can take the call: one wave per stream
     for (int k = 0; k < n; ++k) {
       KernelTimer timer("dec_kernel", st);
@@ -2065,13 +2165,13 @@ int decode_lanes_many(tfc_decoder* const* ds, int n, const Dst* dsts, const int3
     }
     return 0;
   }
-  const PipePairMap pm{t->d_pair_adjust.as<int>()};
-  for (int g0 = 0; g0 < n; g0 += per_launch) {
-    const int gn = std::min(per_launch, n - g0);
+  for (int g0 = 0; g0 < n; g0 += pipe.per_launch) {
+    const int gn = std::min(pipe.per_launch, n - g0);
+    // 1. the jobs
     DecLaneJobs<Dst> jobs;
     jobs.streams = streams;
     jobs.elems = elems;
-    jobs.blocks_per_job = static_cast<int>(ceil_div(streams, block));
+    jobs.blocks_per_job = static_cast<int>(ceil_div(streams, lanes.block));
     jobs.n = gn;
     for (int k = 0; k < gn; ++k) {
       tfc_decoder* d = ds[g0 + k];
@@ -2084,117 +2184,39 @@ int decode_lanes_many(tfc_decoder* const* ds, int n, const Dst* dsts, const int3
       J.first_error = d->status.as<unsigned long long>();
     }
     KernelTimer timer("dec_kernel", st);
+    // 2. the workspace of the pipelined kernels
     DevBuf temp;
-    bool piped = pipe;
+    const size_t groups = static_cast<size_t>(pipe.groups_per_job) * gn;
+    const plan::DecLayout lay = plan::dec_layout(pipe, groups, gn, indexed, streams, elems);
+    bool piped = pipe.enabled;
     la.guard = nullptr;
-    if (pipe) do {
-      const size_t groups = static_cast<size_t>(pa.groups_per_job) * gn;
-      const size_t tiles = static_cast<size_t>(pa.rows) / kParseRows + 1;
-      const size_t raw_all = raw_bytes * groups, rec_all = rec_bytes * groups, st_all = 64 * sizeof(uint4) * groups;
-      const size_t kend_all = (sizeof(unsigned int) * groups + 255) & ~size_t{255};
-      const size_t addr_all = indexed ? ((2 * static_cast<size_t>(streams) * elems * gn + 255) & ~size_t{255}) : 0;
-      // zeroed per launch: fallback flags (64 jobs), chain workgroups started, rows released per group, tiles taken
-      const size_t flags_all = (512 + sizeof(unsigned int) * groups * (1 + tiles) + 255) & ~size_t{255};
-      if (temp.alloc(raw_all + rec_all + st_all + kend_all + addr_all + flags_all, st) != hipSuccess) {
-        // no room for the raw rows: the lane-per-stream kernel decodes this launch
-        (void)hipGetLastError();
-        temp.p = nullptr;
-        piped = false;
-        break;
-      }
-      uint8_t* base = temp.as<uint8_t>();
-      pa.raw = reinterpret_cast<unsigned short*>(base);
-      pa.posrec = reinterpret_cast<unsigned int*>(base + raw_all);
-      pa.state_out = reinterpret_cast<uint4*>(base + raw_all + rec_all);
-      pa.kend = reinterpret_cast<unsigned int*>(base + raw_all + rec_all + st_all);
-      unsigned short* rowaddr = reinterpret_cast<unsigned short*>(base + raw_all + rec_all + st_all + kend_all);
-      pa.rowaddr = rowaddr;
-      pa.fallback = reinterpret_cast<unsigned int*>(base + raw_all + rec_all + st_all + kend_all + addr_all);
-      pa.started = pa.fallback + 64;
-      pa.progress = pa.fallback + 128;
-      pa.tile_done = pa.progress + groups;
-      pa.groups = static_cast<int>(groups);
-      pa.poll_ticks = 200000;         // 2 ms: the chain releases rows every ~0.2 ms
+    if (piped && temp.alloc(lay.total, st) != hipSuccess) {
+      // no room for the raw rows: the lane-per-stream kernel decodes this launch
+      (void)hipGetLastError();
+      temp.p = nullptr;
+      piped = false;
+    }
+    if (piped) {
+      bind_workspace(&pa, temp.as<uint8_t>(), lay, groups);
       // (kend of a group the chain gave up on stays unset: the parse skips the whole job under its fallback flag)
-      TFC_HIP(hipMemsetAsync(pa.fallback, 0, flags_all, st));
+      TFC_HIP(hipMemsetAsync(temp.as<uint8_t>() + lay.zero_offset, 0, lay.zero_bytes, st));
+      // 3. the launches: row addresses (index mode), chain, parse
       pipe_launches().fetch_add(1, std::memory_order_relaxed);
-      PipeDecJobs cj;
-      cj.streams = streams;
-      cj.elems = elems;
-      cj.blocks_per_job = static_cast<int>(ceil_div(pa.groups_per_job, pblock / 64));
-      cj.n = gn;
-      for (int k = 0; k < gn; ++k) cj.job[k] = PipeDecJob{jobs.job[k].blob, jobs.job[k].off, jobs.job[k].state};
-      if (indexed) {
-        PipeRowJobs rj;
-        rj.per_job = streams * elems;
-        rj.ntab = la.ntab;
-        rj.n = gn;
-        for (int k = 0; k < gn; ++k) { rj.job[k].index = jobs.job[k].index; rj.job[k].first_error = jobs.job[k].first_error; }
-        hipLaunchKernelGGL(dec_rows_kernel, dim3(static_cast<unsigned>(ceil_div(rj.per_job, 1024)), static_cast<unsigned>(gn)),
-                           dim3(256), 0, st, rj, rowaddr);
-      }
-      // The chain on the library's own stream, the parse next to it on the caller's: tiles of raw rows are turned
-      // into elements as the chain releases them, and a second pass behind the chain takes what the first left
-      // (the last rows, tiles it did not get in time) and commits the successor states.
-      // (a large launch only: see encode_lanes_many)
-      const int overlap = groups >= 64 ? pipe_overlap() : 0;
-      SideStream side;
-      if (overlap) {
-        if (side_stream(st, &side)) return 1;
-        TFC_HIP(hipEventRecord(side.fork, st));
-        TFC_HIP(hipStreamWaitEvent(side.stream, side.fork, 0));
-      }
-      const hipStream_t cst = overlap ? side.stream : st;
-      const dim3 cgrid(static_cast<unsigned>(cj.blocks_per_job * gn));
-      const dim3 pgrid(static_cast<unsigned>(groups * tiles));
-      // The pass next to the chain takes the tiles every stream is sure to reach (a row per element at least); the rows
-      // beyond — escape codes' bit rows past the last element's place, a fraction of a percent — and the planned-for
-      // capacity behind them (a quarter more) are the second pass's: workgroups of tiles that never fill would only be
-      // dispatched behind the last real ones, wait for the chain's end and leave (16 000 of them in the 20-batch launch).
-      const size_t ctiles = std::min<size_t>(tiles, static_cast<size_t>(ceil_div(elems, static_cast<int64_t>(kParseRows))));
-      const dim3 pgrid_next(static_cast<unsigned>(groups * ctiles));
-      {
-        KernelTimer t2("dec_chain", cst);
-        if (pairs && indexed) hipLaunchKernelGGL((dec_chain_kernel<true, true>), cgrid, dim3(pblock), plds, cst, cj, pla, pa);
-        else if (pairs) hipLaunchKernelGGL((dec_chain_kernel<false, true>), cgrid, dim3(pblock), plds, cst, cj, pla, pa);
-        else if (indexed) hipLaunchKernelGGL((dec_chain_kernel<true, false>), cgrid, dim3(pblock), plds, cst, cj, pla, pa);
-        else hipLaunchKernelGGL((dec_chain_kernel<false, false>), cgrid, dim3(pblock), plds, cst, cj, pla, pa);
-      }
-      auto parse = [&](int concurrent) {
-        pa.concurrent = concurrent;
-        const dim3 g = concurrent ? pgrid_next : pgrid;
-        const DecRow* dd = t->d_dec_dir.as<DecRow>();
-        if (pairs && indexed) hipLaunchKernelGGL((dec_parse_kernel<true, true, Dst>), g, dim3(256), 0, st, jobs, pa, dd, la.ntab, pm);
-        else if (pairs) hipLaunchKernelGGL((dec_parse_kernel<false, true, Dst>), g, dim3(256), 0, st, jobs, pa, dd, la.ntab, pm);
-        else if (indexed) hipLaunchKernelGGL((dec_parse_kernel<true, false, Dst>), g, dim3(256), 0, st, jobs, pa, dd, la.ntab, pm);
-        else hipLaunchKernelGGL((dec_parse_kernel<false, false, Dst>), g, dim3(256), 0, st, jobs, pa, dd, la.ntab, pm);
-      };
-      if (overlap) {
-        KernelTimer t2("dec_parse_next", st);      // (next to the chain: as long as the chain, by construction)
-        // (the chain's workgroups first: where one takes a CU's whole LDS it cannot be placed next to parse workgroups)
-        hipLaunchKernelGGL(enc_gate_kernel, dim3(1), dim3(1), 0, st, pa.started, cgrid.x, static_cast<long long>(20000));
-        parse(1);
-      }
-      if (overlap) {
-        TFC_HIP(hipEventRecord(side.join, side.stream));
-        TFC_HIP(hipStreamWaitEvent(st, side.join, 0));
-      }
-      {
-        KernelTimer t2("dec_parse", st);           // behind the chain: what the first pass left
-        parse(0);
-      }
+      if (int rc = launch_dec_pipe(jobs, pa, pla, pipe, dev, t, indexed, st)) return rc;
+      // 4. ... and the fallback behind them for the jobs they gave up on
       la.guard = pa.fallback;
-    } while (false);
+    }
     const dim3 grid(static_cast<unsigned>(jobs.blocks_per_job * gn));
     if (piped && !pipe_fallback_launch()) {}
-    else if (!lanes_fit) {
+    else if (!lanes.fits) {
       // (the tables' lane image does not fit a CU) what the pipelined kernels gave up on — or, without temporaries, the
       // whole launch — on the wave-per-stream kernels, handle by handle under its fallback flag
       for (int k = 0; k < gn; ++k)
         if (launch_wave_decoder(ds[g0 + k], jobs.job[k].index, elems, dsts[g0 + k], st, piped ? pa.fallback + k : nullptr)) return 1;
     }
-    else if (indexed) hipLaunchKernelGGL((dec_lanes_kernel<true, Dst>), grid, dim3(block), lds_bytes, st, jobs, la);
-    else hipLaunchKernelGGL((dec_lanes_kernel<false, Dst>), grid, dim3(block), lds_bytes, st, jobs, la);
+    else with_flags(indexed, [&](auto I) {
+      hipLaunchKernelGGL((dec_lanes_kernel<decltype(I)::value, Dst>), grid, dim3(lanes.block), lanes.lds_bytes, st, jobs, la);
+    });
   }
   TFC_HIP(hipGetLastError());
   return 0;
@@ -2246,11 +2268,9 @@ bool decodes_on_lanes(const tfc_decoder* d, int64_t streams_in_launch, int64_t e
   const tfc_tables* t = d->tables;
   // (which wave-per-stream kernel runs otherwise is launch_wave_decoder's choice)
   if (select_family(t, d->mode, streams_in_launch, elems, false) != kLanes) return false;
-  using WaveLds = DecWaveLds<Elem>;
-  const int need = ((t->lane_dec_bytes + 1023) & ~1023) + (indexed ? WaveLds::kBytes : WaveLds::kIndex);
-  const int need_pairs = ((t->pair_dec_bytes + 1023) & ~1023) + (indexed ? PipeDecLds::kBytes : PipeDecLds::kRows) + PipeDecLds::kStage;
-  const bool compact_ok = t->pairs_ok && pipe_enabled() && pipe_format() != 1 && need_pairs <= kLds;
-  return need <= kLds || compact_ok;
+  // (the job limit is no part of the question)
+  constexpr plan::KernelFacts kf = kernel_facts<DecWaveLds<Elem>, 0>();
+  return plan::decode_fits_lanes(table_facts(t), kf, indexed, kLds, pipe_enabled(), pipe_format());
 }
 
 // One handle that decode_jobs did not batch (checked and touched there)

@@ -4,6 +4,10 @@ equal the oracle's (cc/kernels/range_coder_kernels.cc:191-322, 360-471; cc/lib/r
 be THESE kernels that produced them: tfc_pipe_counters tells whether the lane-per-stream fallback had to take a job.
 (tests/test_range_coder_gpu.py runs every golden vector through the same kernels via the "throughput" fixture.)"""
 import ctypes as C
+import json
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -235,6 +239,109 @@ def test_more_groups_than_the_chip_hosts_at_once(tfc, port):
             assert [bytes(s) for s in tfc.fetch_strings(h)] == port.encode(lookup, v)[0], k
     l1, f1 = counters()
     assert l1 - l0 >= 3 and f1 - f0 == 0, (l1 - l0, f1 - f0)
+
+
+# The split that only the temp budget causes: TFC_PIPE_TEMP_MB is read once per process, so a child process.  Three runs of
+# 20 handles (64 streams x 256 elements, 1 % escape codes): eager handles (each backs its coder states up before the
+# launch that codes it), deferred handles, and index mode through the raw `*_many` entries.  The child prints, per run,
+# the pipelined launches and fallback workgroups of the encode call and of the decode call.
+_TEMP_SPLIT = """
+import ctypes as C
+import json
+import sys
+import numpy as np
+import torch
+import compression_amd as tfc
+from compression_amd import _lib
+sys.path.insert(0, sys.argv[2])
+from test_pipe_gpu import counters, dev
+z = np.load(sys.argv[1], allow_pickle=True)
+lookup, n = z["lookup"], int(z["n"])
+streams, elems = z["value0"].shape
+lt = torch.from_numpy(lookup)
+tfc.set_default_mode("throughput")
+lib, st = _lib.lib(), _lib.stream_ptr()
+ptrs = lambda xs: (C.c_void_p * n)(*xs)
+counts = []
+for run in ("eager", "deferred", "indexed"):
+    values = [z["%s%d" % ("ivalue" if run == "indexed" else "value", k)] for k in range(n)]
+    strings = [[bytes(x) for x in z["%s%d" % ("istrings" if run == "indexed" else "strings", k)]] for k in range(n)]
+    l0, f0 = counters()
+    hs = tfc.create_range_encoders(n, [streams], lt, deferred_errors=run != "eager")
+    if run == "indexed":
+        keep = [(dev(z["index%d" % k]), dev(v)) for k, v in enumerate(values)]
+        ip = ptrs([i.data_ptr() for i, _ in keep])
+        _lib.check(lib.tfc_encoder_encode_many(n, ptrs([h.ptr for h in hs]), ptrs([v.data_ptr() for _, v in keep]), ip,
+                                               elems, st))
+    else:
+        hs = tfc.entropy_encode_channel_many(hs, [dev(v) for v in values])
+    torch.cuda.synchronize()
+    l1, f1 = counters()
+    hs = tfc.entropy_encode_finalize_device_many(hs)
+    ds = tfc.create_range_decoders(hs, lt)
+    l2, f2 = counters()
+    if run == "indexed":
+        decoded = [torch.empty(streams, elems, dtype=torch.int32, device="cuda") for _ in range(n)]
+        _lib.check(lib.tfc_decoder_decode_many(n, ptrs([d.ptr for d in ds]), ip, ptrs([o.data_ptr() for o in decoded]),
+                                               elems, st))
+    else:
+        ds, decoded = tfc.entropy_decode_channel_many(ds, [elems], torch.int32)
+    oks = tfc.entropy_decode_finalize_device_many(ds)
+    torch.cuda.synchronize()
+    l3, f3 = counters()
+    for k in range(n):
+        assert [bytes(s) for s in tfc.fetch_strings(hs[k])] == strings[k], (run, k, "bytes differ")
+        assert np.array_equal(decoded[k].cpu().numpy().reshape(streams, elems), values[k]), (run, k, "symbols differ")
+        assert bool(oks[k].all()), (run, k, "Finalize")
+    counts.append([l1 - l0, f1 - f0, l3 - l2, f3 - f2])
+print("SPLIT", json.dumps(counts))
+"""
+
+
+def test_launches_split_by_the_temp_budget(port, tmp_path):
+    """TFC_PIPE_TEMP_MB=1: a job's temporaries are ~116 KB (encode) / ~112 KB (decode, + 32 KB of row addresses in
+    index mode), so 20 handles behind one call go out as 9 + 9 + 2 jobs (7 + 7 + 6 for the indexed decode): three
+    pipelined launches per direction where the chip alone would host all 20 in one.  Bytes against the oracle, every
+    element back, every Finalize flag, for eager handles (whose pre-call state backups are indexed across the launches),
+    deferred handles and index mode; and the launch and fallback counts are what the library gave before the launch plans
+    moved to range_plan.h: three launches each way and no fallback, except in the indexed encode, where one stream of
+    handle 14 takes 472 coder calls against the 448 rows planned (256 + 128 + 64) and its job, the sixth of the second
+    launch, goes to the lane-per-stream kernel under its own fallback flag."""
+    lookup = tables(port, 16)
+    n, streams, elems = 20, 64, 256
+    rng = np.random.default_rng(31)
+    rows = synthetic.lookup_rows(lookup)
+    arrays = {"lookup": lookup, "n": np.int64(n)}
+    for k in range(n):
+        value = synthetic.sample_symbols(lookup, streams, elems, seed=700 + k, escape_fraction=0.01)
+        # (index mode: values drawn through the indexed table, 1 % of them far outside it)
+        index = rng.integers(0, 16, value.shape).astype(np.int32)
+        u = rng.integers(0, 1 << 12, index.shape)
+        ivalue = np.zeros(index.shape, np.int32)
+        for t, (_, c) in enumerate(rows):
+            m = index == t
+            ivalue[m] = np.searchsorted(np.asarray(c), u[m], side="right") - 1
+        ivalue = np.where(rng.random(index.shape) < 0.01, rng.integers(-300, 300, index.shape) * 5, ivalue).astype(np.int32)
+        for name, strings in (("strings", port.encode(lookup, value)[0]),
+                              ("istrings", port.encode(lookup, ivalue, index=index)[0])):
+            arr = np.empty(len(strings), dtype=object)
+            for i, x in enumerate(strings):
+                arr[i] = x
+            arrays["%s%d" % (name, k)] = arr
+        arrays["value%d" % k], arrays["ivalue%d" % k], arrays["index%d" % k] = value, ivalue, index
+    np.savez(tmp_path / "cases.npz", **arrays)
+    here = os.path.dirname(os.path.abspath(__file__))
+    root = os.path.dirname(here)
+    env = dict(os.environ, TFC_PIPE_TEMP_MB="1", PYTHONPATH=root)
+    r = subprocess.run([sys.executable, "-c", _TEMP_SPLIT, str(tmp_path / "cases.npz"), here], cwd=root, env=env,
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    tag, _, text = r.stdout.strip().rpartition("\n")[2].partition(" ")
+    assert tag == "SPLIT", r.stdout[-1000:]
+    counts = json.loads(text)
+    print("pipelined launches / fallback workgroups (encode, decode) per run:", counts)
+    assert all(c[0] > 1 and c[2] > 1 for c in counts), counts
+    assert counts == [[3, 0, 3, 0], [3, 0, 3, 0], [3, 1, 3, 0]], counts
 
 
 @pytest.fixture(params=[1, 2], ids=["full", "compact"])
