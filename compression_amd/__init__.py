@@ -32,6 +32,8 @@ from .ops.scctx_ops import (SpaceChannelParams, SpaceChannelScan, scctx_decode, 
                             scctx_scan_reference)
 from .ops.mixture_ops import (mixture_bits, mixture_bits_reference, mixture_cdf, mixture_cdf_reference,  # noqa: F401
                               mixture_decode, mixture_encode, MixtureStrings)
+from .ops.ans_ops import (AnsStrings, ans_decode, ans_decode_reference, ans_encode, ans_encode_reference,  # noqa: F401
+                          strings_from_blob)
 from .ops.round_ops import round_st, soft_round, soft_round_conditional_mean, soft_round_inverse  # noqa: F401
 from .datasets import *  # noqa: F401,F403
 from .datasets.clip_dataset import ClipDataset  # noqa: F401

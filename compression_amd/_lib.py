@@ -196,6 +196,9 @@ SIGNATURES = {
                                   _vp]),
     "tfc_mixture_bits_forward": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _int, _i64, _i64, _vp, _vp]),
     "tfc_mixture_bits_backward": (_int, [_vp, _vp, _vp, _vp, _int, _int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tfc_ans_blob_capacity": (_i64, [_i64, _i64, _int]),
+    "tfc_ans_encode": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
+    "tfc_ans_decode": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _vp, _vp, _vp]),
 }
 
 # the dtype argument of the C ABI: entries on float32 / bfloat16 tensors, and those that take float16 as well

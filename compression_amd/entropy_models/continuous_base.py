@@ -12,13 +12,26 @@ from .. import _lib
 from ..distributions import helpers, uniform_noise
 from ..ops import gen_ops
 
-__all__ = ["ContinuousEntropyModelBase"]
+__all__ = ["ContinuousEntropyModelBase", "check_coder"]
+
+CODERS = ("range", "ans")
+
+
+def check_coder(coder, ans_lanes):
+    """The `coder` / `ans_lanes` options as the entropy models and the image models take them -> (coder, ans_lanes)."""
+    if coder not in CODERS:
+        raise ValueError(f"`coder` must be one of {CODERS}, got {coder!r}")
+    ans_lanes = int(ans_lanes)
+    if not 1 <= ans_lanes <= 64 or ans_lanes & (ans_lanes - 1):
+        raise ValueError(f"`ans_lanes` must be a power of two in [1, 64], got {ans_lanes}")
+    return coder, ans_lanes
 
 
 class ContinuousEntropyModelBase(torch.nn.Module, metaclass=abc.ABCMeta):
     def __init__(self, coding_rank=None, compression=False, stateless=False, expected_grads=False,
-                 tail_mass=2 ** -8, bottleneck_dtype=None, laplace_tail_mass=0):
+                 tail_mass=2 ** -8, bottleneck_dtype=None, laplace_tail_mass=0, coder="range", ans_lanes=64):
         super().__init__()
+        self._coder, self._ans_lanes = check_coder(coder, ans_lanes)
         self._prior = None
         self._coding_rank = int(coding_rank)
         self._compression = bool(compression)
@@ -36,6 +49,45 @@ class ContinuousEntropyModelBase(torch.nn.Module, metaclass=abc.ABCMeta):
         if not self.compression:
             raise RuntimeError(
                 "For range coding, the entropy model must be instantiated with `compression=True`.")
+
+    def _range_only(self, what):
+        """`what` belongs to the range coder's handle API: with coder="ans" it is an error that says so."""
+        if self.coder == "ans":
+            raise NotImplementedError(
+                f'{what} is not available with coder="ans": the interleaved rANS format has no handle API and reads '
+                'its strings back; use coder="range" for it.')
+
+    # coder="ans": the strings of ops.ans_ops, one stream per coding unit (DESIGN section 28)
+    def _ans_compressed(self, symbols, flat_indexes, batch_shape):
+        """symbols (and table indexes, or None for channel mode) int32 [*batch_shape, ...] -> object array of bytes
+        shaped batch_shape."""
+        import numpy as np
+
+        from ..ops import ans_ops
+        streams = int(torch.Size(batch_shape).numel())
+        symbols = symbols.reshape(streams, -1)
+        if flat_indexes is not None:
+            flat_indexes = flat_indexes.reshape(streams, -1)
+        encoded = ans_ops.ans_encode(self.cdf, symbols, flat_indexes, self.ans_lanes)
+        out = np.empty(streams, dtype=object)
+        out[:] = ans_ops.strings_from_blob(encoded)
+        return out.reshape(tuple(batch_shape))
+
+    def _ans_decompressed(self, strings, elems, flat_indexes):
+        """strings (any container of bytes) -> (symbols int32 [strings, elems], their shape); raises where a verdict is
+        bad and `decode_sanity_check` is on."""
+        import numpy as np
+
+        from ..ops import ans_ops
+        strings = np.asarray(strings, dtype=object)
+        shape = tuple(strings.shape)
+        flat = [bytes(s) for s in strings.reshape(-1)]
+        if flat_indexes is not None:
+            flat_indexes = flat_indexes.reshape(len(flat), -1)
+        symbols, ok = ans_ops.ans_decode(flat, self.cdf, (len(flat), elems), flat_indexes, self.ans_lanes)
+        if getattr(self, "decode_sanity_check", True) and not bool(ok.all()):
+            raise RuntimeError("Sanity check failed.")
+        return symbols, shape
 
     # how compress() / decompress() and their `*_many` forms end in every model that codes through gen_ops handles
     @staticmethod
@@ -88,6 +140,8 @@ class ContinuousEntropyModelBase(torch.nn.Module, metaclass=abc.ABCMeta):
     expected_grads = property(lambda self: self._expected_grads)
     laplace_tail_mass = property(lambda self: self._laplace_tail_mass)
     coding_rank = property(lambda self: self._coding_rank)
+    coder = property(lambda self: self._coder)
+    ans_lanes = property(lambda self: self._ans_lanes)
     compression = property(lambda self: self._compression)
     stateless = property(lambda self: self._stateless)
     tail_mass = property(lambda self: self._tail_mass)

@@ -24,7 +24,9 @@ class ContinuousBatchedEntropyModel(continuous_base.ContinuousEntropyModelBase):
                  expected_grads=False, tail_mass=2 ** -8, range_coder_precision=12,
                  bottleneck_dtype=None, prior_shape=None, cdf=None, cdf_offset=None,
                  cdf_shapes=None, offset_heuristic=True, quantization_offset=None,
-                 decode_sanity_check=True, laplace_tail_mass=0):
+                 decode_sanity_check=True, laplace_tail_mass=0, coder="range", ans_lanes=64):
+        """`coder`: "range" (the reference's bytes) or "ans", the interleaved rANS format of ops.ans_ops with
+        `ans_lanes` coder states per stream: other bytes, the same symbols."""
         if (prior is None) == (prior_shape is None):
             raise ValueError("Either `prior` or `prior_shape` must be provided.")
         if (prior is None) + (cdf_shapes is None) + (cdf is None) != 2:
@@ -35,7 +37,8 @@ class ContinuousBatchedEntropyModel(continuous_base.ContinuousEntropyModelBase):
             raise ValueError("`prior` must be a (batch of) scalar distribution(s).")
         super().__init__(coding_rank=coding_rank, compression=compression, stateless=stateless,
                          expected_grads=expected_grads, tail_mass=tail_mass,
-                         bottleneck_dtype=bottleneck_dtype, laplace_tail_mass=laplace_tail_mass)
+                         bottleneck_dtype=bottleneck_dtype, laplace_tail_mass=laplace_tail_mass, coder=coder,
+                         ans_lanes=ans_lanes)
         self._prior = prior
         self._offset_heuristic = bool(offset_heuristic)
         self._prior_shape = torch.Size(prior_shape if prior is None else prior.batch_shape)
@@ -145,20 +148,23 @@ class ContinuousBatchedEntropyModel(continuous_base.ContinuousEntropyModelBase):
             raise ValueError("compress_many: all bottlenecks must have the same shape")
         return bottlenecks, shape[:len(shape) - self.coding_rank] if self.coding_rank else shape
 
+    def _symbols(self, b):
+        """continuous_batched.py:370-383 in tensor ops: the coder's int32 symbols of one batch, shaped like it."""
+        cdf_offset, _, qn = self._device_tables(b.device)
+        channels = int(self.prior_shape.numel())
+        sym = torch.round(b if qn is None else b - qn).to(torch.int32)
+        iid = b.shape[:b.dim() - len(self.prior_shape)]
+        return (sym.reshape(tuple(iid) + (channels,)) - cdf_offset).reshape(b.shape).contiguous()
+
     def _encode(self, handles, bottlenecks):
         """continuous_batched.py:370-383 for one batch per handle, ONE coder launch for all of them -> the handles, not
         finalized."""
-        cdf_offset, qoff, qn = self._device_tables(handles[0].device)
+        cdf_offset, qoff, _ = self._device_tables(handles[0].device)
         channels = int(self.prior_shape.numel())
         if self.fused and bottlenecks[0].dtype in _DTYPE_CODE:
             gen_ops.encode_values(handles, bottlenecks, cdf_offset, qoffset=qoff, channels=channels)
         else:
-            symbols = []
-            for b in bottlenecks:
-                sym = torch.round(b if qn is None else b - qn).to(torch.int32)
-                iid = b.shape[:b.dim() - len(self.prior_shape)]
-                symbols.append((sym.reshape(tuple(iid) + (channels,)) - cdf_offset).reshape(b.shape).contiguous())
-            gen_ops.encode_symbols(handles, symbols)
+            gen_ops.encode_symbols(handles, [self._symbols(b) for b in bottlenecks])
         for h, b in zip(handles, bottlenecks):
             h.coder_inputs = (b, None)           # what the coder read (values, table indexes): for checkers
         return handles
@@ -193,6 +199,10 @@ class ContinuousBatchedEntropyModel(continuous_base.ContinuousEntropyModelBase):
         the model's tables produces): "a stream outgrew its output slab".  The plain call (`device_result=False`)
         repeats itself with the bound that cannot be exceeded instead; call it for such data."""
         bottlenecks, batch_shape = self._batches([bottleneck])
+        if self.coder == "ans":
+            if device_result:
+                self._range_only("compress(device_result=True)")
+            return self._ans_compressed(self._symbols(bottlenecks[0]), None, batch_shape)
         handle = gen_ops.create_range_encoder(batch_shape, self.cdf, deferred_errors=device_result)
         return self._compressed(self._encode([handle], bottlenecks)[0], device_result)
 
@@ -204,6 +214,17 @@ class ContinuousBatchedEntropyModel(continuous_base.ContinuousEntropyModelBase):
         uint8 result of EntropyDecodeFinalize (1 = the end-of-stream check passed) for the caller to test
         once the stream has run."""
         self._check_compression()
+        if self.coder == "ans":
+            if defer_sanity:
+                self._range_only("decompress(defer_sanity=True)")
+            broadcast_shape = tuple(int(s) for s in broadcast_shape)
+            channels = int(self.prior_shape.numel())
+            elems = int(torch.Size(broadcast_shape).numel()) * channels
+            symbols, shape = self._ans_decompressed(strings, elems, None)
+            cdf_offset, _, qn = self._device_tables(symbols.device)
+            out = (symbols.reshape(-1, channels) + cdf_offset).reshape(shape + broadcast_shape + tuple(self.prior_shape))
+            out = out.to(self.bottleneck_dtype)
+            return out if qn is None else out + qn
         decoder = gen_ops.create_range_decoder(strings, self.cdf)
         return self._decompressed(decoder, self._decode([decoder], broadcast_shape)[0], defer_sanity)
 
@@ -215,6 +236,7 @@ class ContinuousBatchedEntropyModel(continuous_base.ContinuousEntropyModelBase):
         finalized encoder handle per batch (`gen_ops.fetch_strings`, `decompress_many`).  Same strings as
         compress() batch by batch.  (Like `compress(device_result=True)`: a stream of more than ~16-20 bits per
         symbol outgrows the speculative slab; `fetch_strings` then codes that handle again, synchronously.)"""
+        self._range_only("compress_many")
         bottlenecks, batch_shape = self._batches(bottlenecks)
         if not bottlenecks:
             return []
@@ -227,6 +249,7 @@ class ContinuousBatchedEntropyModel(continuous_base.ContinuousEntropyModelBase):
         decoder launch for all of them; returns ([values per batch], ok) with `ok` the device-resident
         EntropyDecodeFinalize flags [len(handles), *batch_shape] — nothing is read back."""
         self._check_compression()
+        self._range_only("decompress_many")
         decoders = gen_ops.create_range_decoders(handles, self.cdf, mode="throughput")
         if not decoders:
             return [], None
@@ -236,7 +259,8 @@ class ContinuousBatchedEntropyModel(continuous_base.ContinuousEntropyModelBase):
         config = super().get_config()
         config.update(prior_shape=tuple(map(int, self.prior_shape)),
                       offset_heuristic=self.offset_heuristic,
-                      quantization_offset=self.quantization_offset is not None)
+                      quantization_offset=self.quantization_offset is not None,
+                      coder=self.coder, ans_lanes=self.ans_lanes)
         return config
 
     @classmethod

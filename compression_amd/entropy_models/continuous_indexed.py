@@ -18,7 +18,9 @@ class ContinuousIndexedEntropyModel(continuous_base.ContinuousEntropyModelBase):
     def __init__(self, prior_fn, index_ranges, parameter_fns, coding_rank, channel_axis=-1,
                  compression=False, stateless=False, expected_grads=False, tail_mass=2 ** -8,
                  range_coder_precision=12, bottleneck_dtype=None, prior_dtype=torch.float32,
-                 decode_sanity_check=True, laplace_tail_mass=0):
+                 decode_sanity_check=True, laplace_tail_mass=0, coder="range", ans_lanes=64):
+        """`coder`: "range" (the reference's bytes) or "ans", the interleaved rANS format of ops.ans_ops with
+        `ans_lanes` coder states per stream: other bytes, the same symbols."""
         if not callable(prior_fn):
             raise TypeError("`prior_fn` must be a class or factory function.")
         for name, fn in parameter_fns.items():
@@ -28,7 +30,8 @@ class ContinuousIndexedEntropyModel(continuous_base.ContinuousEntropyModelBase):
                 raise TypeError(f"`parameter_fns['{name}']` must be callable.")
         super().__init__(coding_rank=coding_rank, compression=compression, stateless=stateless,
                          expected_grads=expected_grads, tail_mass=tail_mass,
-                         bottleneck_dtype=bottleneck_dtype, laplace_tail_mass=laplace_tail_mass)
+                         bottleneck_dtype=bottleneck_dtype, laplace_tail_mass=laplace_tail_mass, coder=coder,
+                         ans_lanes=ans_lanes)
         self._index_ranges = tuple(int(r) for r in index_ranges)
         if not self.index_ranges:
             raise ValueError("`index_ranges` must have at least one element.")
@@ -206,6 +209,12 @@ class ContinuousIndexedEntropyModel(continuous_base.ContinuousEntropyModelBase):
         """continuous_indexed.py:355-386.  `device_result=True`: see
         `ContinuousBatchedEntropyModel.compress` (nothing read back, returns the finalized handle)."""
         bottlenecks, flats, batch_shape = self._batches([bottleneck], [indexes])
+        if self.coder == "ans":
+            if device_result:
+                self._range_only("compress(device_result=True)")
+            cdf_offset = self._device_offsets(bottlenecks[0].device)
+            symbols = (torch.round(bottlenecks[0]).to(torch.int32) - cdf_offset[flats[0].long()]).contiguous()
+            return self._ans_compressed(symbols, flats[0], batch_shape)
         handle = gen_ops.create_range_encoder(batch_shape, self.cdf, deferred_errors=device_result)
         return self._compressed(self._encode([handle], bottlenecks, flats)[0], device_result)
 
@@ -215,6 +224,14 @@ class ContinuousIndexedEntropyModel(continuous_base.ContinuousEntropyModelBase):
         `ContinuousBatchedEntropyModel.decompress`)."""
         self._check_compression()
         flats = self._flats([indexes])
+        if self.coder == "ans":
+            if defer_sanity:
+                self._range_only("decompress(defer_sanity=True)")
+            shape = tuple(flats[0].shape)
+            decode_shape = shape[len(shape) - self.coding_rank:] if self.coding_rank else ()
+            symbols, _ = self._ans_decompressed(strings, int(torch.Size(decode_shape).numel()), flats[0])
+            cdf_offset = self._device_offsets(symbols.device)
+            return (symbols.reshape(shape) + cdf_offset[flats[0].long()]).to(self.bottleneck_dtype)
         decoder = gen_ops.create_range_decoder(strings, self.cdf)
         return self._decompressed(decoder, self._decode([decoder], flats)[0], defer_sanity)
 
@@ -224,6 +241,7 @@ class ContinuousIndexedEntropyModel(continuous_base.ContinuousEntropyModelBase):
         their parallel expansion pass; the serial chain of all batches' streams is one small grid).  Nothing is read
         back: one finalized encoder handle per batch (`gen_ops.fetch_strings`, `decompress_many`); same strings as
         compress() batch by batch.  `indexes`: one tensor per batch (continuous_indexed.py:355-386)."""
+        self._range_only("compress_many")
         bottlenecks, flats, batch_shape = self._batches(bottlenecks, indexes)
         if not bottlenecks:
             return []
@@ -235,6 +253,7 @@ class ContinuousIndexedEntropyModel(continuous_base.ContinuousEntropyModelBase):
         """decompress() for the handles of compress_many: one decoder launch per stage for all of them; returns
         ([values per batch], ok) with `ok` the device-resident EntropyDecodeFinalize flags — nothing is read back."""
         self._check_compression()
+        self._range_only("decompress_many")
         handles = list(handles)
         if not handles:
             return [], None
@@ -256,7 +275,7 @@ class LocationScaleIndexedEntropyModel(ContinuousIndexedEntropyModel):
 
     def __init__(self, prior_fn, num_scales, scale_fn, coding_rank, compression=False,
                  stateless=False, expected_grads=False, tail_mass=2 ** -8, range_coder_precision=12,
-                 bottleneck_dtype=None, prior_dtype=torch.float32, laplace_tail_mass=0):
+                 bottleneck_dtype=None, prior_dtype=torch.float32, laplace_tail_mass=0, coder="range", ans_lanes=64):
         num_scales = int(num_scales)
         super().__init__(
             prior_fn=prior_fn, index_ranges=(num_scales,),
@@ -264,7 +283,7 @@ class LocationScaleIndexedEntropyModel(ContinuousIndexedEntropyModel):
             coding_rank=coding_rank, channel_axis=None, compression=compression,
             stateless=stateless, expected_grads=expected_grads, tail_mass=tail_mass,
             range_coder_precision=range_coder_precision, bottleneck_dtype=bottleneck_dtype,
-            prior_dtype=prior_dtype, laplace_tail_mass=laplace_tail_mass)
+            prior_dtype=prior_dtype, laplace_tail_mass=laplace_tail_mass, coder=coder, ans_lanes=ans_lanes)
 
     def forward(self, bottleneck, scale_indexes, loc=None, training=True, noise=None):
         if loc is None:

@@ -10,6 +10,7 @@ from .. import distributions, entropy_models, layers
 from ..layers import functional
 from ..ops import image_ops
 from ..pipeline import inline_lane
+from .codec_io import set_model_coder
 
 __all__ = ["AnalysisTransform", "SynthesisTransform", "BLS2017Model"]
 
@@ -56,12 +57,18 @@ class BLS2017Model(torch.nn.Module):
     # layout of the .tfci container: [string, x_shape, y_shape] (bls2017.py:164-176, 280-283)
     num_strings, num_packed = 1, 3
 
-    def __init__(self, lmbda=0.01, num_filters=128, compute_dtype=torch.float32, distortion="mse"):
+    def __init__(self, lmbda=0.01, num_filters=128, compute_dtype=torch.float32, distortion="mse", coder="range",
+                 ans_lanes=64):
         """`distortion`: "mse" (the reference's scripts) or "ms-ssim": the loss is then
         bpp + lmbda * mean over the batch of (1 - ssim_multiscale(x, x_hat, 255)) and forward()'s third value is that
         distortion.  The `-opt-msssim` models the reference publishes results for were trained this way; its model
-        scripts themselves do not carry the switch."""
+        scripts themselves do not carry the switch.
+
+        `coder`: "range" (strings a reference model of the same weights reads) or "ans": the interleaved rANS format
+        of ops.ans_ops with `ans_lanes` states per stream — other bytes in the same container, the same
+        reconstruction.  Stored with the model (codec_io.set_model_coder)."""
         super().__init__()
+        set_model_coder(self, coder, ans_lanes)
         if distortion not in ("mse", "ms-ssim"):
             raise ValueError(f'distortion must be "mse" or "ms-ssim", got {distortion!r}')
         self.lmbda = lmbda
@@ -92,7 +99,8 @@ class BLS2017Model(torch.nn.Module):
     def init_compression(self):
         """What `fit()` does after training (bls2017.py:157-162): fix the range-coding tables."""
         self.entropy_model = entropy_models.ContinuousBatchedEntropyModel(
-            self.prior, coding_rank=3, compression=True, bottleneck_dtype=self.compute_dtype)
+            self.prior, coding_rank=3, compression=True, bottleneck_dtype=self.compute_dtype, coder=self.coder,
+            ans_lanes=self.ans_lanes)
         return self
 
     def _latent(self, x):

@@ -10,6 +10,7 @@ from .. import distributions, entropy_models, layers
 from ..layers import functional
 from ..ops import image_ops
 from ..pipeline import inline_lane
+from .codec_io import set_model_coder
 
 __all__ = ["AnalysisTransform", "SynthesisTransform", "HyperAnalysisTransform",
            "HyperSynthesisTransform", "BMSHJ2018Model"]
@@ -85,12 +86,15 @@ class BMSHJ2018Model(torch.nn.Module):
     num_strings, num_packed = 2, 5
 
     def __init__(self, lmbda=0.01, num_filters=192, num_scales=64, scale_min=0.11, scale_max=256.0,
-                 compute_dtype=torch.float32, distortion="mse"):
+                 compute_dtype=torch.float32, distortion="mse", coder="range", ans_lanes=64):
         """`distortion`: "mse" (the reference's scripts) or "ms-ssim": the loss is then
         bpp + lmbda * mean over the batch of (1 - ssim_multiscale(x, x_hat, 255)) and forward()'s third value is that
         distortion.  The `-opt-msssim` models the reference publishes results for were trained this way; its model
-        scripts themselves do not carry the switch."""
+        scripts themselves do not carry the switch.
+
+        `coder` / `ans_lanes`: see BLS2017Model; both entropy models take them."""
         super().__init__()
+        set_model_coder(self, coder, ans_lanes)
         if distortion not in ("mse", "ms-ssim"):
             raise ValueError(f'distortion must be "mse" or "ms-ssim", got {distortion!r}')
         self.distortion = distortion
@@ -109,9 +113,10 @@ class BMSHJ2018Model(torch.nn.Module):
     def _models(self, compression):
         em = entropy_models.LocationScaleIndexedEntropyModel(
             distributions.NoisyNormal, self.num_scales, self.scale_fn, coding_rank=3,
-            compression=compression, bottleneck_dtype=self.compute_dtype)
+            compression=compression, bottleneck_dtype=self.compute_dtype, coder=self.coder, ans_lanes=self.ans_lanes)
         side = entropy_models.ContinuousBatchedEntropyModel(
-            self.hyperprior, coding_rank=3, compression=compression, bottleneck_dtype=self.compute_dtype)
+            self.hyperprior, coding_rank=3, compression=compression, bottleneck_dtype=self.compute_dtype,
+            coder=self.coder, ans_lanes=self.ans_lanes)
         return em, side
 
     def forward(self, x, training=True):

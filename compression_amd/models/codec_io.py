@@ -15,7 +15,7 @@ from ..ops import image_ops
 from ..util import PackedTensors
 
 __all__ = ["read_png", "write_png", "compress_file", "decompress_file", "container_dtypes", "load_checkpoint",
-           "main"]
+           "set_model_coder", "main"]
 
 
 def read_png(filename) -> torch.Tensor:
@@ -91,6 +91,18 @@ def decompress_file(model, input_file, output_file=None):
     return x_hat
 
 
+def set_model_coder(model, coder, ans_lanes=64):
+    """Sets a model's `coder` ("range" | "ans") and `ans_lanes`.  The choice is stored with the model: an "ans" model
+    carries the buffer `_ans_lanes` in its state_dict, a "range" model carries nothing, so its state_dict is what it
+    was before the option existed and a file written then loads as "range"."""
+    from ..entropy_models.continuous_base import check_coder
+    model.coder, model.ans_lanes = check_coder(coder, ans_lanes)
+    model._buffers.pop("_ans_lanes", None)
+    if model.coder == "ans":
+        model.register_buffer("_ans_lanes", torch.tensor(model.ans_lanes, dtype=torch.int32))
+    return model
+
+
 def build_lazy_parameters(model, state_dict):
     """A GDN layer inside a convolution creates `reparam_beta` / `reparam_gamma` on its first call, so a model that
     has not run yet lacks them and a trained state_dict has them: they are created here, with the stored sizes."""
@@ -111,6 +123,12 @@ def load_checkpoint(model, state_dict):
     entropy models are created first (so the buffers exist), their buffers take the stored shapes, then
     everything is loaded strictly.  A checkpoint without tables gets them built from its prior."""
     build_lazy_parameters(model, state_dict)
+    if hasattr(model, "coder"):
+        # the coder the file was written with (none stored: "range"); the entropy models are created below
+        if "_ans_lanes" in state_dict:
+            set_model_coder(model, "ans", int(state_dict["_ans_lanes"]))
+        else:
+            set_model_coder(model, "range")
     has_tables = any(k.rsplit(".", 1)[-1] in ("_cdf", "_cdf_offset") for k in state_dict)
     if not has_tables:
         model.load_state_dict(state_dict)
@@ -129,7 +147,8 @@ def load_checkpoint(model, state_dict):
 # The constructor arguments a model may have beyond lmbda and num_filters, as flags of `train`
 # (bmshj2018.py:449-457, ms2020.py:619-639); the defaults are the constructor's own.
 MODEL_FLAGS = {"num_scales": int, "scale_min": float, "scale_max": float, "latent_depth": int,
-               "hyperprior_depth": int, "num_slices": int, "max_support_slices": int, "stream_positions": int}
+               "hyperprior_depth": int, "num_slices": int, "max_support_slices": int, "stream_positions": int,
+               "coder": str, "ans_lanes": int}
 
 
 def compute_dtype_of(precision_policy):

@@ -1318,6 +1318,42 @@ int tfc_mixture_bits_backward(const void* y_hat, const float* logits, const floa
                               int dtype, int64_t units, int64_t elems, const float* gbits, void* dy, float* dlogits,
                               float* dloc, float* dscale, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Interleaved rANS: one stream, up to 64 coder states at once              */
+/* ------------------------------------------------------------------------ */
+/* A second, opt-in stream format next to the range coder (csrc/ans_core.h): `lanes` rANS states
+ * (a power of two in [1, 64]) code `lanes` consecutive elements of one stream per step.  These calls play the role of
+ * EntropyEncodeIndex / EntropyEncodeChannel + Finalize and their decoding counterparts
+ * (cc/kernels/range_coder_kernels.cc:191-322,360-471): the same `lookup` tables (a tfc_tables), the same index and
+ * channel modes, the same escape mapping of values outside a row with a negative header.  THE BYTES ARE NOT THE
+ * REFERENCE'S: the format is this library's own, and `lanes` is part of it (the decoder has to be given the encoder's).
+ * value DEV int32 [streams, elems], the row's offset already subtracted; index DEV int32 [streams, elems], or NULL for
+ * channel mode (element j of a stream takes row j mod rows).  One wave per stream; one call takes at most 2^23
+ * streams of at most 2^27 elements.  Bad scalar arguments are refused on the host before anything is launched. */
+
+/* Bytes of the `blob` tfc_ans_encode needs: per stream 4 words per element (4 calls of one word each) and the
+ * states; -1 and tfc_last_error on bad sizes. */
+int64_t tfc_ans_blob_capacity(int64_t streams, int64_t elems, int lanes);
+
+/* Writes the strings back to back into blob DEV (tfc_ans_blob_capacity bytes) and offsets DEV int64 [streams + 1];
+ * *overflow DEV uint32 is 0 unless a stream outgrew its slab (an internal error); status DEV int32 [streams] is 0, or
+ * has bit 0 set where a value lay outside a row without escape (or on a symbol of zero width) and bit 1 where an index
+ * named no row: that stream's string is not to be used.  Enqueues only, nothing is read back. */
+int tfc_ans_encode(const tfc_tables* tables, const int32_t* index, const int32_t* value, int64_t streams,
+                   int64_t elems, int lanes, uint8_t* blob, int64_t* offsets, uint32_t* overflow, int32_t* status,
+                   void* stream);
+
+/* The inverse: string j (blob, offsets DEV int64 [nstrings + 1]) is stream stream_index[j] (DEV int32 [nstrings], or
+ * NULL when nstrings == streams and string j is stream j; no stream twice: the caller's duty).  A decoded stream's
+ * values go to its row of out DEV int32 [streams, elems]; the rest of out is left alone.  ok DEV uint8 [nstrings] is 1
+ * only where the string has its states and an even rest, every word was consumed and none was missing, and every
+ * state ended at 2^16; 0 as well where stream_index[j] names no stream (nothing else is written then).  Words behind
+ * the end of a string read as zero, a symbol search cannot leave its row: whatever the bytes are, nothing outside the
+ * stream's own outputs is written. */
+int tfc_ans_decode(const tfc_tables* tables, const uint8_t* blob, const int64_t* offsets, const int32_t* stream_index,
+                   int64_t nstrings, const int32_t* index, int64_t streams, int64_t elems, int lanes, int32_t* out,
+                   uint8_t* ok, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
