@@ -1107,6 +1107,14 @@ constexpr unsigned int kPipeFinal = 0x80000000u;
 #define TFC_PIPE_RELEASE 64
 #endif
 constexpr unsigned int kPipeRelease = TFC_PIPE_RELEASE;      // blocks between two releases of the chain's rows
+// Rows of a parse tile (dec_parse_kernel).  The parse reads a group's block records at its tiles' edges only — the record
+// of a tile's first block and of the block behind its last row — and at the chain's last row, so the chain writes the
+// record of every (kParseRows / kPipeBlock)-th block and the final one; the other slots of `posrec` stay undefined.  A
+// release publishes whole tiles: its block's record is one of those.
+constexpr int kParseRows = 128;
+constexpr unsigned int kPipeRecordEvery = kParseRows / kPipeBlock;      // blocks between two block records
+static_assert(kParseRows % kPipeBlock == 0, "a parse tile is whole blocks: its edges have block records");
+static_assert((kPipeRelease * kPipeBlock) % kParseRows == 0, "a release ends on a tile edge: its own block's record is written");
 struct PipeDecJob { const uint8_t* blob; const long long* off; const uint4* state; };
 struct PipeDecJobs {
   int64_t streams, elems;
@@ -1169,7 +1177,7 @@ struct PipeDecLds {
 // state step by step.  Fixed temporaries v104-v142; v[122:123] = (lo << 16, 0), v[124:125] = (hi << 16, 0): the low halves of
 // v122 / v124 and v123 / v125 are zeroed in the block's head and nothing in a step writes them.
 // TFC_PDEC_ABL (build switch, bits, timing experiments only — results are wrong): 1 the step stores nothing, 2 one load per
-// window request instead of five, 4 no flush of the raw rows
+// window request instead of five, 4 no flush of the raw rows, 8 no block-record store
 #ifndef TFC_PDEC_ABL
 #define TFC_PDEC_ABL 0
 #endif
@@ -1561,6 +1569,33 @@ __global__ void __launch_bounds__(512) dec_chain_kernel(const PipeDecJobs jobs, 
     }
     staged = false;
   };
+  // The steady-state loop reads the staged rows into registers right behind the block that wrote them (and behind its
+  // step-by-step repeat): the rows are complete there, and the flag test, the position update and the park cover the LDS
+  // round trip, which a read in front of the stores — at the top of the next memory phase — had nothing to cover.  The
+  // stores stay in that phase: behind the park, which waits on vmcnt, and in front of the requests.
+  struct StagedRows { uint4 v[L::kStage / 1024u]; };
+  auto read_staged = [&](StagedRows& sv) __attribute__((always_inline)) {
+#pragma unroll
+    for (unsigned int j = 0; j < L::kStage / 1024u; ++j) {
+#if TFC_PDEC_ABL & 4
+      asm("" : "=v"(sv.v[j].x), "=v"(sv.v[j].y), "=v"(sv.v[j].z), "=v"(sv.v[j].w));
+#else
+      sv.v[j] = *reinterpret_cast<const uint4*>(lanes_lds + stg_off + 1024u * j + 16u * lane);
+#endif
+    }
+  };
+  auto flush_read = [&](const StagedRows& sv) __attribute__((always_inline)) {
+    if (!staged) return;
+#if !(TFC_PDEC_ABL & 4)
+    // (inside the loop the staged block is the one before row k: from staged_k, the address took a vector register and
+    // two copies on the back edge)
+    unsigned char* dst = reinterpret_cast<unsigned char*>(raw + static_cast<size_t>(k - kPipeBlock) * 64) + 16u * lane;
+#pragma unroll
+    for (unsigned int j = 0; j < L::kStage / 1024u; ++j)
+      lanes_gstore16(dst + 1024u * j, make_uint2(sv.v[j].x, sv.v[j].y), make_uint2(sv.v[j].z, sv.v[j].w));
+#endif
+    staged = false;
+  };
 
   // the row of element `pos` (channel mode: pw is kept inside the directory)
   auto load_row = [&]() {
@@ -1740,20 +1775,25 @@ __global__ void __launch_bounds__(512) dec_chain_kernel(const PipeDecJobs jobs, 
   };
   // memory phase of a block, first half: send the previous block's raw rows off, decide — THE rule, its one copy —
   // which windows the wave requests from the current positions
-  auto phase_decide = [&](WindowRefill& rq) __attribute__((always_inline)) {
+  // (flush_rows: flush, or the steady-state loop's flush_read of the rows it holds in registers)
+  auto phase_decide = [&](WindowRefill& rq, auto flush_rows) __attribute__((always_inline)) {
 #if TFC_PIPE_TIMING
     const unsigned long long tm1 = clock64();
 #endif
-    flush();
-    if (k != 0u && (k / kPipeBlock) % kPipeRelease == 0u) {
-      // the rows so far (and their block records) to the parse running next to this kernel: a release costs the wave a
-      // wait for its stores, so it is rare
+    flush_rows();
+    if ((k / kPipeBlock) % kPipeRecordEvery == 0u) {
+      // A block record where the parse reads one (kPipeRecordEvery; wave-uniform): elements STARTED before row k (an
+      // escape code in progress has its first row behind us)
+#if !(TFC_PDEC_ABL & 8)
       posrec[static_cast<size_t>(k / kPipeBlock) * 64] = pos + (M != 0 ? 1u : 0u);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      if (lane == 0u) __hip_atomic_store(&pa.progress[gi], k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+      if (k != 0u && (k / kPipeBlock) % kPipeRelease == 0u) {
+        // the rows so far (and their block records, this block's among them) to the parse running next to this kernel: a
+        // release costs the wave a wait for its stores, so it is rare
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        if (lane == 0u) __hip_atomic_store(&pa.progress[gi], k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
     }
-    // elements STARTED before row k (an escape code in progress has its first row behind us)
-    posrec[static_cast<size_t>(k / kPipeBlock) * 64] = pos + (M != 0 ? 1u : 0u);
     ++n_phase;
     rq.code_pos = cw.base + (cp - cw_off);
     rq.code_pending = !__all((cp - cw_off) + kWindowNeed <= 8u * L::kWords);
@@ -1791,7 +1831,7 @@ __global__ void __launch_bounds__(512) dec_chain_kernel(const PipeDecJobs jobs, 
 #endif
   };
   auto memory_phase = [&](WindowRefill& rq) __attribute__((always_inline)) {
-    phase_decide(rq);
+    phase_decide(rq, flush);
     phase_request(rq);
   };
   // kPipeBlock hand-scheduled steps of the lanes in EXEC
@@ -1841,9 +1881,16 @@ __global__ void __launch_bounds__(512) dec_chain_kernel(const PipeDecJobs jobs, 
     // a block whose verification fails is repeated on the spot, step by step.
     if (lds0 == 0u && row_loaded && (INDEXED || static_cast<unsigned int>(la.ntab) >= kPipeBlock)) {
       // (M > -16: a lane's unary prefix cannot reach its 31st zero — where the reference stops counting — inside a block)
+      // (The staged rows are the loop's own: rows the general body staged leave in front of it, and the registers are
+      // defined by an empty statement like the words of a window that is not requested — no value from outside the loop
+      // to merge with.)
+      flush();
+      StagedRows sv;
+#pragma unroll
+      for (unsigned int j = 0; j < L::kStage / 1024u; ++j) asm("" : "=v"(sv.v[j].x), "=v"(sv.v[j].y), "=v"(sv.v[j].z), "=v"(sv.v[j].w));
       while (__all(!live || (pos + kPipeBlock <= elems && M > -16)) && k + kPipeBlock <= static_cast<unsigned int>(pa.rows)) {
         WindowRefill rq;
-        phase_decide(rq);
+        phase_decide(rq, [&]() __attribute__((always_inline)) { flush_read(sv); });
         auto block = [&]() __attribute__((always_inline)) {
           const unsigned int D0 = D, s10 = s1, cp0 = cp, pw0 = pw;
           const int M0 = M;
@@ -1852,6 +1899,7 @@ __global__ void __launch_bounds__(512) dec_chain_kernel(const PipeDecJobs jobs, 
           // (every lane, also those of a last group that have no stream — they decode zeros from their own windows and
           // are ignored: under `if (live)` the compiler copied the block's nine operands twice)
           fast_block(flag);
+          read_staged(sv);
           if (__builtin_expect(__any(live && flag != 0u), 0)) {
             // A verification failed somewhere in the block (the quotient estimate one off: ~1e-5 of the symbols, 2.5 % of the
             // blocks): again from the saved state, one hand-scheduled step at a time, and only the step that fails again
@@ -1872,6 +1920,7 @@ __global__ void __launch_bounds__(512) dec_chain_kernel(const PipeDecJobs jobs, 
                 if (!INDEXED) pw -= pw >= dir_end ? dir_end : 0u;
               }
             }
+            read_staged(sv);         // (the repeat wrote the rows again)
           } else {
             pos += (pw - pw0) / (INDEXED ? 2u : 16u);
             if (!INDEXED) pw -= pw >= dir_end ? dir_end : 0u;      // (a block is at most one turn of the directory: ntab >= kPipeBlock)
@@ -1999,7 +2048,7 @@ __global__ void __launch_bounds__(512) dec_chain_kernel(const PipeDecJobs jobs, 
 // stream's column 64 rows at a time; the rows that start an element (M = 0) are numbered by a ballot prefix from
 // the block records of the chain, an escape symbol collects its value from the bit rows behind it, and the
 // elements of a stream leave in order (coalesced along the stream).
-constexpr int kParseRows = 128;
+// (kParseRows: with the block records' rule, in front of dec_chain_kernel)
 constexpr unsigned int kParseMargin = 96;     // rows behind a tile the parse next to the chain waits for
 
 constexpr int kParseEscTables = 2048;     // escape symbols of up to this many tables are staged in LDS
