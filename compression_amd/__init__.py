@@ -34,6 +34,7 @@ from .ops.mixture_ops import (mixture_bits, mixture_bits_reference, mixture_cdf,
                               mixture_decode, mixture_encode, MixtureStrings)
 from .ops.ans_ops import (AnsStrings, ans_decode, ans_decode_reference, ans_encode, ans_encode_reference,  # noqa: F401
                           strings_from_blob)
+from .ops.arm_ops import arm_bits, arm_bits_reference, arm_context_offsets  # noqa: F401
 from .ops.round_ops import round_st, soft_round, soft_round_conditional_mean, soft_round_inverse  # noqa: F401
 from .datasets import *  # noqa: F401,F403
 from .datasets.clip_dataset import ClipDataset  # noqa: F401

@@ -19,3 +19,5 @@ from .scctx_ops import (SpaceChannelParams, SpaceChannelScan, scctx_decode, scct
                         scctx_parameters_reference, scctx_place, scctx_scan, scctx_scan_reference)
 from .flow_ops import (gaussian_scale_space, gaussian_scale_space_reference, scale_space_predict,  # noqa: F401
                        scale_space_predict_reference, scale_space_warp, scale_space_warp_reference)
+from . import arm_ops  # noqa: E402
+from .arm_ops import arm_bits, arm_bits_reference, arm_context_offsets  # noqa: F401,E402

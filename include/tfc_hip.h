@@ -1354,6 +1354,34 @@ int tfc_ans_decode(const tfc_tables* tables, const uint8_t* blob, const int64_t*
                    int64_t nstrings, const int32_t* index, int64_t streams, int64_t elems, int lanes, int32_t* out,
                    uint8_t* ok, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Autoregressive-MLP entropy model (the ARM of the overfitted codecs:      */
+/* Ladune et al., Cool-chic; Kim et al., C3)                                */
+/* ------------------------------------------------------------------------ */
+
+/* The definition is this project's own; parity with anyone's checkpoints is unpinned.  Per pixel (i, j) of grid n:
+ *   h0[k] = y[n, i + DI[k], j + DJ[k]], k < context   (csrc/arm_params.h: the causal half-plane by distance; 0 outside)
+ *   h <- relu(h W_l + b_l) + h, l < layers;   (mu, s) = h W_out + b_out;   scale = exp(clamp(s, -4.6, 5))
+ *   p = the Laplace(mu, scale) mass of [y - 1/2, y + 1/2];   bits[n] = sum over the grid of -log2(max(p, 2^-16))
+ * y DEV f32 [batch, height, width]; w [layers, context, context], b [layers, context], w_out [context, 2], b_out [2] DEV
+ * f32; bits DEV f32 [batch]; mu and scale DEV f32 [batch, height, width], or both NULL.  context is 8, 16, 24 or 32,
+ * layers 1..3, batch 1..65535, height * width < 2^31: checked on the host before any launch.  One fused launch (no
+ * [pixels, context] tensor exists) and a one-workgroup-per-grid sum behind it.  Every output is one fmaf chain in
+ * ascending k and the sums have a fixed order: bits[n] does not depend on batch, and is bit-identical from call to
+ * call. */
+int tfc_arm_bits_forward(const float* y, const float* w, const float* b, const float* w_out, const float* b_out,
+                         int64_t batch, int64_t height, int64_t width, int context, int layers, float* bits,
+                         float* mu, float* scale, void* stream);
+/* Its gradients for g_bits = dL/dbits (DEV f32 [batch]); the forward is recomputed.  d_y DEV f32 [batch, height, width]
+ * or NULL: through the centre and through every pixel that reads it as context, gathered (not scattered) from a
+ * [batch, context + 1, height, width] temporary.  d_params DEV f32 [layers context^2 + layers context + 2 context + 2]
+ * or NULL: dW, db, dW_out, db_out one after the other.  The gradient is zero where p lies under the floor and, for s,
+ * outside the clamp.  No atomics: at most 512 workgroups hold one partial parameter gradient each, merged in ascending
+ * order; bit-identical from call to call. */
+int tfc_arm_bits_backward(const float* y, const float* w, const float* b, const float* w_out, const float* b_out,
+                          const float* g_bits, int64_t batch, int64_t height, int64_t width, int context, int layers,
+                          float* d_y, float* d_params, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
